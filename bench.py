@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: sampled frames/s (whole job) of the DDPM sampling hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config NAME]
+    python bench.py --gpus N --steps K --warmup W [--config NAME] [--dump-outputs DIR] [--full]
 
 A "step" is ONE full sampling job over one batch per GPU.  Default workload = BASELINE.json configs[1]: `ddpm_sampler` with
 subsample=100 (100 UNet forwards + fused updates + the denoise forward = 101 forwards) on smmnist_DDPM_big5 with ngf=96, 64x64,
@@ -10,6 +10,11 @@ step per GPU.  For the autoregressive config (`--config cityscapes_big`: num_fra
 `video_gen` block loop (6 sampler calls, cond shift on the device) and frames = B * 28 KEPT frames.
 `value` = frames of all ranks / max-over-ranks wall time (weak scaling: per-GPU batch fixed).  Inputs are resident in HBM before
 the timed region.  One JSON line on stdout (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the line (headline leg, its roofline block from the instrumented
+forward inside the timed region).  `--full` adds what takes runs of its own: the B = 1 self-check of row 0 (`valid: false`, exit
+code 3, when it fails), the reported-only f16x2 leg and the CPU baseline.  `--dump-outputs DIR` writes the frames the headline
+leg's last timed step returned as DIR/frames.npy (float32; a seeded sample of rows, DIR/frames_rows.npy, above 64 MB).
 
 `--gpus N` with N > 1 and no launcher (WORLD_SIZE unset) re-executes itself under `python -m torch.distributed.run` with one
 rank per GPU (RCCL); under the driver's own torchrun launch it just reads RANK / LOCAL_RANK / WORLD_SIZE.
@@ -311,6 +316,24 @@ def pmc_traffic(args, roofline):
                 hbm_gbs=round(tb / (roofline["avg_launch_us"] * 1e-6) / 1e9, 1))
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out_dir, frames):
+    """`--dump-outputs`: the frames one timed step returns, [rows, C * frames, S, S], as out_dir/frames.npy in float32.  Above
+    DUMP_LIMIT_BYTES a fixed sample of whole rows (seed 0, ascending) is written instead, with their indices in frames_rows.npy."""
+    import numpy as np
+    a = frames.detach().float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    row_bytes = a[:1].nbytes
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 8 * a.shape[0]) // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+        a = a[rows]
+        np.save(os.path.join(out_dir, "frames_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "frames.npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -331,13 +354,17 @@ def main():
                     "(pinned kernels: the run executes the table the parity tests check), else the autotuner measures")
     ap.add_argument("--save-tuning", default=None, help="directory: write the table of every leg there (tune_<config>_B<batch>_<arithmetic>.json)")
     ap.add_argument("--no-tune-file", action="store_true", help="ignore committed tables: let the autotuner measure")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the B = 1 self-check, the f16x2 leg and the "
+                    "CPU baseline (each can be left out again with its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, help="directory: rank 0 writes the frames of the headline leg's last timed step there as "
+                    "frames.npy (float32), so that two builds can be compared output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-selfcheck", action="store_true", help="skip the B = 1 recomputation of row 0 after the timed region (profiling runs: its "
+    ap.add_argument("--no-selfcheck", action="store_true", help="with --full: skip the B = 1 recomputation of row 0 after the timed region (profiling runs: its "
                     "101 single-sample forwards would enter the per-kernel averages of rocprofv3 --stats)")
     ap.add_argument("--dump-frames", default=None, help="file: rank 0 saves the gathered frames of the headline leg's last timed step (torch.save) "
                     "-- tests compare an N-rank job with the N = 1 job of the same global batch bit for bit")
     ap.add_argument("--no-f16x2-leg", "--no-fp32-leg", dest="no_second_leg", action="store_true",
-                    help="skip the second, reported-only timing with the two-piece fp16 kernels offered")
+                    help="with --full: skip the second, reported-only timing with the two-piece fp16 kernels offered")
     ap.add_argument("--pmc-traffic", action="store_true", help="N = 1: measure roofline.traffic IN THIS RUN -- after the timed region, two short "
                     "rocprofv3 passes of this script (--pmc FETCH_SIZE, then --pmc WRITE_SIZE; kernel-trace only, one counter per pass, 6 forwards "
                     "under the same kernel table) and (2 x FETCH + WRITE) / launches of the dominant family (MI355X_MICROARCH.md, HBM section). "
@@ -484,6 +511,8 @@ def main():
         assert torch.isfinite(frames).all() and frames.shape[0] == total and frames.shape[1] == config.data.channels * nfp
         if args.dump_frames and rank == 0 and arith_name == main_arith:
             torch.save(frames.cpu(), args.dump_frames)
+        if args.dump_outputs and rank == 0 and arith_name == main_arith:
+            dump_outputs(args.dump_outputs, frames)
         roofline, arith = roofline_of_leg(net, args, B, arith_name)
         # ---- self-check, outside the timed region: row 0 of this rank's shard recomputed ALONE (B = 1) under the same kernel table with the
         # same Philox key (seed, global row) must reproduce the row the full batch produced -- a mis-indexed tile at the benchmarked batch
@@ -492,7 +521,7 @@ def main():
         kw = dict(final_only=True, denoise=True, subsample_steps=subsample, clip_before=True, verbose=False, log=False,
                   seed=1000 + last_seed, sample_offset=b0)
         selfcheck = None
-        if not args.no_selfcheck:
+        if args.full and not args.no_selfcheck:
             if autoreg:    # (video_gen draws its block inits from a torch generator whose stream depends on the batch: check one block's sampler call)
                 full = ddpm_sampler(x, net, cond=cond, **kw)[0]
             else:
@@ -513,7 +542,7 @@ def main():
     main_leg = run_leg(main_arith, args.f16x2, args.warmup, args.steps, 0, args.tune_cache or table_path(main_arith))
     # ---- reported only (N = 1): the same timed region with the two-piece fp16 kernels offered as well (narrower arithmetic: an option)
     second = None
-    if world == 1 and not args.no_second_leg and not args.f16x2:
+    if args.full and world == 1 and not args.no_second_leg and not args.f16x2:
         second = run_leg("f16x2", 1, 1, args.steps, 500, table_path("f16x2"))
         net.set_option("f16x2", 0)
 
@@ -551,10 +580,10 @@ def main():
                    roofline=main_leg["roofline"],
                    selfcheck_max_abs=main_leg["selfcheck_max_abs"],
                    selfcheck_note="max |row 0 of the last timed call - the same row sampled alone (B = 1, same kernel table, same Philox key)| "
-                                  "over the final frames (data range [-1, 1]); computed after the timed region",
+                                  "over the final frames (data range [-1, 1]); computed after the timed region by --full runs (null otherwise)",
                    profile=1, profile_note="context option profile = 1: the first forward of each leg's LAST timed call runs op by op with HIP "
                                            "events around every launch (the roofline breakdown); it is inside the timed region (< 0.1 % of it)",
-                   rccl_ranks_seen=ranks_seen)
+                   rccl_ranks_seen=ranks_seen, full=args.full)
         if second:
             res["f16x2_leg"] = dict(value=round(second["value"], 3), unit="frames/s", ms_per_step=round(second["ms_per_step"], 2),
                                     dtype=second["dtype"], kernel_table=second["kernel_table"], roofline=second["roofline"],
@@ -577,7 +606,7 @@ def main():
             res["valid"] = False
             res["invalid_reason"] = (res.get("invalid_reason", "") + f" per_rank_spread {res['per_rank_spread']} > {args.rank_spread_tol}: ranks with equal "
                                      f"shards took {main_leg['per_rank_busy']} s for their own sampler calls -- a straggler GPU").strip()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(config, sd, subsample, kept_fraction=nfp / (n_blocks * nfr) if autoreg else 1.0)
                 res["cpu_baseline"]["speedup"] = round(main_leg["value"] / res["cpu_baseline"]["value"], 1)

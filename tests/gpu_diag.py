@@ -1,4 +1,4 @@
-"""GPU diagnostics -- test infrastructure (uses the oracle as checker; writes gpurun_out/diag_*.txt): precision vs the
+"""GPU diagnostics -- test infrastructure (uses the oracle as checker; writes results/diag_*.txt): precision vs the
 fp32/fp64 oracle, per-op timings, conv tile sweep.
     python tests/gpu_diag.py [precision] [ops] [sweep]
 """
@@ -16,7 +16,7 @@ torch.set_num_threads(min(os.cpu_count() or 1, 16))
 from mcvd_pytorch_amd import HipScoreNet, _lib, ddim_sampler, ddpm_sampler, synthetic  # noqa: E402
 from oracle import sampler_ref, synth, unet_ref  # noqa: E402
 
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = os.path.join(ROOT, "results")
 os.makedirs(OUT, exist_ok=True)
 
 

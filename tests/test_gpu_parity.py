@@ -10,6 +10,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import sampler_ref, synth, unet_ref
+from tests.golden_io import load_golden
 
 pytestmark = pytest.mark.gpu
 
@@ -1524,7 +1525,7 @@ def test_video_gen_config5_vs_reference_golden(golden_dir):
     (oracle/gen_golden.py:gen_autoregressive).  Two chained 100-step blocks: 2e-4."""
     from mcvd_pytorch_amd import video_gen
     from mcvd_pytorch_amd.samplers import ddpm_sampler
-    g = torch.load(os.path.join(golden_dir, "cityscapes_big_b1_ar8.pt"), weights_only=False)
+    g = load_golden(golden_dir, "cityscapes_big_b1_ar8.pt")
     config, sd, net = _net(g["config_name"])
     B, nfp, sub = g["batch"], g["nfp"], g["subsample"]
     d = config.data
@@ -2027,7 +2028,7 @@ def _bench_job(tmp_path, tag, gpus, batch, backend=None, tune_cache=None, save_t
             env["MCVD_BENCH_SERIALIZE"] = "1"
     dump = os.path.join(str(tmp_path), f"frames_{tag}.pt")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", "1", "--warmup", "1", "--subsample", "5",
-           "--batch", str(batch), "--no-cpu-baseline", "--no-f16x2-leg", "--dump-frames", dump]
+           "--batch", str(batch), "--full", "--no-cpu-baseline", "--no-f16x2-leg", "--dump-frames", dump]
     if tune_cache:
         cmd += ["--tune-cache", tune_cache]
     if save_tuning:

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from oracle import synth
+from tests.golden_io import load_golden
 from tests.test_oracle_golden import SURFACE_KEYS, add_back_step_noise, surface_case
 
 pytestmark = pytest.mark.gpu
@@ -200,7 +201,7 @@ def test_three_edits_of_integration_md_against_the_real_runner(golden_dir, capsy
     import re
     from mcvd_pytorch_amd import runner as r
     from mcvd_pytorch_amd.samplers import ddim_sampler, ddpm_sampler, fpndm_sampler, get_sampler
-    g = torch.load(os.path.join(golden_dir, fx), weights_only=False)
+    g = load_golden(golden_dir, fx)
     config, sd, net = _net(g["config_name"])                                  # edit 1
     config.sampling.num_frames_pred, config.sampling.subsample = g["nfp"], g["subsample"]
     for k_, v_ in g.get("overrides", {}).items():                             # init_prev_t (blocks restart from the previous frames, re-noised) / one_frame_at_a_time

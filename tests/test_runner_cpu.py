@@ -118,8 +118,8 @@ def _runner_tol(g):
 
 
 def _runner_fixture(golden_dir, name="tiny_runner_videogen.pt"):
-    import os
-    return torch.load(os.path.join(golden_dir, name), weights_only=False)
+    from tests.golden_io import load_golden
+    return load_golden(golden_dir, name)
 
 
 def _runner_config(g):

@@ -1,7 +1,7 @@
 """Patch ONE entry of the committed kernel tables: the stem conv (the first 3x3 conv op of the plan) of the configs whose stem became eligible for
 the GEMM form with the LDS-staged im2col in round 6 (15 / 21 input channels).  Everything else in the tables stays as committed and tested.
 For each config: autotune at the bench's per-GPU batch (timing launches), read what the tuner chose for the stem, and if it is shape id 23 write
-[23, cot] into that entry of profiles/tune_<config>_B<batch>_{bf16x3,f16x2}.json (under gpurun_out/tune_patched/ -- copy to profiles/ and commit).
+[23, cot] into that entry of profiles/tune_<config>_B<batch>_{bf16x3,f16x2}.json (under results/tune_patched/ -- copy to profiles/ and commit).
 Run on the GPU box:  python tools/gpu_patch_stem_tables.py"""
 import ctypes as C
 import json
@@ -15,7 +15,7 @@ sys.path.insert(0, ROOT)
 from bench import DEFAULTS, make_config  # noqa: E402
 from mcvd_pytorch_amd import HipScoreNet, _lib, synthetic  # noqa: E402
 
-OUT = os.path.join(ROOT, "gpurun_out", "tune_patched")
+OUT = os.path.join(ROOT, "results", "tune_patched")
 os.makedirs(OUT, exist_ok=True)
 for name in ("kth64_big_ngf128", "cityscapes_big", "cityscapes_big_variant", "smmnist_big5", "smmnist_big5_ngf96", "bair_big_spade"):
     B = DEFAULTS[name][0]

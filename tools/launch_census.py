@@ -2,7 +2,7 @@
 kind, how long they take (HIP events around every op, option "profile") and how many of them are shorter than 20 us -- the regime where a
 launch is bound by its own ramp-up and tail rather than by its work.  Run on the GPU box:
 
-    python tools/launch_census.py bair_big_spade 16 > gpurun_out/census.txt
+    python tools/launch_census.py bair_big_spade 16 > results/census.txt
 """
 import ctypes as C
 import json
