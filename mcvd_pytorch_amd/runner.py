@@ -56,6 +56,58 @@ def conditioning_fn(config, X, num_frames_pred=0, prob_mask_cond=0.0, prob_mask_
     return pred, torch.cat(blocks, dim=1) if len(blocks) > 1 else blocks[0], cond_mask
 
 
+TASKS = ("pred", "interp", "pred_future_masked", "gen")
+# (prob_mask_cond, prob_mask_future) each phase of NCSNRunner.video_gen hands conditioning_fn (:1458-1459, :1625-1626, :1798-1799)
+_TASK_MASKS = {"pred": (0.0, 0.0), "interp": (0.0, 0.0), "pred_future_masked": (0.0, 1.0), "gen": (1.0, 1.0)}
+
+
+def _task_frames(config, task):
+    """Frames a task produces (:1450-1456, :1621, :1793); ValueError for a task the config's layout cannot run."""
+    d, s = config.data, config.sampling
+    future = getattr(d, "num_frames_future", 0)
+    if task not in _TASK_MASKS:
+        raise ValueError(f"unknown task {task!r}; one of {TASKS}")
+    if task == "pred" and future > 0:
+        raise ValueError("task 'pred' needs data.num_frames_future == 0 (with future frames the reference interpolates, :1453-1456)")
+    if task in ("interp", "pred_future_masked") and future == 0:
+        raise ValueError(f"task {task!r} needs data.num_frames_future > 0")
+    if task == "interp":
+        return int(d.num_frames)
+    if task == "gen":
+        return int(d.num_frames_cond) + int(s.num_frames_pred)
+    return int(s.num_frames_pred)
+
+
+def video_tasks(config):
+    """The phases NCSNRunner.video_gen runs on a batch for this config, in its order, as [(task, num_frames_pred), ...]:
+
+      (1) "pred" (num_frames_future == 0, sampling.num_frames_pred frames) or "interp" (future > 0, data.num_frames frames);
+      (2) "pred_future_masked" when future > 0, data.prob_mask_future > 0 and not data.prob_mask_sync (sampling.num_frames_pred);
+      (3) "gen" when data.prob_mask_cond > 0 (num_frames_cond + sampling.num_frames_pred frames).
+
+    Branch table :1309-1335, phase gates :1444, :1612, :1783.  The reference runs (3) only under `sampling.fvd` and only when
+    num_frames_cond + num_frames_pred >= 10 (an FVD rule); neither gate is applied here.  With prob_mask_sync the reference sizes its
+    dataloader by the :1406 branch (the :1408 one cannot be reached), but runs the phases of :1326-1329: (1) and (3)."""
+    d, s = config.data, config.sampling
+    future = getattr(d, "num_frames_future", 0)
+    tasks = [("interp" if future > 0 else "pred")]
+    if future > 0 and getattr(d, "prob_mask_future", 0.0) > 0.0 and not getattr(d, "prob_mask_sync", False):
+        tasks.append("pred_future_masked")
+    if getattr(d, "prob_mask_cond", 0.0) > 0.0:
+        tasks.append("gen")
+    return [(t, _task_frames(config, t)) for t in tasks]
+
+
+def task_conditioning(config, X, task):
+    """Clip [B, T, C, H, W] (network range) -> (real, cond, cond_mask, num_frames_pred) for one phase of `video_tasks`: conditioning_fn
+    with that phase's masks -- "pred" / "interp" (0, 0), "pred_future_masked" (0, 1: the future block zeroed), "gen" (1, 1: cond and
+    future zeroed, cond_mask all zeros).  The "gen" call draws its cond mask from torch.rand as the reference does."""
+    nfp = _task_frames(config, task)
+    p_cond, p_future = _TASK_MASKS[task]
+    real, cond, cond_mask = conditioning_fn(config, X, num_frames_pred=nfp, prob_mask_cond=p_cond, prob_mask_future=p_future)
+    return real, cond, cond_mask, nfp
+
+
 def _mean_image(config, like):
     m = getattr(config, "image_mean", None)
     return None if m is None else m.to(like.device)[None, ...]
@@ -93,7 +145,7 @@ def inverse_data_transform(config, X):
 
 @torch.no_grad()
 def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, sampler=None, data_init=None, verbose=False,
-              log=False, **sampler_kwargs):
+              log=False, task=None, cond_mask=None, **sampler_kwargs):
     """Autoregressive block loop of NCSNRunner.video_gen (runners/ncsn_runner.py:1476-1569, prediction path: future == 0), kept on
     the device between blocks (the reference moves every block to the CPU and back, :1521-1539).  Returns [B, C*num_frames_pred, S, S].
 
@@ -114,10 +166,32 @@ def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, 
 
     `init_noise_fn(block_index, shape, device)` supplies z (default: torch.randn on the device, or the centred gamma variate for a
     `model.gamma` config).  A `seed=` kwarg (on-device Philox step noise) is advanced by one per block, so blocks never share a
-    noise stream."""
+    noise stream.
+
+    `task` (one of `video_tasks(config)`, with cond / cond_mask from `task_conditioning`) runs that phase's block loop instead;
+    `num_frames_pred` then defaults to the task's frame count.  `task=None` is the loop above, unchanged.
+      * "pred": the loop above (future == 0).
+      * "interp" (:1444-1569 with future > 0): one block; num_frames_pred > num_frames is refused (ValueError).  Under
+        one_frame_at_a_time the reference runs num_frames one-frame blocks with the prediction shift (:1502, :1530-1531), which moves
+        the future frame into the past window -- reproduced as it is.
+      * "pred_future_masked" (:1612-1720) and "gen" (:1783-1916) with future > 0: the shift keeps the trailing C*future channels (the
+        zero future block) at the end of cond (:1700-1708, :1874-1882); "gen" with future == 0 shifts as prediction (:1867-1871).
+        Under one_frame_at_a_time that shift grows cond by C*future channels per block and the reference's second sampler call fails
+        on the shape: a RuntimeError before the second block here.
+    `cond_mask` goes to the sampler as given for block 0 and as ones for every later block (:1885-1886).  It is not routed into the
+    forward: the reference samplers take it into **kwargs and drop it (models/__init__.py:207-209), so a `model.cond_emb` net samples
+    as if the mask were ones, here as there.  data_init, init_prev_t, model.gamma and the per-block seed mean the same in every task."""
     d, s = config.data, config.sampling
     C, nf, nc, S = d.channels, d.num_frames, d.num_frames_cond, d.image_size
-    nfp = int(num_frames_pred if num_frames_pred is not None else s.num_frames_pred)
+    future = getattr(d, "num_frames_future", 0)
+    if task is None:
+        nfp = int(num_frames_pred if num_frames_pred is not None else s.num_frames_pred)
+    else:
+        task_frames = _task_frames(config, task)                                      # also refuses a task the layout cannot run
+        nfp = int(num_frames_pred if num_frames_pred is not None else task_frames)
+        if task == "interp" and nfp > nf:                                             # :1456: one block of num_frames frames
+            raise ValueError(f"task 'interp' produces at most data.num_frames = {nf} frames, asked for {nfp}")
+    keep_future = task in ("pred_future_masked", "gen") and future > 0                # :1700-1708, :1874-1882
     one_at_a_time = bool(getattr(s, "one_frame_at_a_time", False))
     sampler = sampler or get_sampler(config)
     dev = scorenet.device
@@ -159,13 +233,18 @@ def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, 
         return alpha0.sqrt() * real_init1 + (1 - alpha0).sqrt() * z                   # :1495-1496, :1563-1564
 
     init = init_for(0, real_init[:, :C * nf] if real_init is not None else None)       # :1488
+    cond_width = None if cond is None else cond.shape[1]
     preds, gen = [], None
     for i in range(n_iter):
         x0 = init if (i == 0 or t_min <= 0) else gen                                    # :1513
         kw = dict(sampler_kwargs)
         if seed is not None:
             kw["seed"] = int(seed) + i
-        out = sampler(x0, scorenet, cond=cond, cond_mask=None, final_only=True, denoise=getattr(s, "denoise", True),
+        if task is not None and cond is not None and cond.shape[1] != cond_width:       # one_frame_at_a_time + kept future block
+            raise RuntimeError(f"task {task!r}, block {i}: the cond shift left {cond.shape[1]} cond channels, the network takes "
+                               f"{cond_width} (the reference's sampler call fails here too, :1700-1703, :1874-1877)")
+        mask = cond_mask if (i == 0 or cond_mask is None) else torch.ones_like(cond_mask)   # :1885-1886
+        out = sampler(x0, scorenet, cond=cond, cond_mask=mask, final_only=True, denoise=getattr(s, "denoise", True),
                       subsample_steps=getattr(s, "subsample", None), clip_before=getattr(s, "clip_before", True),
                       t_min=t_min, gamma=gamma, verbose=verbose, log=log, **kw)
         gen = out[-1].reshape(B, C * nf, S, S)                                          # :1521-1522
@@ -174,6 +253,10 @@ def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, 
             continue
         if cond is None:                                                                # :1528-1529
             cond = gen
+        elif keep_future:                                                               # :1700-1708, :1874-1882
+            head = cond[:, C:] if one_at_a_time else cond[:, C * nf:cond.shape[1] - C * future]
+            new = gen[:, :C] if one_at_a_time else gen[:, C * max(0, nf - nc):]
+            cond = torch.cat([head, new, cond[:, cond.shape[1] - C * future:]], dim=1).contiguous()
         elif one_at_a_time:                                                             # :1530-1531
             cond = torch.cat([cond[:, C:], gen[:, :C]], dim=1).contiguous()
         else:                                                                           # :1532-1535
