@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "model.h"
+#include "conv_kernels.h"
 
 using namespace mcvd;
 
@@ -295,7 +296,7 @@ int mcvd_ctx_selftest(mcvd_ctx* ctx) {
             c->stats_buf = stats_buf; c->spade_gb = spade_gb; c->spade_coef2 = spade_coef2; c->dbg = dbg;
         }
     };
-    const int shapes[3] = {4, 10, 16};
+    const int shapes[3] = {CK_WINO, CK_WINO3, CK_WINO3P};
     int rc = 0, ran[3] = {-1, -1, -1};
     std::vector<float> out(3 * ny);
     {
@@ -316,7 +317,7 @@ int mcvd_ctx_selftest(mcvd_ctx* ctx) {
         d10 = std::max(d10, std::fabs(out[ny + i] - out[i]));
         diff16 += memcmp(&out[2 * ny + i], &out[ny + i], sizeof(float)) != 0;
     }
-    const bool ok = ran[0] == 4 && ran[1] == 10 && ran[2] == 16 && scale > 0.1f && d10 <= 1e-4f * scale && diff16 == 0 && std::isfinite(d10);
+    const bool ok = ran[0] == shapes[0] && ran[1] == shapes[1] && ran[2] == shapes[2] && scale > 0.1f && d10 <= 1e-4f * scale && diff16 == 0 && std::isfinite(d10);
     if (ok) { ctx->wino_selftest = 1; return 0; }
     ctx->wino_selftest = -1;
     ctx->bf16x3 = 0;
@@ -1122,18 +1123,16 @@ int mcvd_op_conv2d(mcvd_ctx* ctx, const float* x0, int C0, const float* x1, int 
     a.CinP = round_up(a.Cin, conv_chunk(ks));
     a.CoutP = round_up(Cout, 32 * a.cot);
     const size_t wfloats = (size_t)a.CinP * ks * ks * a.CoutP;
-    const bool wino = (ctx->conv_shape == 4 || ctx->conv_shape == 8 || (ctx->conv_shape >= 10 && ctx->conv_shape <= 13) ||
-                       (ctx->conv_shape >= 16 && ctx->conv_shape <= 20)) && conv_wino_supported(ks, H, W);
-    const bool wino_h = wino && (ctx->conv_shape == 12 || ctx->conv_shape == 13);     // fp16 pieces as well
-    const bool wino_b = wino && (ctx->conv_shape == 10 || ctx->conv_shape == 11 || (ctx->conv_shape >= 16 && ctx->conv_shape <= 20));     // bf16 pieces as well
-    const int np1 = (ks == 1 && ctx->conv_shape == 14) ? 2 : (ks == 1 && ctx->conv_shape == 15) ? 3 : 0;      // 1x1 pieces
+    const ConvKernelDesc& k = conv_kernel(ctx->conv_shape);      // the forced kernel decides which weight images are packed
+    const bool wino = is_winograd(k.id) && conv_wino_supported(ks, H, W);
+    const bool wino_h = wino && k.weights == CW_WPH;     // fp16 pieces as well
+    const bool wino_b = wino && k.weights == CW_WPB;     // bf16 pieces as well
+    const int np1 = (ks == 1 && k.family == CF_SPLIT1) ? k.pieces : 0;      // 1x1 pieces
     const size_t ufloats = wino ? (size_t)a.CinP * 16 * a.CoutP : 0;
     const size_t hfloats = wino_h ? (size_t)((conv_wino2h_weight_floats(a.CinP, a.CoutP) + 3) / 4 * 4)
                            : wino_b ? (size_t)((conv_wino3_weight_floats(a.CinP, a.CoutP) + 3) / 4 * 4)
                            : np1 ? (size_t)((conv1x1_h2_weight_floats(a.CinP, a.CoutP, np1) + 3) / 4 * 4) : 0;
-    const int kparts = (ctx->conv_shape == 8 || ctx->conv_shape == 11 || ctx->conv_shape == 13 || ctx->conv_shape == 17) ? 2
-                       : (ctx->conv_shape == 18 || ctx->conv_shape == 20) ? 4 : ctx->conv_shape == 19 ? 8 : 0;
-    const size_t pfloats = wino ? (size_t)kparts * B * Cout * H * W : 0;     // K-split partial results
+    const size_t pfloats = wino ? (size_t)k.kparts * B * Cout * H * W : 0;     // K-split partial results
     if (int rc = ctx->ensure_scratch((wfloats + a.CoutP + ufloats + hfloats + pfloats) * sizeof(float))) return rc;
     MCVD_HIP_CHECK(hipMemsetAsync(ctx->scratch, 0, (wfloats + a.CoutP + ufloats + hfloats) * sizeof(float), ctx->stream));
     if (wino) {
@@ -1158,7 +1157,7 @@ int mcvd_op_conv2d(mcvd_ctx* ctx, const float* x0, int C0, const float* x1, int 
     a.wp = ctx->scratch;
     a.bias = ctx->scratch + wfloats;
     a.shape_hint = ctx->conv_shape;
-    if ((ctx->conv_shape == 5 || ctx->conv_shape == 6 || ctx->conv_shape == 9 || ctx->conv_shape == 14 || ctx->conv_shape == 15) && ctx->conv_cot > 0) a.cot = ctx->conv_cot;
+    if (k.own_cot && ctx->conv_cot > 0) a.cot = ctx->conv_cot;
     a.wdma = ctx->conv_wdma;
     a.pgrid = ctx->persist_grid;
     a.dbg = ctx->dbg;
@@ -1169,7 +1168,7 @@ int mcvd_op_conv2d(mcvd_ctx* ctx, const float* x0, int C0, const float* x1, int 
         a.gb = ctx->spade_gb;
         a.coef2 = ctx->spade_coef2;
         ConvArgs t = a;
-        t.ksplit = ctx->conv_shape == 8 ? 2 : 0;
+        t.ksplit = k.family == CF_WINO ? k.kparts : 0;
         MCVD_REQUIRE(conv_wino_usable(t) || (t.ksplit = 0, conv_wino_usable(t)), "op_conv2d: shape not served by the Winograd kernel");
     }
     return ctx->naive_conv ? launch_conv_naive(a, ctx->stream) : launch_conv_mfma(a, ctx->stream);

@@ -97,11 +97,7 @@ struct ConvArgs {
     int B, Cin, CinP, Cout, CoutP, H, W;
     int ks;               // 1 or 3
     int cot;              // cout tile in units of 32 channels (1..4); CoutP % (32*cot) == 0
-    int shape_hint;       // -1 auto; 0/1/2 force the 256/128/64-pixel tile, 3 split-K+WDB, 4 Winograd (8: with a 2-way K split), 5 / 6 all-DMA 1x1 GEMM (16 / 32 channels per chunk),
-                          // 9 the 1x1 GEMM with 64 pixels per wave, 10 Winograd on the bf16 pipe with three-piece operands (11: with a 2-way K split),
-                          // 12 Winograd on the fp16 pipe with two-piece operands (13: with a 2-way K split), 14 the 1x1 GEMM on the fp16 pipe
-                          // with two-piece operands, 15 the 1x1 GEMM on the bf16 pipe with three-piece operands, 16 / 17 the three-piece bf16 Winograd
-                          // kernel as persistent workgroups (17: with a 2-way K split)
+    int shape_hint;       // the kernel wanted (conv_kernels.h: ConvKernel), -1 auto; a kernel that does not apply falls back as its descriptor says
     int ksplit;           // Winograd kernel only: 2 = two workgroups per tile contract half the input channels each into
                           // `part`, a second pass sums the halves; 0/1 = off
     float* part;          // ksplit >= 2: scratch for the partial results, ksplit * B*Cout*H*W floats
@@ -146,7 +142,9 @@ int conv_cout_tile(int Cout);                 // 32-channel units per block alon
 int conv_chunk(int ks);                       // input-channel chunk the MFMA kernel consumes per stage
 int launch_conv_mfma(const ConvArgs& a, hipStream_t s);
 int launch_conv_naive(const ConvArgs& a, hipStream_t s);
-int last_conv_kernel();                       // kernel family of this thread's last launch_conv_mfma (see conv.cpp)
+int last_conv_kernel();                       // the kernel (conv_kernels.h: ConvKernel) this thread's last launch_conv_mfma ran
+bool conv_kernel_usable(int id, const ConvArgs& a);        // kernel `id` takes this launch as it stands (its K parts applied; a.cot where the kernel has tiles of its own)
+int conv_kernel_launch(int id, const ConvArgs& a, hipStream_t s);
 // 3x3 convs with a handful of channels on one side as 1x1 GEMMs (conv_gemm_forms.cpp): shape ids 22 (taps as outputs + shift-and-add) / 23 (im2col)
 int launch_im2col3x3(const float* x0, int C0, const float* x1, int C1, float* col, int B, int H, int W, int K, hipStream_t s);
 int launch_taps_shift_add(const float* z, const float* bias, const float* res, float scale, float* y, int B, int Cout, int H, int W, hipStream_t s);

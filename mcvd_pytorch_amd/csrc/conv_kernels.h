@@ -1,0 +1,151 @@
+// The convolution kernel variants, once: what each "shape id" is, what it needs, what it turns into when an arithmetic option is off and
+// what a launch tries after it.  The ids are public (the context options conv_shape / conv_shape1, the committed tuning tables under
+// profiles/, mcvd_last_conv_kernel / mcvd_model_op_kernel): a new variant gets a new number and one line here; numbers are never reused.
+// Plain C++17, no HIP: the static_asserts at the end check the table in every build.
+#pragma once
+#include <initializer_list>
+
+namespace mcvd {
+
+enum ConvKernel : int {
+    CK_AUTO = -1,                 // the dispatcher's own choice (kernels/conv.cpp)
+    CK_TILE256 = 0, CK_TILE128 = 1, CK_TILE64 = 2, CK_TILE_SPLITK = 3,
+    CK_WINO = 4, CK_DMA1 = 5, CK_DMA1_CK32 = 6, /* 7 unused */ CK_WINO_K2 = 8, CK_DMA1_PX64 = 9,
+    CK_WINO3 = 10, CK_WINO3_K2 = 11, CK_WINO2H = 12, CK_WINO2H_K2 = 13, CK_GEMM1_F16X2 = 14, CK_GEMM1_BF16X3 = 15,
+    CK_WINO3P = 16, CK_WINO3P_K2 = 17, CK_WINO3_K4 = 18, CK_WINO3_K8 = 19, CK_WINO3P_K4 = 20, /* 21 unused */
+    CK_GEMM3_TAPS = 22, CK_GEMM3_IM2COL = 23,
+    CK_RETIRED_SPADE_WINO = 36, CK_RETIRED_SPADE_WINO_K2 = 40      // round-5 tables: the per-layer fused SPADE loader, gone; read as CK_AUTO
+};
+
+// Ordered: within the Winograd families a larger value is the more specialised kernel (fallback lists only ever go down).
+enum ConvFamily : int {
+    CF_NONE,        // not a kernel (CK_AUTO, unused and unknown ids)
+    CF_TILE,        // direct implicit GEMM on the fp32 MFMA; the id is the pixel tile (conv_mfma.h)
+    CF_DMA1,        // all-DMA 1x1 GEMM, fp32 MFMA (conv1x1_dma.cpp)
+    CF_SPLIT1,      // split-operand 1x1 GEMM on the fp16 / bf16 pipe (conv1x1_h2.cpp)
+    CF_GEMM3,       // a 3x3 as a CF_SPLIT1 GEMM plus a copy / shift pass (conv_gemm_forms.cpp); launched by the model, not by the dispatcher
+    CF_WINO,        // Winograd F(2x2,3x3), fp32 MFMA (conv_wino.cpp)
+    CF_WINO2H,      // ... on the fp16 pipe, two-piece operands (conv_wino2h.cpp)
+    CF_WINO3,       // ... on the bf16 pipe, three-piece operands (conv_wino3.cpp)
+    CF_WINO3P       // ... the same as persistent workgroups (conv_wino3p.cpp)
+};
+
+enum ConvWeights : int { CW_WP, CW_WPW, CW_WPH, CW_WPB };      // the ConvArgs weight image the kernel reads
+
+struct ConvKernelDesc {
+    int id;
+    const char* name;
+    ConvFamily family;
+    int ks;                // kernel size served (0: 1 and 3)
+    int pieces;            // operand pieces: 0 fp32, 2 fp16, 3 bf16
+    int kparts;            // K split: 0 none, else ConvArgs::ksplit
+    bool own_cot;          // takes a cout tile of its own (ConvArgs::cot is not the direct kernel's)
+    ConvWeights weights;
+    int no_f16x2;          // the id it becomes when the option f16x2 is off or the input is raw
+    int no_bf16x3;         // the id it becomes when the option bf16x3 is off
+    int fallback[7];       // what a launch with this hint tries, in order, each only if usable; -1 ends the list, then the direct-tile heuristic
+};
+
+inline constexpr ConvKernelDesc kConvKernels[] = {
+    //  id               name              family     ks pc kp own_cot weights  no_f16x2         no_bf16x3        fallback
+    {CK_TILE256,      "tile256",        CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE256,      CK_TILE256,      {-1}},
+    {CK_TILE128,      "tile128",        CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE128,      CK_TILE128,      {-1}},
+    {CK_TILE64,       "tile64",         CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE64,       CK_TILE64,       {-1}},
+    {CK_TILE_SPLITK,  "tile64_splitk",  CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE_SPLITK,  CK_TILE_SPLITK,  {-1}},
+    {CK_WINO,         "wino",           CF_WINO,    3, 0, 0, false, CW_WPW, CK_WINO,         CK_WINO,         {CK_WINO, -1}},
+    {CK_DMA1,         "dma1",           CF_DMA1,    1, 0, 0, true,  CW_WP,  CK_DMA1,         CK_DMA1,         {CK_DMA1, -1}},
+    {CK_DMA1_CK32,    "dma1_ck32",      CF_DMA1,    1, 0, 0, true,  CW_WP,  CK_DMA1_CK32,    CK_DMA1_CK32,    {CK_DMA1_CK32, -1}},
+    {CK_WINO_K2,      "wino_k2",        CF_WINO,    3, 0, 2, false, CW_WPW, CK_WINO_K2,      CK_WINO_K2,      {CK_WINO_K2, CK_WINO, -1}},
+    {CK_DMA1_PX64,    "dma1_px64",      CF_DMA1,    1, 0, 0, true,  CW_WP,  CK_DMA1_PX64,    CK_DMA1_PX64,    {CK_DMA1_PX64, -1}},
+    {CK_WINO3,        "wino3",          CF_WINO3,   3, 3, 0, false, CW_WPB, CK_WINO3,        CK_WINO,         {CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3_K2,     "wino3_k2",       CF_WINO3,   3, 3, 2, false, CW_WPB, CK_WINO3_K2,     CK_WINO_K2,      {CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO2H,       "wino2h",         CF_WINO2H,  3, 2, 0, false, CW_WPH, CK_WINO3,        CK_WINO2H,       {CK_WINO2H, CK_WINO, -1}},
+    {CK_WINO2H_K2,    "wino2h_k2",      CF_WINO2H,  3, 2, 2, false, CW_WPH, CK_WINO3_K2,     CK_WINO2H_K2,    {CK_WINO2H_K2, CK_WINO2H, CK_WINO, -1}},
+    {CK_GEMM1_F16X2,  "gemm1_f16x2",    CF_SPLIT1,  1, 2, 0, true,  CW_WPH, CK_GEMM1_BF16X3, CK_GEMM1_F16X2,  {CK_GEMM1_F16X2, -1}},
+    {CK_GEMM1_BF16X3, "gemm1_bf16x3",   CF_SPLIT1,  1, 3, 0, true,  CW_WPB, CK_GEMM1_BF16X3, CK_DMA1,         {CK_GEMM1_BF16X3, -1}},
+    {CK_WINO3P,       "wino3p",         CF_WINO3P,  3, 3, 0, false, CW_WPB, CK_WINO3P,       CK_WINO,         {CK_WINO3P, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3P_K2,    "wino3p_k2",      CF_WINO3P,  3, 3, 2, false, CW_WPB, CK_WINO3P_K2,    CK_WINO_K2,      {CK_WINO3P_K2, CK_WINO3P, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3_K4,     "wino3_k4",       CF_WINO3,   3, 3, 4, false, CW_WPB, CK_WINO3_K4,     CK_WINO_K2,      {CK_WINO3_K4, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3_K8,     "wino3_k8",       CF_WINO3,   3, 3, 8, false, CW_WPB, CK_WINO3_K8,     CK_WINO_K2,      {CK_WINO3_K8, CK_WINO3_K4, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3P_K4,    "wino3p_k4",      CF_WINO3P,  3, 3, 4, false, CW_WPB, CK_WINO3P_K4,    CK_WINO_K2,      {CK_WINO3P_K4, CK_WINO3P_K2, CK_WINO3P, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_GEMM3_TAPS,   "gemm3_taps",     CF_GEMM3,   3, 3, 0, true,  CW_WPB, CK_GEMM3_TAPS,   CK_GEMM3_TAPS,   {-1}},     // (bf16x3 off: the model falls
+    {CK_GEMM3_IM2COL, "gemm3_im2col",   CF_GEMM3,   3, 3, 0, true,  CW_WPB, CK_GEMM3_IM2COL, CK_GEMM3_IM2COL, {-1}},     //  back to CK_AUTO itself)
+};
+inline constexpr ConvKernelDesc kNoConvKernel = {CK_AUTO, "auto", CF_NONE, 0, 0, 0, false, CW_WP, CK_AUTO, CK_AUTO, {-1}};
+
+// the descriptor of an id; kNoConvKernel for CK_AUTO and for anything that is not a kernel (an option or an imported table can hold any integer)
+constexpr const ConvKernelDesc& conv_kernel(int id) {
+    for (const ConvKernelDesc& k : kConvKernels)
+        if (k.id == id) return k;
+    return kNoConvKernel;
+}
+constexpr bool is_winograd(int id) { return conv_kernel(id).family >= CF_WINO; }
+constexpr int k_parts(int id) { return conv_kernel(id).kparts; }
+constexpr int pieces(int id) { return conv_kernel(id).pieces; }
+constexpr int without_f16x2(int id) { return conv_kernel(id).id == id ? conv_kernel(id).no_f16x2 : id; }
+constexpr int without_bf16x3(int id) { return conv_kernel(id).id == id ? conv_kernel(id).no_bf16x3 : id; }
+
+// ---- the table, checked ----
+namespace conv_kernels_check {
+constexpr int N = sizeof(kConvKernels) / sizeof(kConvKernels[0]);
+constexpr bool known(int id) { return conv_kernel(id).id == id && id != CK_AUTO; }
+constexpr int rank(const ConvKernelDesc& k) { return k.family * 16 + k.kparts; }       // "simpler" = lower
+constexpr bool fallback_is(int id, std::initializer_list<int> want) {
+    const int* f = conv_kernel(id).fallback;
+    for (int w : want)
+        if (*f++ != w) return false;
+    return *f == -1;
+}
+constexpr bool ids_unique() {
+    for (int i = 0; i < N; ++i)
+        for (int j = 0; j < i; ++j)
+            if (kConvKernels[i].id == kConvKernels[j].id) return false;
+    return true;
+}
+// a list is empty or starts with its own id, names kernels of the same size only, gets strictly simpler and, for a Winograd id, ends in CK_WINO
+constexpr bool fallbacks_sound() {
+    for (const ConvKernelDesc& k : kConvKernels) {
+        const ConvKernelDesc* prev = nullptr;
+        for (const int* f = k.fallback; *f != -1; ++f) {
+            const ConvKernelDesc& e = conv_kernel(*f);
+            if (!known(*f) || e.ks != k.ks || (prev ? rank(e) >= rank(*prev) : e.id != k.id)) return false;
+            prev = &e;
+        }
+        if (k.family >= CF_WINO ? (!prev || prev->id != CK_WINO) : (prev && prev->id != k.id)) return false;
+        if ((k.family == CF_TILE || k.family == CF_GEMM3) && prev) return false;
+    }
+    return true;
+}
+// a remap stays within the kernel size, drops exactly the pieces the option names and keeps a K split where the target family has one
+constexpr bool remaps_sound() {
+    for (const ConvKernelDesc& k : kConvKernels) {
+        const ConvKernelDesc &f = conv_kernel(k.no_f16x2), &b = conv_kernel(k.no_bf16x3);
+        if (!known(k.no_f16x2) || !known(k.no_bf16x3) || f.ks != k.ks || b.ks != k.ks) return false;
+        if (k.pieces == 2 ? (f.pieces != 3 || f.kparts != k.kparts) : f.id != k.id) return false;
+        if (k.pieces == 3 && k.family != CF_GEMM3 ? (b.pieces != 0 || (b.kparts != 0) != (k.kparts != 0)) : b.id != k.id) return false;
+    }
+    return true;
+}
+static_assert(ids_unique(), "conv kernel ids must be unique");
+static_assert(!known(7) && !known(21) && !known(CK_AUTO) && !known(CK_RETIRED_SPADE_WINO) && !known(CK_RETIRED_SPADE_WINO_K2), "7 and 21 stay unused; retired ids are not kernels");
+static_assert(fallbacks_sound(), "a fallback list names an unknown id, another kernel size, or does not get simpler");
+static_assert(remaps_sound(), "an option remap names an unknown id, changes the kernel size or loses the K split");
+static_assert(fallback_is(CK_WINO3P_K4, {20, 17, 16, 11, 10, 4}), "fallback list of 20");
+static_assert(fallback_is(CK_WINO3_K8, {19, 18, 11, 10, 4}), "fallback list of 19");
+static_assert(fallback_is(CK_WINO3_K4, {18, 11, 10, 4}), "fallback list of 18");
+static_assert(fallback_is(CK_WINO3P_K2, {17, 16, 11, 10, 4}), "fallback list of 17");
+static_assert(fallback_is(CK_WINO3P, {16, 10, 4}), "fallback list of 16");
+static_assert(fallback_is(CK_WINO2H_K2, {13, 12, 4}), "fallback list of 13");
+static_assert(fallback_is(CK_WINO2H, {12, 4}), "fallback list of 12");
+static_assert(fallback_is(CK_WINO3_K2, {11, 10, 4}), "fallback list of 11");
+static_assert(fallback_is(CK_WINO3, {10, 4}), "fallback list of 10");
+static_assert(fallback_is(CK_WINO_K2, {8, 4}), "fallback list of 8");
+static_assert(fallback_is(CK_WINO, {4}), "fallback list of 4");
+static_assert(fallback_is(15, {15}) && fallback_is(14, {14}) && fallback_is(5, {5}) && fallback_is(6, {6}) && fallback_is(9, {9}), "the 1x1 GEMMs try themselves only");
+static_assert(fallback_is(0, {}) && fallback_is(3, {}) && fallback_is(22, {}) && fallback_is(23, {}) && fallback_is(7, {}) && fallback_is(CK_AUTO, {}), "everything else: the tile heuristic");
+static_assert(without_f16x2(12) == 10 && without_f16x2(13) == 11 && without_f16x2(14) == 15 && without_f16x2(15) == 15 && without_f16x2(99) == 99, "f16x2 off");
+static_assert(without_bf16x3(10) == 4 && without_bf16x3(16) == 4 && without_bf16x3(15) == 5 && without_bf16x3(11) == 8 && without_bf16x3(17) == 8 &&
+              without_bf16x3(18) == 8 && without_bf16x3(19) == 8 && without_bf16x3(20) == 8 && without_bf16x3(22) == 22 && without_bf16x3(99) == 99, "bf16x3 off");
+}  // namespace conv_kernels_check
+
+}  // namespace mcvd

@@ -3,6 +3,7 @@
 #include <stdlib.h>
 
 #include "conv_mfma.h"
+#include "../conv_kernels.h"
 
 namespace mcvd {
 
@@ -22,11 +23,7 @@ static int env_int(const char* name, int dflt) {      // diagnostics build only:
 }
 #endif
 
-// which kernel family the last launch_conv_mfma of this thread dispatched to (tests assert a forced shape did not fall back
-// silently): 0..3 direct implicit GEMM tile shapes, 4 Winograd, 8 Winograd + K split, 5 / 6 all-DMA 1x1 GEMM (16 / 32 channels),
-// 9 the 1x1 GEMM with 64 pixels per wave, 10 / 11 Winograd on the bf16 pipe with three-piece operands (11: + K split), 12 / 13 Winograd on
-// the fp16 pipe with two-piece operands (13: + K split), 14 the 1x1 GEMM on the fp16 pipe with two-piece operands, 15 the 1x1 GEMM on
-// the bf16 pipe with three-piece operands, 16 / 17 the three-piece bf16 Winograd kernel as persistent workgroups (17: + K split)
+// the kernel (conv_kernels.h: ConvKernel) the last launch_conv_mfma of this thread dispatched to: tests assert a forced id did not fall back silently
 static thread_local int g_last_conv_kernel = -1;
 int last_conv_kernel() { return g_last_conv_kernel; }
 
@@ -39,6 +36,45 @@ void set_last_conv_stats_np(int np) { g_last_stats_np = np; }
 static thread_local int g_last_gn_fused = 0;
 int last_conv_gn_fused() { return g_last_gn_fused; }
 void set_last_conv_gn_fused(int v) { g_last_gn_fused = v; }
+
+// the launch as the kernel sees it: its K parts in ksplit (the fp32 Winograd kernel without a split -- the last resort of every list -- takes
+// the caller's arguments as they come)
+static ConvArgs with_k_parts(const ConvKernelDesc& k, const ConvArgs& a) {
+    ConvArgs b = a;
+    if (k.id != CK_WINO) b.ksplit = k.kparts;
+    return b;
+}
+static int dma1_chunk(int id) { return id == CK_DMA1_CK32 ? 32 : 16; }      // channels per chunk
+static int dma1_pxw(int id) { return id == CK_DMA1_PX64 ? 2 : 1; }          // 2: 64 pixels per wave
+
+// One usable / launch pair for every kernel the dispatcher serves, keyed by id.  The direct tiles (launch_conv_mfma's heuristic) and the GEMM
+// forms of a 3x3 (model.cpp) are not launched from here: not usable.
+bool conv_kernel_usable(int id, const ConvArgs& a) {
+    const ConvKernelDesc& k = conv_kernel(id);
+    switch (k.family) {
+        case CF_WINO: return conv_wino_usable(with_k_parts(k, a));
+        case CF_WINO2H: return conv_wino2h_usable(with_k_parts(k, a));
+        case CF_WINO3: return conv_wino3_usable(with_k_parts(k, a));
+        case CF_WINO3P: return conv_wino3p_usable(with_k_parts(k, a));
+        case CF_SPLIT1: return conv1x1_h2_supported(a, a.cot, k.pieces);
+        case CF_DMA1: return conv1x1_dma_supported(a, dma1_chunk(id), dma1_pxw(id)) && !(id == CK_DMA1_CK32 && a.cot == 9);
+        default: return false;
+    }
+}
+
+int conv_kernel_launch(int id, const ConvArgs& a, hipStream_t s) {
+    const ConvKernelDesc& k = conv_kernel(id);
+    switch (k.family) {
+        case CF_WINO: return launch_conv_wino(with_k_parts(k, a), s);
+        case CF_WINO2H: return launch_conv_wino2h(with_k_parts(k, a), s);
+        case CF_WINO3: return launch_conv_wino3(with_k_parts(k, a), s);
+        case CF_WINO3P: return launch_conv_wino3p(with_k_parts(k, a), s);
+        case CF_SPLIT1: return launch_conv1x1_h2(a, a.cot, s, k.pieces);
+        case CF_DMA1: return launch_conv1x1_dma(a, a.cot, dma1_chunk(id), s, dma1_pxw(id));
+        default: break;
+    }
+    MCVD_REQUIRE(false, "conv: kernel id %d is not launched by the dispatcher", id);
+}
 
 int launch_conv_mfma(const ConvArgs& a, hipStream_t s) {
     g_last_stats_np = 0;
@@ -57,77 +93,16 @@ int launch_conv_mfma(const ConvArgs& a, hipStream_t s) {
     auto blocks = [&](int bpx) { return ((px + bpx - 1) / bpx) * ntc; };
     auto fits = [&](int bpx) { return bpx % a.W == 0 && (bpx / a.W <= a.H ? a.H % (bpx / a.W) == 0 : (bpx / a.W) % a.H == 0); };
     int shape;
-    // hints 4 / 5 select the specialised kernels where they apply and fall back to the tile heuristic elsewhere
-    if (a.shape_hint == 13) {                                       // f16x2 Winograd with a 2-way K split
-        ConvArgs b = a;
-        b.ksplit = 2;
-        if (conv_wino2h_usable(b)) { g_last_conv_kernel = 13; return launch_conv_wino2h(b, s); }
-    }
-    if (a.shape_hint == 12 || a.shape_hint == 13) {                 // Winograd on the fp16 matrix pipe, two-piece operands
-        ConvArgs b = a;
-        b.ksplit = 0;
-        if (conv_wino2h_usable(b)) { g_last_conv_kernel = 12; return launch_conv_wino2h(b, s); }
-    }
-    // bf16x3 Winograd ids: 10 plain, 11 / 18 / 19 = K split in 2 / 4 / 8 parts (small-batch 8x8 / 16x16 layers: more workgroups than
-    // (region, cout tile) pairs), 16 / 17 / 20 = persistent workgroups with 1 / 2 / 4 K parts.  A deeper split that a layer cannot take
-    // (too few channel chunks) degrades to the next shallower one.
-    int h = a.shape_hint;
-    if (h == 20) {
-        ConvArgs b = a;
-        b.ksplit = 4;
-        if (conv_wino3p_usable(b)) { g_last_conv_kernel = 20; return launch_conv_wino3p(b, s); }
-        h = 17;
-    }
-    if (h == 19) {
-        ConvArgs b = a;
-        b.ksplit = 8;
-        if (conv_wino3_usable(b)) { g_last_conv_kernel = 19; return launch_conv_wino3(b, s); }
-        h = 18;
-    }
-    if (h == 18) {
-        ConvArgs b = a;
-        b.ksplit = 4;
-        if (conv_wino3_usable(b)) { g_last_conv_kernel = 18; return launch_conv_wino3(b, s); }
-        h = 11;
-    }
-    if (h == 17) {                                                  // persistent bf16x3 Winograd, the two K halves are items
-        ConvArgs b = a;
-        b.ksplit = 2;
-        if (conv_wino3p_usable(b)) { g_last_conv_kernel = 17; return launch_conv_wino3p(b, s); }
-    }
-    if (h == 16 || h == 17) {                                       // persistent bf16x3 Winograd (one workgroup per CU walks an item range)
-        ConvArgs b = a;
-        b.ksplit = 0;
-        if (conv_wino3p_usable(b)) { g_last_conv_kernel = 16; return launch_conv_wino3p(b, s); }
-    }
-    if (h == 11 || h == 17) {                                       // bf16x3 Winograd with a 2-way K split
-        ConvArgs b = a;
-        b.ksplit = 2;
-        if (conv_wino3_usable(b)) { g_last_conv_kernel = 11; return launch_conv_wino3(b, s); }
-    }
-    if (h == 10 || h == 11 || h == 16 || h == 17) {                 // Winograd on the bf16 matrix pipe, operands split three ways
-        ConvArgs b = a;
-        b.ksplit = 0;
-        if (conv_wino3_usable(b)) { g_last_conv_kernel = 10; return launch_conv_wino3(b, s); }
-    }
-    if (a.shape_hint == 8) {                                        // Winograd with a 2-way K split (fills the CUs on 8x8 layers)
-        ConvArgs b = a;
-        b.ksplit = 2;
-        if (conv_wino_usable(b)) { g_last_conv_kernel = 8; return launch_conv_wino(b, s); }
-    }
-    if ((a.shape_hint == 4 || a.shape_hint == 8 || (a.shape_hint >= 10 && a.shape_hint <= 13) || (a.shape_hint >= 16 && a.shape_hint <= 20)) && conv_wino_usable(a)) { g_last_conv_kernel = 4; return launch_conv_wino(a, s); }   // Winograd F(2x2,3x3)
-    if (a.shape_hint == 15 && conv1x1_h2_supported(a, a.cot, 3)) { g_last_conv_kernel = 15; return launch_conv1x1_h2(a, a.cot, s, 3); }   // 1x1 GEMM, bf16 pipe, three exact pieces
-    if (a.shape_hint == 14 && conv1x1_h2_supported(a, a.cot, 2)) { g_last_conv_kernel = 14; return launch_conv1x1_h2(a, a.cot, s, 2); }   // 1x1 GEMM, fp16 pipe, two-piece operands
-    if (a.shape_hint == 5 && conv1x1_dma_supported(a, 16)) { g_last_conv_kernel = 5; return launch_conv1x1_dma(a, a.cot, 16, s); }   // all-DMA 1x1 GEMM
-    if (a.shape_hint == 6 && conv1x1_dma_supported(a, 32) && a.cot != 9) { g_last_conv_kernel = 6; return launch_conv1x1_dma(a, a.cot, 32, s); }
-    if (a.shape_hint == 9 && conv1x1_dma_supported(a, 16, 2)) { g_last_conv_kernel = 9; return launch_conv1x1_dma(a, a.cot, 16, s, 2); }   // 64 pixels per wave
+    // the hint's own kernel where it applies, else the next of its fallback list (conv_kernels.h), else the tile heuristic
+    for (const int* f = conv_kernel(a.shape_hint).fallback; *f >= 0; ++f)
+        if (conv_kernel_usable(*f, a)) { g_last_conv_kernel = *f; return conv_kernel_launch(*f, a, s); }
     if (a.cot < 1 || a.cot > 4 || a.CoutP % (32 * a.cot) != 0) {   // a cout tile meant for another kernel: use this one's
         ConvArgs b = a;
         b.cot = conv_cout_tile(a.Cout);
         if (a.CoutP % (32 * b.cot) != 0) b.cot = 1;
         return launch_conv_mfma(b, s);
     }
-    const int want = (a.shape_hint >= 0 && a.shape_hint <= 3) ? a.shape_hint : forced;
+    const int want = conv_kernel(a.shape_hint).family == CF_TILE ? a.shape_hint : forced;
     if (want >= 0 && want <= 3 && fits(want == 0 ? 256 : want == 1 ? 128 : 64)) shape = want;
     else if (fits(256) && blocks(256) >= min_blocks) shape = 0;
     else if (fits(128) && blocks(128) >= min_blocks) shape = 1;

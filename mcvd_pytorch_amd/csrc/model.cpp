@@ -1,6 +1,7 @@
 // Static op plan for the `unetmore` UNet (reference: models/better/ncsnpp_more.py:70-249 construction order,
 // :251-392 forward order), parameter blob, weight packing and the forward executor.
 #include "model.h"
+#include "conv_kernels.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -184,17 +185,17 @@ struct Builder {
         // the GEMM forms of a 3x3 conv with a handful of channels on one side (conv_gemm_forms.cpp), offered to the autotuner
         if (ks == 3 && wnames.size() == 1 && !nin && op.W % 4 == 0 && (op.H * op.W) % 32 == 0 && op.H == op.W) {
             if (9 * Cout <= 64) {                        // taps as outputs: Cin -> 9 * Cout, then shift-and-add
-                p.alt_kind = 22;
+                p.alt_kind = CK_GEMM3_TAPS;
                 p.alt_CinP = round_up(Cin, 16);
                 p.alt_CoutP = round_up(9 * Cout, 32);
             } else if (9 * Cin <= 256) {                 // im2col: 9 * Cin -> Cout.  Up to 10 input channels (96 rows) either staged in LDS by the GEMM
                                                          // (conv1x1_h2.cpp IM) or materialised in HBM (im2col3x3_kernel; needs the `col` buffer); up to 28
                                                          // channels (kth / bair: 15, cityscapes: 21) in the LDS form only
-                p.alt_kind = 23;
+                p.alt_kind = CK_GEMM3_IM2COL;
                 p.alt_CinP = round_up(9 * Cin, 16);
                 p.alt_CoutP = p.CoutP;
             }
-            if (p.alt_kind && (p.alt_kind == 22 ? Cin % 16 != 0 : false)) p.alt_kind = 0;      // (the GEMM stages whole 16-channel chunks of real data)
+            if (p.alt_kind == CK_GEMM3_TAPS && Cin % 16 != 0) p.alt_kind = 0;      // (the GEMM stages whole 16-channel chunks of real data)
             if (p.alt_kind) {
                 p.alt_wp = alloc_packed((int64_t)p.alt_CinP * p.alt_CoutP);
                 p.alt_wpb = alloc_packed(conv1x1_h2_weight_floats(p.alt_CinP, p.alt_CoutP, 3));
@@ -203,8 +204,8 @@ struct Builder {
                 op.alt_wpb = p.alt_wpb;
                 op.alt_CinP = p.alt_CinP;
                 op.alt_CoutP = p.alt_CoutP;
-                op.alt_bias = p.alt_kind == 22 ? alloc_packed(p.alt_CoutP) : -1;           // (the packed blob is zero-filled: a zero bias)
-                if (p.alt_kind == 22) op.alt_buf = alloc(9 * Cout, op.H);
+                op.alt_bias = p.alt_kind == CK_GEMM3_TAPS ? alloc_packed(p.alt_CoutP) : -1;           // (the packed blob is zero-filled: a zero bias)
+                if (p.alt_kind == CK_GEMM3_TAPS) op.alt_buf = alloc(9 * Cout, op.H);
                 else if (9 * Cin <= 96) op.alt_buf = alloc(p.alt_CinP, op.H);                   // (wider stems: no `col` buffer, the LDS form or nothing)
             }
         }
@@ -686,13 +687,13 @@ int mcvd_model::launch_gn(const Op& op, const float* x, const void* lab, const f
     return launch_gn_coef(a, s);
 }
 
-// ---- the GEMM forms of a 3x3 conv (kernels/conv_gemm_forms.cpp; shape ids 22 / 23).  `a` = the conv's arguments as launch_op built them.
+// ---- the GEMM forms of a 3x3 conv (kernels/conv_gemm_forms.cpp; CK_GEMM3_TAPS / CK_GEMM3_IM2COL).  `a` = the conv's arguments as launch_op built them.
 bool mcvd_model::gemm_form_usable(const Op& op, const ConvArgs& a) const {
     if (!op.alt_kind || a.shape_hint != op.alt_kind || !ctx->bf16x3 || a.gb || a.ks != 3) return false;
-    if (op.alt_kind == 22 && (a.stats || a.C1 != 0)) return false;        // (the shift-and-add pass emits no GroupNorm partials; one source)
-    if (op.alt_kind == 23 && (a.coef || a.act)) return false;             // (im2col copies raw values)
+    if (op.alt_kind == CK_GEMM3_TAPS && (a.stats || a.C1 != 0)) return false;        // (the shift-and-add pass emits no GroupNorm partials; one source)
+    if (op.alt_kind == CK_GEMM3_IM2COL && (a.coef || a.act)) return false;             // (im2col copies raw values)
     ConvArgs g = gemm_form_args(op, a, nullptr);
-    if (op.alt_kind == 23 && !g.im2col && op.alt_buf.kind == REF_NONE) return false;      // (a wide stem whose geometry the LDS form does not take)
+    if (op.alt_kind == CK_GEMM3_IM2COL && !g.im2col && op.alt_buf.kind == REF_NONE) return false;      // (a wide stem whose geometry the LDS form does not take)
     for (int c = 4; c >= 1; --c)
         if (conv1x1_h2_supported(g, c, 3)) return true;
     return false;
@@ -706,10 +707,10 @@ ConvArgs mcvd_model::gemm_form_args(const Op& op, const ConvArgs& a, float* buf)
     g.wpb = packed + op.alt_wpb;
     g.wpw = nullptr; g.wph = nullptr;
     g.part = nullptr;
-    g.shape_hint = 15;
+    g.shape_hint = CK_GEMM1_BF16X3;
     g.CinP = op.alt_CinP;
     g.CoutP = op.alt_CoutP;
-    if (op.alt_kind == 22) {                 // Cin -> 9 * Cout planes of z; bias / residual / scale belong to the shift-and-add pass
+    if (op.alt_kind == CK_GEMM3_TAPS) {      // Cin -> 9 * Cout planes of z; bias / residual / scale belong to the shift-and-add pass
         g.Cout = 9 * a.Cout;
         g.bias = packed + op.alt_bias;
         g.res = nullptr; g.out_scale = 1.0f; g.stats = nullptr;
@@ -737,10 +738,10 @@ ConvArgs mcvd_model::gemm_form_args(const Op& op, const ConvArgs& a, float* buf)
 
 int mcvd_model::launch_gemm_form(const Op& op, const ConvArgs& a, float* buf, hipStream_t s) {
     const ConvArgs g = gemm_form_args(op, a, buf);
-    if (op.alt_kind == 23 && !g.im2col)
+    if (op.alt_kind == CK_GEMM3_IM2COL && !g.im2col)
         if (int rc = launch_im2col3x3(a.x0, a.C0, a.x1, a.C1, buf, a.B, a.H, a.W, op.alt_CinP, s)) return rc;
     if (int rc = launch_conv_mfma(g, s)) return rc;
-    if (op.alt_kind == 22) return launch_taps_shift_add(buf, a.bias, a.res, a.out_scale, a.y, a.B, a.Cout, a.H, a.W, s);
+    if (op.alt_kind == CK_GEMM3_TAPS) return launch_taps_shift_add(buf, a.bias, a.res, a.out_scale, a.y, a.B, a.Cout, a.H, a.W, s);
     return 0;
 }
 
@@ -796,24 +797,24 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
             a.part = (op.ks == 3 && op.H * op.W <= 256) ? ksplit_buf : nullptr;
             a.part_floats = a.part ? ksplit_floats : 0;
             const size_t oi = (size_t)(&op - ops.data());
-            if (a.shape_hint == 14 || a.shape_hint == 15) {      // forced split-operand 1x1 GEMM (tests): a cout tile that kernel serves
-                const int np = a.shape_hint == 14 ? 2 : 3;
+            if (conv_kernel(a.shape_hint).family == CF_SPLIT1) {      // forced split-operand 1x1 GEMM (tests): a cout tile that kernel serves
+                const int np = pieces(a.shape_hint);
                 for (int c = 4; c >= 1 && !conv1x1_h2_supported(a, a.cot, np); --c)
                     if (conv1x1_h2_supported(a, c, np)) a.cot = c;
             }
             if (a.shape_hint < 0 && tuned_B == B && oi < tuned_shape.size() && tuned_shape[oi] >= 0) {
                 a.shape_hint = tuned_shape[oi];
                 a.cot = tuned_cot[oi];
-                // an imported table from a run under other options: the options win.  f16x2 hints (12 / 13 / 14) go to their bf16x3
-                // counterparts (10 / 11 / 15) when f16x2 is off -- and for convs with a raw input in any case (f16x2 range guard, below);
-                // bf16x3 hints go to the fp32-MFMA kernels (4 / 8 / 5) when bf16x3 is off
+                // an imported table from a run under other options: the options win.  f16x2 hints go to their bf16x3 counterparts when
+                // f16x2 is off -- and for convs with a raw input in any case (f16x2 range guard, below); bf16x3 hints go to the fp32-MFMA
+                // kernels when bf16x3 is off (conv_kernels.h: no_f16x2 / no_bf16x3)
                 const bool raw_in = op.coef.kind == REF_NONE;
-                if ((!ctx->f16x2 || raw_in) && a.shape_hint >= 12 && a.shape_hint <= 14) {
-                    a.shape_hint = a.shape_hint == 12 ? 10 : a.shape_hint == 13 ? 11 : 15;
-                    if (a.shape_hint == 15 && !conv1x1_h2_supported(a, a.cot, 3)) a.cot = op.cot;
+                if ((!ctx->f16x2 || raw_in) && without_f16x2(a.shape_hint) != a.shape_hint) {
+                    a.shape_hint = without_f16x2(a.shape_hint);
+                    if (conv_kernel(a.shape_hint).own_cot && !conv_kernel_usable(a.shape_hint, a)) a.cot = op.cot;
                 }
-                if (!ctx->bf16x3 && (a.shape_hint == 10 || a.shape_hint == 11 || (a.shape_hint >= 15 && a.shape_hint <= 20))) {
-                    a.shape_hint = (a.shape_hint == 10 || a.shape_hint == 16) ? 4 : a.shape_hint == 15 ? 5 : 8;
+                if (!ctx->bf16x3 && without_bf16x3(a.shape_hint) != a.shape_hint) {
+                    a.shape_hint = without_bf16x3(a.shape_hint);
                     a.cot = op.cot;
                 }
             }
@@ -824,13 +825,13 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
                 // spade_apply materialises silu(((A x + B)(1 + gamma) + beta) s1 + b2) and the conv reads it plainly
                 a.gb = resolve(op.gb, x, cond, out, B);
                 a.coef2 = op.coef2.kind == REF_NONE ? nullptr : resolve(op.coef2, x, cond, out, B);
-                if (a.shape_hint == 36 || a.shape_hint == 40) a.shape_hint = -1;      // (ids of a round-5 table: the per-layer fused loader is gone)
+                if (a.shape_hint == CK_RETIRED_SPADE_WINO || a.shape_hint == CK_RETIRED_SPADE_WINO_K2) a.shape_hint = CK_AUTO;      // (a round-5 table)
                 const bool want_fused = ctx->spade_fuse && !ctx->naive_conv && ctx->winograd;
                 ConvArgs t = a;
-                t.shape_hint = (a.shape_hint == 8) ? 8 : 4;
-                t.ksplit = t.shape_hint == 8 ? 2 : 0;
+                t.shape_hint = a.shape_hint == CK_WINO_K2 ? CK_WINO_K2 : CK_WINO;
+                t.ksplit = k_parts(t.shape_hint);
                 bool fused = want_fused && conv_wino_usable(t);
-                if (!fused && t.ksplit == 2) { t.ksplit = 0; t.shape_hint = 4; fused = want_fused && conv_wino_usable(t); }
+                if (!fused && t.ksplit == 2) { t.ksplit = 0; t.shape_hint = CK_WINO; fused = want_fused && conv_wino_usable(t); }
                 if (fused) {
                     a.shape_hint = t.shape_hint;
                     ++fused_launches[2];
@@ -840,8 +841,8 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
                     a.x0 = tmp; a.x1 = nullptr; a.C0 = a.Cin; a.C1 = 0; a.coef = nullptr; a.act = 0; a.gb = nullptr; a.coef2 = nullptr;
                 }
             }
-            // (the split-operand 1x1 GEMM emits them cheaply from its transposed epilogue: shape ids 14 / 15)
-            a.stats = (ctx->gn_stats && op.stats.kind != REF_NONE && !ctx->naive_conv && (op.ks == 3 || ctx->gn_stats >= 2 || a.shape_hint == 14 || a.shape_hint == 15))
+            // (the split-operand 1x1 GEMM emits them cheaply from its transposed epilogue)
+            a.stats = (ctx->gn_stats && op.stats.kind != REF_NONE && !ctx->naive_conv && (op.ks == 3 || ctx->gn_stats >= 2 || conv_kernel(a.shape_hint).family == CF_SPLIT1))
                           ? resolve(op.stats, x, cond, out, B) : nullptr;
             if (ran_kernel.size() != ops.size()) ran_kernel.assign(ops.size(), -1);
             if (kv_live.size() != ops.size()) kv_live.assign(ops.size(), 0);
@@ -872,7 +873,7 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
                 kv_live[op.attn_op] = 0;
                 const Op& at = ops[op.attn_op];
                 const bool want = ctx->attn_presplit && !ctx->naive_conv && ctx->bf16x3 && !ctx->f16x2 && (ctx->naive_attn == 0 || ctx->naive_attn == 4) &&
-                                  !(ctx->share_fence && mcvd_ctx_shares_device(ctx)) && attn_h2p_supported(at.Cout, at.heads, at.H * at.W) && a.shape_hint == 15;
+                                  !(ctx->share_fence && mcvd_ctx_shares_device(ctx)) && attn_h2p_supported(at.Cout, at.heads, at.H * at.W) && a.shape_hint == CK_GEMM1_BF16X3;
                 if (want) {
                     ConvArgs t = a;
                     t.kv_img = resolve(op.kv, x, cond, out, B);
@@ -889,14 +890,14 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
                 ran_kernel[oi] = -2;
                 return launch_conv_naive(a, s);
             }
-            if (a.shape_hint == 22 || a.shape_hint == 23) {
+            if (conv_kernel(a.shape_hint).family == CF_GEMM3) {
                 if (gemm_form_usable(op, a)) {
                     const int rc = launch_gemm_form(op, a, resolve(op.alt_buf, x, cond, out, B), s);
                     stats_np[oi] = a.stats ? last_conv_stats_np() : 0;
                     ran_kernel[oi] = op.alt_kind;
                     return rc;
                 }
-                a.shape_hint = -1;               // (forced for the whole network, or a table of another build: the dispatcher's own choice)
+                a.shape_hint = CK_AUTO;          // (forced for the whole network, or a table of another build: the dispatcher's own choice)
                 a.cot = op.cot;
             }
             const int rc = launch_conv_mfma(a, s);
@@ -1056,20 +1057,24 @@ int mcvd_model::autotune(int B) {
                 if (ms < best_ms) { best_ms = ms; choice = {shape, cot}; }
                 return 0;
             };
+            auto offer = [&](int id, int cot) -> int {                      // a kernel of the table, timed where it takes this layer with this cout tile
+                a.cot = cot;
+                return conv_kernel_usable(id, a) ? time_candidate(id, cot) : 0;
+            };
             const int cots[2] = {op.cot, 1};
             for (int ci = 0; ci < (op.cot == 1 ? 1 : 2); ++ci) {
-                for (int shape = 0; shape < 5; ++shape) {
-                    if (spade_fused && conv_wino_usable(a) && shape != 4) continue;   // SPADE prologue: the Winograd kernel only
-                    if (shape == 3 && (op.ks != 3 || !ctx->conv_wdma)) continue;      // 3 = split-K with double-buffered weights
-                    if (shape == 4 && (ci > 0 || !ctx->winograd || !conv_wino_usable(a))) continue;   // 4 = Winograd F(2x2,3x3), own cout tile
-                    const int bpx = shape == 0 ? 256 : shape == 1 ? 128 : 64;
+                for (int shape = CK_TILE256; shape <= CK_WINO; ++shape) {
+                    if (spade_fused && conv_kernel_usable(CK_WINO, a) && shape != CK_WINO) continue;   // SPADE prologue: the Winograd kernel only
+                    if (shape == CK_TILE_SPLITK && (op.ks != 3 || !ctx->conv_wdma)) continue;          // split-K with double-buffered weights
+                    if (shape == CK_WINO && (ci > 0 || !ctx->winograd || !conv_kernel_usable(CK_WINO, a))) continue;   // own cout tile
+                    const int bpx = shape == CK_TILE256 ? 256 : shape == CK_TILE128 ? 128 : 64;
                     const bool fits = bpx % op.W == 0 && (bpx / op.W <= op.H ? op.H % (bpx / op.W) == 0 : (bpx / op.W) % op.H == 0);
-                    if (shape != 4 && !fits) continue;
+                    if (shape != CK_WINO && !fits) continue;
                     if (int rc = time_candidate(shape, cots[ci])) return rc;
                 }
             }
             a.cot = op.cot;
-            if (op.alt_kind && !spade_fused && op.gb.kind == REF_NONE) {         // 22 / 23 = the conv as a 1x1 GEMM on the three-piece kernel + its copy / shift pass
+            if (op.alt_kind && !spade_fused && op.gb.kind == REF_NONE) {         // the conv as a 1x1 GEMM on the three-piece kernel + its copy / shift pass
                 ConvArgs t = a;
                 t.shape_hint = op.alt_kind;
                 t.stats = (ctx->gn_stats && op.stats.kind != REF_NONE) ? resolve(op.stats, scratch_io, scratch_io, scratch_io, B) : nullptr;
@@ -1089,82 +1094,50 @@ int mcvd_model::autotune(int B) {
                     if (ms < best_ms) { best_ms = ms; choice = {op.alt_kind, c}; }
                 }
             }
-            if (op.ks == 3 && ctx->winograd) {             // 8 = Winograd with a 2-way K split (more workgroups: 8x8 layers)
-                ConvArgs b = a;
-                b.ksplit = 2;
-                if (conv_wino_usable(b))
-                    if (int rc = time_candidate(8, op.cot)) return rc;
-            }
-            if (op.ks == 3 && ctx->winograd && ctx->bf16x3 && !spade_fused) {     // 10 / 11 = Winograd on the bf16 pipe, three exact pieces per operand
-                ConvArgs b = a;
-                b.ksplit = 0;
-                if (conv_wino3_usable(b))
-                    if (int rc = time_candidate(10, op.cot)) return rc;
-                b.ksplit = 2;
-                if (conv_wino3_usable(b))
-                    if (int rc = time_candidate(11, op.cot)) return rc;
-                // 16 / 17 = the same kernel as persistent workgroups (conv_wino3p.cpp): the staging pipeline runs on across the items of a CU
-                b.ksplit = 0;
-                if (conv_wino3p_usable(b))
-                    if (int rc = time_candidate(16, op.cot)) return rc;
-                b.ksplit = 2;
-                if (conv_wino3p_usable(b))
-                    if (int rc = time_candidate(17, op.cot)) return rc;
-                // 18 / 19 / 20 = 4 / 8 K parts (20: persistent, 4 parts), offered where the 2-way split leaves the chip with less than
-                // a few workgroups per CU (the measurement decides; above that the reduce pass only costs)
+            if (op.ks == 3 && ctx->winograd)               // the K split fills the CUs on 8x8 layers
+                if (int rc = offer(CK_WINO_K2, op.cot)) return rc;
+            if (op.ks == 3 && ctx->winograd && ctx->bf16x3 && !spade_fused) {     // Winograd on the bf16 pipe, three exact pieces per operand
+                for (int id : {CK_WINO3, CK_WINO3_K2, CK_WINO3P, CK_WINO3P_K2})    // (persistent: the staging pipeline runs on across the items of a CU)
+                    if (int rc = offer(id, op.cot)) return rc;
+                // 4 / 8 K parts are offered where the 2-way split leaves the chip with less than a few workgroups per CU (the measurement
+                // decides; above that the reduce pass only costs)
                 const bool g8 = op.H == 8 && op.W == 8;
                 const long pairs = (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout)));
                 if (2 * pairs < 1024) {
-                    b.ksplit = 4;
-                    if (conv_wino3_usable(b))
-                        if (int rc = time_candidate(18, op.cot)) return rc;
-                    if (conv_wino3p_usable(b))
-                        if (int rc = time_candidate(20, op.cot)) return rc;
-                    b.ksplit = 8;
-                    if (4 * pairs < 1024 && conv_wino3_usable(b))
-                        if (int rc = time_candidate(19, op.cot)) return rc;
+                    for (int id : {CK_WINO3_K4, CK_WINO3P_K4})
+                        if (int rc = offer(id, op.cot)) return rc;
+                    if (4 * pairs < 1024)
+                        if (int rc = offer(CK_WINO3_K8, op.cot)) return rc;
                 }
             }
             // f16x2 range guard: the two-piece fp16 kernels see GroupNorm-ed inputs only (a.coef set: normalised, O(1) by construction).
             // A conv over a RAW tensor (stem, shortcuts, NIN_3) has no bound on its input and stays on the fp32-range kernels.
             const bool f16_ok = ctx->f16x2 && a.coef != nullptr;
-            if (op.ks == 3 && ctx->winograd && f16_ok && !spade_fused) {          // 12 / 13 = Winograd on the fp16 pipe, two-piece operands
-                ConvArgs b = a;
-                b.ksplit = 0;
-                if (conv_wino2h_usable(b))
-                    if (int rc = time_candidate(12, op.cot)) return rc;
-                b.ksplit = 2;
-                if (conv_wino2h_usable(b))
-                    if (int rc = time_candidate(13, op.cot)) return rc;
-            }
-            if (op.ks == 1 && ctx->conv_dma1) {        // 5 / 6 = all-DMA 1x1 GEMM (16 / 32 channels per chunk), cout tiles of its own
+            if (op.ks == 3 && ctx->winograd && f16_ok && !spade_fused)            // Winograd on the fp16 pipe, two-piece operands
+                for (int id : {CK_WINO2H, CK_WINO2H_K2})
+                    if (int rc = offer(id, op.cot)) return rc;
+            if (op.ks == 1 && ctx->conv_dma1) {        // the 1x1 GEMMs, cout tiles of their own
                 // small cout tiles first: the sweep of every 1x1 layer shape (profiles/r02_conv1x1_candidates.txt) has tiles 1-3 winning
                 // everywhere; 6 / 9 never did
                 static const int g1_cots[] = {2, 1, 3, 4, 6, 9};
-                for (int ck = 16; ck <= 32; ck += 16) {
-                    if (!conv1x1_dma_supported(a, ck)) continue;
+                for (int id : {CK_DMA1, CK_DMA1_CK32}) {
                     int tried = 0;
                     for (int c : g1_cots) {
-                        if ((op.CoutP / 32) % c != 0 || tried >= 3 || (ck == 32 && c == 9)) continue;
+                        a.cot = c;
+                        if ((op.CoutP / 32) % c != 0 || tried >= 3 || !conv_kernel_usable(id, a)) continue;
                         ++tried;
-                        if (int rc = time_candidate(ck == 16 ? 5 : 6, c)) return rc;
+                        if (int rc = time_candidate(id, c)) return rc;
                     }
                 }
-                if (f16_ok) {                               // 14 = the GEMM on the fp16 pipe with two-piece operands, cout tiles 1..4
+                if (f16_ok)                                 // the split-operand GEMMs, cout tiles 1..4: two fp16 pieces ...
                     for (int c = 4; c >= 1; --c)
-                        if (conv1x1_h2_supported(a, c, 2))
-                            if (int rc = time_candidate(14, c)) return rc;
-                }
-                if (ctx->bf16x3) {                          // 15 = the GEMM on the bf16 pipe with three exact pieces per operand
+                        if (int rc = offer(CK_GEMM1_F16X2, c)) return rc;
+                if (ctx->bf16x3)                            // ... three exact bf16 pieces
                     for (int c = 4; c >= 1; --c)
-                        if (conv1x1_h2_supported(a, c, 3))
-                            if (int rc = time_candidate(15, c)) return rc;
-                }
-                if (conv1x1_dma_supported(a, 16, 2)) {      // 9 = the same GEMM with 64 pixels per wave (256-pixel tiles), cout tiles 1 / 2
-                    if (int rc = time_candidate(9, 1)) return rc;
-                    if ((op.CoutP / 32) % 2 == 0)
-                        if (int rc = time_candidate(9, 2)) return rc;
-                }
+                        if (int rc = offer(CK_GEMM1_BF16X3, c)) return rc;
+                if (int rc = offer(CK_DMA1_PX64, 1)) return rc;              // 256-pixel tiles, cout tiles 1 / 2
+                if ((op.CoutP / 32) % 2 == 0)
+                    if (int rc = offer(CK_DMA1_PX64, 2)) return rc;
             }
             it = best.emplace(k, choice).first;
         }
@@ -1214,7 +1187,7 @@ int mcvd_model::ensure_f16x2_weights() {
 
 // Partial-output buffer of the K-split Winograd layers (H*W <= 256): `parts` x B x Cout x HW floats for the DEEPEST split anything can
 // select at this batch (it was 8 parts for every model and batch, ~200 MB for config 2 at B = 64 where no layer ever takes more
-// than 2): 2 parts everywhere; 4 / 8 where the autotuner's own rule offers shape ids 18 / 20 / 19 (few (region, cout tile) pairs:
+// than 2): 2 parts everywhere; 4 / 8 where the autotuner's own rule offers the 4- / 8-part kernels (few (region, cout tile) pairs:
 // autotune()), where a test forces one of them (conv_shape), or where an installed table for this batch names one.
 int mcvd_model::ensure_ksplit(int B) {
     size_t need = 0;
@@ -1228,7 +1201,7 @@ int mcvd_model::ensure_ksplit(int B) {
         const bool g8 = op.H == 8 && op.W == 8;
         const long pairs = (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout)));
         if (ctx->autotune && !table && tuned_B != B && 2 * pairs < 1024) parts = 4 * pairs < 1024 ? 8 : 4;    // the candidates autotune() is about to time
-        auto deepen = [&](int shape) { if (shape == 19) parts = std::max(parts, 8); else if (shape == 18 || shape == 20) parts = std::max(parts, 4); };
+        auto deepen = [&](int shape) { parts = std::max(parts, k_parts(shape)); };
         deepen(ctx->conv_shape);
         if (table) deepen((*table)[i]);
         if (tuned_B == B && i < tuned_shape.size()) deepen(tuned_shape[i]);
@@ -1252,8 +1225,8 @@ int mcvd_model::prepare_B(int B) {
     // autotune() then times (the launches carry the capacity as well, ConvArgs::part_floats)
     sync_tuning_options();
     if (int rc = ensure_ksplit(B)) return rc;
-    // (a forced two-piece kernel family -- the tests' conv_shape 12 / 13 / 14 -- needs the pieces as well as the option does)
-    const bool forced_h = (ctx->conv_shape >= 12 && ctx->conv_shape <= 14) || ctx->conv_shape1 == 14;
+    // (a forced two-piece kernel family -- tests -- needs the pieces as well as the option does)
+    const bool forced_h = pieces(ctx->conv_shape) == 2 || ctx->conv_shape1 == CK_GEMM1_F16X2;
     if (ctx->f16x2 || forced_h)
         if (int rc = ensure_f16x2_weights()) return rc;
     if (!ctx->naive_conv && tuned_B != B) {

@@ -107,8 +107,8 @@ struct Op {
     int64_t wpb = -1;              // the same, pre-split into three bf16 pieces (conv_wino3.cpp / conv1x1_h2.cpp), else -1
     int CinP = 0, CoutP = 0, cot = 0;
     float out_scale = 1.f;
-    // 3x3 conv that can also run as a 1x1 GEMM on the three-piece bf16 kernel (kernels/conv_gemm_forms.cpp): alt_kind = 23 im2col (few
-    // input channels: the stem), 22 taps as outputs (few output channels: the last conv); the GEMM's packed matrix / pieces / zero bias,
+    // 3x3 conv that can also run as a 1x1 GEMM on the three-piece bf16 kernel (kernels/conv_gemm_forms.cpp): alt_kind is CK_GEMM3_IM2COL (few
+    // input channels: the stem) or CK_GEMM3_TAPS (few output channels: the last conv), 0 = none; the GEMM's packed matrix / pieces / zero bias,
     // its padded dims and the per-sample buffer (the im2col rows, or the 9 * Cout planes of z)
     int alt_kind = 0;
     int64_t alt_wp = -1, alt_wpb = -1, alt_bias = -1;
@@ -152,7 +152,7 @@ struct ConvPack {
     int64_t wpw = -1;
     int64_t wph = -1;
     int64_t wpb = -1;
-    int alt_kind = 0;                   // 22 / 23: the conv's GEMM form is packed too (Op::alt_kind)
+    int alt_kind = 0;                   // != 0: the conv's GEMM form is packed too (Op::alt_kind)
     int64_t alt_wp = -1, alt_wpb = -1;
     int alt_CinP = 0, alt_CoutP = 0;
     bool zero_bias = false;             // the packed bias stays zero (the shortcut GEMM of an up block: its bias is added elsewhere)
