@@ -28,6 +28,7 @@
  *                                            models/better/op/upfirdn2d.cpp:12-23
  *   mcvd_model_export_blob/import_blob    <- nn.DataParallel's per-forward replicate (runners/ncsn_runner.py:924);
  *                                            here ONE broadcast of the packed blob at load time
+ *   mcvd_frame_metrics                    <- the per-frame MSE / SSIM loop of video_gen's test mode, runners/ncsn_runner.py:1580-1609
  */
 #ifndef MCVD_HIP_H
 #define MCVD_HIP_H
@@ -318,6 +319,19 @@ int mcvd_randn(mcvd_ctx* ctx, float* out, uint64_t seed, uint64_t sample_offset,
 /* uint8 frame packing of the result side (runners/ncsn_runner.py:2019-2062: each frame BCHW -> HWC, `(frame * 255).astype('uint8')`):
  * frames01:[B, T*C, H, W] fp32 in [0, 1] (inverse_data_transform's output, frame-major channels) -> out:[B, T, H, W, C] uint8. */
 int mcvd_pack_frames_u8(mcvd_ctx* ctx, const float* frames01, uint8_t* out, int B, int T, int C, int H, int W);
+/* Per-frame MSE and SSIM of video_gen's test mode (replaces the per-frame loop of runners/ncsn_runner.py:1580-1609, and :1749-1778 for
+ * phase (2)).  pred01, real01: [B, T*C, H, W] fp32 in [0, 1] (inverse_data_transform's output, frame-major channels).  For frame t of row b:
+ *   mse_out[b*T + t]  (fp32)  F.mse_loss(real, pred) over its C*H*W values: fp32 differences, squared and summed in fp64, rounded once;
+ *   ssim_out[b*T + t] (fp64)  skimage structural_similarity(grey_p, grey_r, data_range=255, gaussian_weights=True,
+ *                             use_sample_covariance=False) of the frames' grey planes: ToPILImage (x.mul(255).byte()) -> convert("RGB")
+ *                             -> convert("L") (Pillow's luma (19595 R + 38470 G + 7471 B + 0x8000) >> 16).
+ * flags: MCVD_METRIC_ROUND_BINARY = the MNIST rule (:1596-1599): both frames torch.round()ed (half to even) before quantisation.
+ * grey_out: NULL, or [2, B, T, H, W] uint8 that receives the grey planes of pred, then of real (tests).
+ * MCVD_EINVAL for C not in {1, 3} (torchvision's LA / RGBA images of C = 2 / 4 are not served: no MCVD dataset has them), H or W < 11
+ * (skimage raises for frames smaller than its 11 x 11 window) or a NULL required pointer.  Deterministic: bit-identical run to run. */
+#define MCVD_METRIC_ROUND_BINARY 1
+int mcvd_frame_metrics(mcvd_ctx* ctx, const float* pred01, const float* real01, int B, int T, int C, int H, int W, int flags, float* mse_out,
+                       double* ssim_out, uint8_t* grey_out);
 /* Standardised gamma noise of the `gamma=True` samplers (models/__init__.py:273-276, :319-322): out = (g - kt) / sd, g = raw[i]
  * when raw != NULL (a Gamma(k, rate 1/theta).sample() drawn elsewhere) else theta * Gamma(k) from the library's Philox stream;
  * kt = k * theta and sd = sqrt(1 - alpha_i) are passed as the fp32 scalars the reference computes.  out:[B, per_sample]. */

@@ -1083,6 +1083,21 @@ int mcvd_pack_frames_u8(mcvd_ctx* ctx, const float* frames01, uint8_t* out, int 
     return launch_pack_frames_u8(frames01, out, B, T, C, H * W, ctx->stream);
 }
 
+int mcvd_frame_metrics(mcvd_ctx* ctx, const float* pred01, const float* real01, int B, int T, int C, int H, int W, int flags, float* mse_out,
+                       double* ssim_out, uint8_t* grey_out) {
+    API_TRY
+    MCVD_REQUIRE(ctx && pred01 && real01 && mse_out && ssim_out, "frame_metrics: NULL argument");
+    MCVD_REQUIRE(C == 1 || C == 3, "frame_metrics: channels must be 1 (L) or 3 (RGB), got %d", C);
+    MCVD_REQUIRE(H >= 11 && W >= 11, "frame_metrics: %d x %d frame is smaller than the 11 x 11 SSIM window", H, W);
+    MCVD_REQUIRE(B > 0 && T > 0 && (int64_t)B * T < (1LL << 31), "frame_metrics: bad B = %d, T = %d", B, T);
+    MCVD_REQUIRE((flags & ~MCVD_METRIC_ROUND_BINARY) == 0, "frame_metrics: unknown flags 0x%x", flags);
+    const int frames = B * T;
+    if (int rc = ctx->ensure_scratch((size_t)frame_metrics_scratch_bytes(frames, H, W))) return rc;
+    return launch_frame_metrics(pred01, real01, frames, C, H, W, (flags & MCVD_METRIC_ROUND_BINARY) ? 1 : 0, mse_out, ssim_out, grey_out,
+                                (double*)ctx->scratch, ctx->stream);
+    API_CATCH
+}
+
 int mcvd_gamma_noise(mcvd_ctx* ctx, float* out, const float* raw, float k, float theta, float kt, float sd, uint64_t seed,
                      uint64_t sample_offset, uint64_t draw, int B, int64_t per_sample) {
     MCVD_REQUIRE(ctx && out, "gamma_noise: NULL argument");

@@ -261,6 +261,10 @@ int launch_renoise(float* x, const float* noise, float ca, float cb, int64_t n, 
 int launch_axpy_out(float* x, const float* eps, float c, int64_t n, hipStream_t s);   // x -= c * eps
 int launch_nonfinite_flag(const float* v, int64_t n, int* flag, hipStream_t s);          // *flag = 1 if any v[i] is Inf / NaN (f16x2 range guard)
 int launch_pack_frames_u8(const float* in, uint8_t* out, int B, int T, int C, int HW, hipStream_t s);
+// per-frame MSE (fp32) and SSIM (fp64) of video_gen's test mode, kernels/metrics.cpp; part: frame_metrics_scratch_bytes of device scratch
+int64_t frame_metrics_scratch_bytes(int frames, int H, int W);
+int launch_frame_metrics(const float* pred, const float* real, int frames, int C, int H, int W, int binary, float* mse_out, double* ssim_out,
+                         unsigned char* grey_out, double* part, hipStream_t s);
 int launch_randn(float* out, uint64_t seed, uint64_t sample_offset, uint64_t draw, int B, int64_t per_sample,
                  hipStream_t s);
 // standardised gamma variates (models/__init__.py:273-276, :319-322): out = (g - kt) / sd with g = raw[i] when raw != NULL, else
