@@ -29,6 +29,7 @@
  *   mcvd_model_export_blob/import_blob    <- nn.DataParallel's per-forward replicate (runners/ncsn_runner.py:924);
  *                                            here ONE broadcast of the packed blob at load time
  *   mcvd_frame_metrics                    <- the per-frame MSE / SSIM loop of video_gen's test mode, runners/ncsn_runner.py:1580-1609
+ *   mcvd_dsm_loss                         <- anneal_dsm_score_estimation, losses/dsm.py:7-52 (NCSNRunner.test, ncsn_runner.py:2370-2430)
  */
 #ifndef MCVD_HIP_H
 #define MCVD_HIP_H
@@ -332,6 +333,25 @@ int mcvd_pack_frames_u8(mcvd_ctx* ctx, const float* frames01, uint8_t* out, int 
 #define MCVD_METRIC_ROUND_BINARY 1
 int mcvd_frame_metrics(mcvd_ctx* ctx, const float* pred01, const float* real01, int B, int T, int C, int H, int W, int flags, float* mse_out,
                        double* ssim_out, uint8_t* grey_out);
+/* Denoising score-matching loss of a checkpoint on a batch, forward only (anneal_dsm_score_estimation, losses/dsm.py:7-52, for versions
+ * DDPM / DDIM / FPNDM).  Three steps on the context's stream, with a = alphas[labels[b]] per row:
+ *   z           = the caller's z, or drawn on the device: Philox normals keyed by (seed, sample_offset + row, draw word 2^40, element) --
+ *                 mcvd_randn's layout for that draw word, so a row's z does not depend on how the batch is sharded;
+ *                 MCVD_DSM_GAMMA: (g - k_cum[t] * theta_t[t]) / sqrt(1 - a), g = the caller's z (then the RAW Gamma(k_cum, scale theta_t)
+ *                 draw, what Gamma(...).sample() returns in the reference) or the library's Philox gamma stream
+ *   perturbed_x = sqrt(a) * x + sqrt(1 - a) * z       (fp32, the reference's roundings: correctly rounded sqrt, 1 - a rounded first)
+ *   eps         = the UNet forward on (perturbed_x, labels, cond, cond_mask) -- as mcvd_unet_forward_masked (cond_mask NULL = ones);
+ *                 a noise_in_cond net draws its conditioning noise as every forward does (mcvd_model_set_cond_noise injects it)
+ *   loss_rows[b] = sum over the row of the fp32 terms 0.5f * (z - eps)^2, or |z - eps| with MCVD_DSM_L1, accumulated in fp64 and
+ *                 rounded once (deterministic: bit-identical run to run).  The caller takes the mean over rows (loss.mean(dim=0)).
+ * x: [B, C*nf, S, S], labels: [B] int64, cond: [B, C*nc, S, S] (NULL iff nc == 0), z: like x or NULL, loss_rows: [B] fp32.
+ * z_out / perturbed_out: NULL, or like x -- receive z (standardised under gamma) and perturbed_x (tests).  z, perturbed_x and the
+ * partial sums otherwise live in the model's workspace (allocated once per batch size, like the forward's arena).
+ * MCVD_EINVAL for MCVD_DSM_GAMMA without mcvd_model_set_gamma_tables, unknown flags or a NULL required pointer. */
+#define MCVD_DSM_L1 1      /* training.L1: |z - eps| instead of 1/2 (z - eps)^2 (losses/dsm.py:41-46) */
+#define MCVD_DSM_GAMMA 2   /* gamma=True: standardised Gamma noise (losses/dsm.py:30-34) */
+int mcvd_dsm_loss(mcvd_model* m, const float* x, const int64_t* labels, const float* cond, const int32_t* cond_mask, const float* z,
+                  uint64_t seed, uint64_t sample_offset, int flags, float* loss_rows, float* z_out, float* perturbed_out, int B);
 /* Standardised gamma noise of the `gamma=True` samplers (models/__init__.py:273-276, :319-322): out = (g - kt) / sd, g = raw[i]
  * when raw != NULL (a Gamma(k, rate 1/theta).sample() drawn elsewhere) else theta * Gamma(k) from the library's Philox stream;
  * kt = k * theta and sd = sqrt(1 - alpha_i) are passed as the fp32 scalars the reference computes.  out:[B, per_sample]. */

@@ -29,6 +29,7 @@ class UNetDesc(C.Structure):
 SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
 FLAG_DENOISE, FLAG_CLIP_BEFORE, FLAG_JUST_BETA, FLAG_GAMMA = 1, 2, 4, 8
 METRIC_ROUND_BINARY = 1
+DSM_L1, DSM_GAMMA = 1, 2
 
 _vp, _i, _f, _i64, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
 _PROTOS = {
@@ -84,6 +85,7 @@ _PROTOS = {
     "mcvd_pack_frames_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "mcvd_frame_metrics": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mcvd_gamma_noise": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _u64, _u64, _u64, _i, _i64]),
+    "mcvd_dsm_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _i]),
     "mcvd_lincomb": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i64]),
     "mcvd_pndm_transfer": (_i, [_vp, _vp, _vp, _vp, _f, _f, _f, _i, _i64]),
     "mcvd_upfirdn2d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _i]),

@@ -458,6 +458,8 @@ void mcvd_model_destroy(mcvd_model* m) {
     if (m->alphas_dev) (void)hipFree(m->alphas_dev);
     if (m->cond_z) (void)hipFree(m->cond_z);
     if (m->noise_buf) (void)hipFree(m->noise_buf);
+    if (m->gamma_dev) (void)hipFree(m->gamma_dev);
+    if (m->dsm_buf) (void)hipFree(m->dsm_buf);
     for (hipEvent_t e : m->ev) (void)hipEventDestroy(e);
     delete m;
 }
@@ -643,6 +645,7 @@ int mcvd_model_set_gamma_tables(mcvd_model* m, const float* k_cum, const float* 
     MCVD_REQUIRE(m && k_cum && theta_t && n == m->d.num_classes, "set_gamma_tables: bad arguments");
     m->k_cum.assign(k_cum, k_cum + n);
     m->theta_t.assign(theta_t, theta_t + n);
+    m->gamma_dev_valid = false;
     return 0;
 }
 
@@ -1095,6 +1098,61 @@ int mcvd_frame_metrics(mcvd_ctx* ctx, const float* pred01, const float* real01, 
     if (int rc = ctx->ensure_scratch((size_t)frame_metrics_scratch_bytes(frames, H, W))) return rc;
     return launch_frame_metrics(pred01, real01, frames, C, H, W, (flags & MCVD_METRIC_ROUND_BINARY) ? 1 : 0, mse_out, ssim_out, grey_out,
                                 (double*)ctx->scratch, ctx->stream);
+    API_CATCH
+}
+
+// anneal_dsm_score_estimation (losses/dsm.py:7-52): perturbation, one forward, per-row reduction (kernels/dsm.cpp)
+int mcvd_dsm_loss(mcvd_model* m, const float* x, const int64_t* labels, const float* cond, const int32_t* cond_mask, const float* z,
+                  uint64_t seed, uint64_t sample_offset, int flags, float* loss_rows, float* z_out, float* perturbed_out, int B) {
+    API_TRY
+    MCVD_REQUIRE(m && x && labels && loss_rows && B > 0, "dsm_loss: bad arguments");
+    MCVD_REQUIRE(m->ctx && m->finalized, "dsm_loss before mcvd_model_finalize (or on a plan-only model)");
+    MCVD_REQUIRE((flags & ~(MCVD_DSM_L1 | MCVD_DSM_GAMMA)) == 0, "dsm_loss: unknown flags 0x%x", flags);
+    const int T = m->d.num_classes;
+    const bool gam = (flags & MCVD_DSM_GAMMA) != 0;
+    MCVD_REQUIRE(!gam || ((int)m->k_cum.size() == T && (int)m->theta_t.size() == T),
+                 "dsm_loss: MCVD_DSM_GAMMA needs the gamma tables (mcvd_model_set_gamma_tables)");
+    const int64_t per = (int64_t)m->d.channels * m->d.num_frames * m->d.image_size * m->d.image_size;
+    MCVD_REQUIRE(per % 4 == 0, "dsm_loss: %lld elements per row is not a multiple of 4", (long long)per);
+    if (int rc = mcvd_ctx_clear_range(m->ctx)) return rc;
+    if (int rc = m->prepare_B(B)) return rc;
+    hipStream_t s = m->ctx->stream;
+    // workspace: z and perturbed_x for arena_B rows, then the partial sums (grown with the arena, never inside a steady-state call)
+    const int64_t n_arena = per * m->arena_B;
+    const int64_t parts_max = dsm_loss_parts(1, per);          // parts per row never grow with B: parts(B) * B <= parts_max * arena_B
+    if (m->dsm_B < m->arena_B) {
+        MCVD_HIP_CHECK(hipStreamSynchronize(s));
+        if (m->dsm_buf) MCVD_HIP_CHECK(hipFree(m->dsm_buf));
+        m->dsm_buf = nullptr;
+        m->dsm_B = 0;
+        MCVD_HIP_CHECK(hipMalloc((void**)&m->dsm_buf, (size_t)(2 * n_arena) * sizeof(float) + (size_t)parts_max * m->arena_B * sizeof(double)));
+        m->dsm_B = m->arena_B;
+    }
+    MCVD_REQUIRE((int64_t)dsm_loss_parts(B, per) * B <= parts_max * m->arena_B, "dsm_loss: partial-sum workspace too small");
+    float* zb = z_out ? z_out : m->dsm_buf;
+    float* pb = perturbed_out ? perturbed_out : m->dsm_buf + n_arena;
+    double* part = reinterpret_cast<double*>(m->dsm_buf + 2 * n_arena);
+    if (!m->alphas_dev) MCVD_HIP_CHECK(hipMalloc((void**)&m->alphas_dev, (size_t)T * sizeof(float)));
+    if (!m->alphas_dev_valid) {
+        MCVD_HIP_CHECK(hipMemcpyAsync(m->alphas_dev, m->alphas.data(), (size_t)T * sizeof(float), hipMemcpyHostToDevice, s));
+        m->alphas_dev_valid = true;
+    }
+    if (gam) {
+        if (!m->gamma_dev) MCVD_HIP_CHECK(hipMalloc((void**)&m->gamma_dev, (size_t)2 * T * sizeof(float)));
+        if (!m->gamma_dev_valid) {
+            MCVD_HIP_CHECK(hipMemcpyAsync(m->gamma_dev, m->k_cum.data(), (size_t)T * sizeof(float), hipMemcpyHostToDevice, s));
+            MCVD_HIP_CHECK(hipMemcpyAsync(m->gamma_dev + T, m->theta_t.data(), (size_t)T * sizeof(float), hipMemcpyHostToDevice, s));
+            m->gamma_dev_valid = true;
+        }
+    }
+    if (int rc = launch_dsm_perturb(x, z, labels, m->alphas_dev, gam ? m->gamma_dev : nullptr, gam ? m->gamma_dev + T : nullptr, T,
+                                    gam ? 1 : 0, seed, sample_offset, B, per, zb, pb, s))
+        return rc;
+    struct MaskGuard { mcvd_model* m; ~MaskGuard() { m->cond_mask = nullptr; } } mask_guard{m};
+    m->cond_mask = cond_mask;
+    if (int rc = m->forward(pb, labels, cond, m->eps_buf, B)) return rc;
+    if (int rc = launch_dsm_loss(zb, m->eps_buf, B, per, (flags & MCVD_DSM_L1) ? 1 : 0, part, loss_rows, s)) return rc;
+    return m->ctx->f16x2 ? mcvd_ctx_check_range(m->ctx) : 0;      // f16x2 range guard, as the samplers
     API_CATCH
 }
 

@@ -20,7 +20,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
          "-I", os.path.join(ROOT, "include")]
 WINO_OBJS = ("conv_wino.o", "conv_wino3.o", "conv_wino2h.o", "conv_wino3p.o")
 HOST_ONLY_FLAGS = {"model.cpp": ["-ffp-contract=off"], "api.cpp": ["-ffp-contract=off"],
-                   "sampler.cpp": ["-ffp-contract=off"]}      # sampler update kernels: one rounding per operation
+                   "sampler.cpp": ["-ffp-contract=off"],      # sampler update kernels: one rounding per operation
+                   "dsm.cpp": ["-ffp-contract=off"]}          # the loss's perturbation: the reference's separate roundings, same Philox bits
 
 
 def sources():

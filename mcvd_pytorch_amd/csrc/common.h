@@ -274,6 +274,13 @@ int launch_gamma_noise(float* out, const float* raw, float k, float theta, float
 // noise_in_cond (ncsnpp_more.py:755-768): out[b] = sqrt(alphas[t_b]) * cond[b] + sqrt(1 - alphas[t_b]) * z[b], t_b = labels[b]
 int launch_cond_noise(const float* cond, const float* z, const float* alphas_dev, const int64_t* labels, int T, float* out, int B,
                       int64_t per_sample, hipStream_t s);
+// denoising score-matching loss (losses/dsm.py:7-52), kernels/dsm.cpp.  perturb: z (the caller's zin -- under gamma the raw Gamma draw g --
+// or Philox) and px = sqrt(a) x + sqrt(1 - a) z per row; loss: loss_rows[b] = sum 1/2 (z - eps)^2 (or |z - eps|), fp64-accumulated.
+// part: dsm_loss_parts(B, per) * B doubles of device scratch
+int dsm_loss_parts(int B, int64_t per);
+int launch_dsm_perturb(const float* x, const float* zin, const int64_t* labels, const float* alphas, const float* k_cum, const float* theta,
+                       int T, int gamma, uint64_t seed, uint64_t sample_offset, int B, int64_t per, float* z, float* px, hipStream_t s);
+int launch_dsm_loss(const float* z, const float* eps, int B, int64_t per, int l1, double* part, float* loss_rows, hipStream_t s);
 // out = scale * sum_k w[k] * in[k], k < nin <= 4 (left-to-right, separately rounded, as the reference's tensor expression);
 // out may alias an input
 int launch_lincomb(float* out, const float* const* in, const float* w, float scale, int nin, int64_t n, hipStream_t s);

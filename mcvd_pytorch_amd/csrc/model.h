@@ -197,6 +197,10 @@ struct mcvd_model {
     float* noise_buf = nullptr;       // [arena_B * C*nf*S*S] standardised gamma draws of one sampler step (model.gamma)
     float cond_gamma_k = 0.f, cond_gamma_theta = 0.f;   // > 0: library-drawn conditioning noise is a standardised gamma variate (sampler loop)
     std::vector<float> k_cum, theta_t;
+    float* gamma_dev = nullptr;       // [2 * num_classes] device copy of k_cum | theta_t (mcvd_dsm_loss under gamma)
+    bool gamma_dev_valid = false;
+    float* dsm_buf = nullptr;         // mcvd_dsm_loss workspace for dsm_B rows: z, perturbed_x (floats), then the fp64 partial sums
+    int dsm_B = 0;
 
     int64_t arena_per_sample = 0;     // floats
     float* arena = nullptr;

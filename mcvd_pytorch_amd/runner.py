@@ -269,6 +269,65 @@ def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, 
     return torch.cat(preds, dim=1)[:, :C * nfp]                                         # :1569
 
 
+def _apply_ema_shadow(net, shadow):
+    """EMAHelper.register / load_state_dict(shadow) / ema(net) of NCSNRunner.test (:2388-2392, models/ema.py:9-29): every parameter that
+    requires grad takes shadow[name] (bare names: the helper unwraps DataParallel); states[0] is not read."""
+    for name, p in net.named_parameters():
+        if p.requires_grad:
+            p.data.copy_(shadow[name].to(device=p.device, dtype=p.dtype))
+    net._loaded = True                       # every parameter now holds a checkpoint value (a missing name raised KeyError above)
+    net.mark_dirty()
+
+
+@torch.no_grad()
+def test_checkpoints(config, scorenet, batches, log_path, ckpts=None, loss_fn=None, log=None):
+    """The loop of NCSNRunner.test() (runners/ncsn_runner.py:2370-2430): for each checkpoint_{ckpt}.pt in `log_path`, the DSM loss of
+    every batch and their average -> {ckpt: average test loss}.
+
+      * ckpts: default range(test.begin_ckpt, test.end_ckpt + 1, getattr(test, "freq", 5000));
+      * weights: with model.ema the EMA shadow states[-1] (register, load_state_dict, ema), else load_state_dict(states[0]);
+      * batches: any iterable of (x, y) with x [B, T, C, H, W] in [0, 1] (the reference's DataLoader), iterated once per checkpoint;
+        each x goes through data_transform and conditioning_fn(num_frames_pred=data.num_frames, prob_mask_cond, prob_mask_future,
+        conditional = num_frames_cond > 0), then `loss_fn` (default anneal_dsm_score_estimation) with the reference's keywords;
+      * the average as the reference forms it: a Python-float sum of the fp32 batch values in batch order, divided by the batch count.
+        The batch values stay on the device until the checkpoint is done (one synchronisation per checkpoint);
+      * `log` (default logging.info) receives "ckpt: {ckpt}, average test loss: {mean}" per checkpoint, the reference's line."""
+    import logging
+    import os
+    from .losses import anneal_dsm_score_estimation
+    loss_fn = loss_fn or anneal_dsm_score_estimation
+    log = log or logging.info
+    t, d, m = config.test, config.data, config.model
+    training = getattr(config, "training", None)
+    if ckpts is None:
+        ckpts = range(t.begin_ckpt, t.end_ckpt + 1, getattr(t, "freq", 5000))
+    net = scorenet.module if hasattr(scorenet, "module") else scorenet
+    conditional = d.num_frames_cond > 0
+    out = {}
+    for ckpt in ckpts:
+        states = torch.load(os.path.join(log_path, f"checkpoint_{ckpt}.pt"), map_location="cpu", weights_only=False)
+        if getattr(m, "ema", False):
+            _apply_ema_shadow(net, states[-1])
+        else:
+            net.load_state_dict(states[0])
+        net.eval()
+        values = []
+        for x, _ in batches:
+            x = data_transform(config, x.to(net.device))
+            x, cond, cond_mask = conditioning_fn(config, x, num_frames_pred=d.num_frames, prob_mask_cond=getattr(d, "prob_mask_cond", 0.0),
+                                                 prob_mask_future=getattr(d, "prob_mask_future", 0.0), conditional=conditional)
+            values.append(loss_fn(scorenet, x, labels=None, cond=cond, cond_mask=cond_mask,
+                                  loss_type=getattr(training, "loss_type", "a"), gamma=getattr(m, "gamma", False),
+                                  L1=getattr(training, "L1", False), all_frames=getattr(m, "output_all_frames", False)).reshape(()))
+        mean_loss = 0.
+        for v in (torch.stack(values).cpu().tolist() if values else []):      # test_loss.item() per batch, in batch order
+            mean_loss += v
+        mean_loss /= len(values)                                                # an empty loader divides by zero, as the reference
+        log("ckpt: {}, average test loss: {}".format(ckpt, mean_loss))
+        out[ckpt] = mean_loss
+    return out
+
+
 def frames_to_uint8(scorenet, frames01, channels):
     """[B, T*C, H, W] frames in [0, 1] (after `inverse_data_transform`) -> uint8 [B, T, H, W, C] on the device: the packing the
     reference applies to every frame before it writes GIFs / PNGs (`(frame * 255).astype('uint8')` on the HWC view,

@@ -377,21 +377,7 @@ class HipScoreNet:
                 if float_t:
                     raise IndexError("tensors used as indices must be long, int, byte or bool tensors (noise_in_cond indexes alphas "
                                      "with the labels)")
-                z = self._cond_z
-                self._cond_z = None
-                if z is None:
-                    if self.gamma:                                              # :761-765, torch's device gamma sampler like the reference
-                        ua = self.alphas[y].reshape(B, 1, 1, 1)
-                        uk = self.k_cum[y].reshape(B, 1, 1, 1).repeat(1, *cond.shape[1:])
-                        ut = self.theta_t[y].reshape(B, 1, 1, 1).repeat(1, *cond.shape[1:])
-                        z = torch.distributions.gamma.Gamma(uk, 1 / ut).sample()
-                        z = (z - uk * ut) / (1 - ua).sqrt()
-                    else:
-                        z = torch.randn_like(cond)
-                z = z.to(device=self.device, dtype=torch.float32).contiguous()
-                if z.shape != cond.shape:
-                    raise RuntimeError(f"conditioning noise has shape {tuple(z.shape)}, cond {tuple(cond.shape)}")
-                _lib.check(_lib.lib.mcvd_model_set_cond_noise(self._model, _fptr(z), 0, 0, 0), "set_cond_noise")
+                z = self._arm_cond_noise(cond, y)
             if self._desc.spade and not self.noise_in_cond:
                 # SPADE gamma/beta depend only on cond: recompute only when the tensor (or its content version) changes
                 key = (cond.data_ptr(), cond._version, B)
@@ -412,6 +398,28 @@ class HipScoreNet:
                 _lib.lib.mcvd_model_set_cond_noise(self._model, None, 0, 0, 0)          # never leave a pointer to a dead tensor behind
             _lib.check(rc, "unet_forward")
         return out
+
+    def _arm_cond_noise(self, cond, y):
+        """noise_in_cond: hand the library the conditioning noise of the next forward -- the injected tensor (set_next_cond_noise), else a
+        fresh draw with torch's device generators as the reference makes it (ncsnpp_more.py:761-767).  Returns the tensor, which must stay
+        alive until the forward is enqueued; the caller clears the library's pointer afterwards."""
+        B = cond.shape[0]
+        z = self._cond_z
+        self._cond_z = None
+        if z is None:
+            if self.gamma:                                              # :761-765, torch's device gamma sampler like the reference
+                ua = self.alphas[y].reshape(B, 1, 1, 1)
+                uk = self.k_cum[y].reshape(B, 1, 1, 1).repeat(1, *cond.shape[1:])
+                ut = self.theta_t[y].reshape(B, 1, 1, 1).repeat(1, *cond.shape[1:])
+                z = torch.distributions.gamma.Gamma(uk, 1 / ut).sample()
+                z = (z - uk * ut) / (1 - ua).sqrt()
+            else:
+                z = torch.randn_like(cond)
+        z = z.to(device=self.device, dtype=torch.float32).contiguous()
+        if z.shape != cond.shape:
+            raise RuntimeError(f"conditioning noise has shape {tuple(z.shape)}, cond {tuple(cond.shape)}")
+        _lib.check(_lib.lib.mcvd_model_set_cond_noise(self._model, _fptr(z), 0, 0, 0), "set_cond_noise")
+        return z
 
     def set_next_cond_noise(self, z):
         """noise_in_cond: use `z` (shaped like cond) instead of a fresh device draw in the NEXT forward (parity runs)."""
