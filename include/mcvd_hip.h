@@ -29,6 +29,8 @@
  *   mcvd_model_export_blob/import_blob    <- nn.DataParallel's per-forward replicate (runners/ncsn_runner.py:924);
  *                                            here ONE broadcast of the packed blob at load time
  *   mcvd_frame_metrics                    <- the per-frame MSE / SSIM loop of video_gen's test mode, runners/ncsn_runner.py:1580-1609
+ *   mcvd_lpips_create / _set_param / _finalize / _frames
+ *                                         <- eval_models.PerceptualLoss + the per-frame T2 / model_lpips.forward calls, ncsn_runner.py:1431, :1602-1605
  *   mcvd_dsm_loss                         <- anneal_dsm_score_estimation, losses/dsm.py:7-52 (NCSNRunner.test, ncsn_runner.py:2370-2430)
  */
 #ifndef MCVD_HIP_H
@@ -333,6 +335,33 @@ int mcvd_pack_frames_u8(mcvd_ctx* ctx, const float* frames01, uint8_t* out, int 
 #define MCVD_METRIC_ROUND_BINARY 1
 int mcvd_frame_metrics(mcvd_ctx* ctx, const float* pred01, const float* real01, int B, int T, int C, int H, int W, int flags, float* mse_out,
                        double* ssim_out, uint8_t* grey_out);
+/* LPIPS v0.1 (AlexNet, "net-lin") of video_gen's test mode: replaces the per-frame `T2(...)` / `model_lpips.forward` calls of
+ * runners/ncsn_runner.py:1602-1605 (phase (2): :1771-1774), i.e. eval_models.PerceptualLoss -> DistModel -> networks_basic.PNetLin over
+ * pretrained_networks.alexnet, one batch-1 forward pair and two Pillow round trips per frame.
+ *   create / destroy    <- eval_models.PerceptualLoss(model='net-lin', net='alex') (:1431).  The net runs on ctx's device and stream.
+ *   set_param           <- DistModel's load_state_dict of weights/v0.1/alex.pth (models/dist_model.py:66-72) and tv.alexnet(pretrained=True)
+ *                          (models/pretrained_networks.py:59).  Names are those of PNetLin.state_dict(): net.slice1.0 / net.slice2.3 /
+ *                          net.slice3.6 / net.slice4.8 / net.slice5.10 (.weight, .bias), lin0 .. lin4 (.model.1.weight),
+ *                          scaling_layer.shift / scaling_layer.scale; the backbone also as torchvision's features.N.weight / .bias.
+ *                          ptr: fp32, host (on_device 0) or device (1); shape / ndim: checked by element count.  MCVD_EINVAL for an unknown
+ *                          name or a wrong size.
+ *   finalize            repacks the conv weights for the GEMM kernel once.  MCVD_ESTATE, naming the first missing tensor in
+ *                          the last-error text: there are no default weights, no fallback and no download.
+ *   frames              pred01, real01: [B, T*C, H, W] fp32 in [0, 1] on the device.  Per frame: x.mul(255).byte(), RGB (C = 1 replicated),
+ *                          Pillow's bilinear resize to 128 x 128 on uint8 (bit-exact; skipped per axis where the size is 128), ToTensor,
+ *                          Normalize(0.5, 0.5), ScalingLayer, the five AlexNet taps, unit-normalised squared differences weighted by the
+ *                          lin layers, spatial means, added in tap order.  lpips_out: [B*T] fp32.  resized_out: NULL or
+ *                          [2, B, T, C, 128, 128] uint8 (pred, then real; tests).  per_tap_out: NULL or [B*T, 5] fp32 (tests).
+ *                          MCVD_ESTATE before finalize, MCVD_EINVAL for C not in {1, 3} or a NULL required pointer.  Deterministic:
+ *                          bit-identical run to run and for any split of the frames into calls.  Frames are processed in chunks of 64,
+ *                          so the workspace stays below 114 MB + 16 KiB * C * H. */
+typedef struct mcvd_lpips mcvd_lpips;
+int mcvd_lpips_create(mcvd_ctx* ctx, mcvd_lpips** out);
+void mcvd_lpips_destroy(mcvd_lpips* net);
+int mcvd_lpips_set_param(mcvd_lpips* net, const char* name, const void* ptr, const int64_t* shape, int ndim, int on_device);
+int mcvd_lpips_finalize(mcvd_lpips* net);
+int mcvd_lpips_frames(mcvd_lpips* net, const float* pred01, const float* real01, int B, int T, int C, int H, int W, float* lpips_out,
+                      uint8_t* resized_out, float* per_tap_out);
 /* Denoising score-matching loss of a checkpoint on a batch, forward only (anneal_dsm_score_estimation, losses/dsm.py:7-52, for versions
  * DDPM / DDIM / FPNDM).  Three steps on the context's stream, with a = alphas[labels[b]] per row:
  *   z           = the caller's z, or drawn on the device: Philox normals keyed by (seed, sample_offset + row, draw word 2^40, element) --
@@ -378,6 +407,11 @@ int mcvd_upfirdn2d(mcvd_ctx* ctx, const float* in, const float* kernel_host, int
 int mcvd_op_conv2d(mcvd_ctx* ctx, const float* x0, int C0, const float* x1, int C1, const float* w, const float* bias,
                    int Cout, int ks, const float* coef, int act, const float* res, float out_scale, float* y, int B, int H,
                    int W);
+/* y = relu?( conv2d(x, w, bias, stride, padding) ): the general conv LPIPS's AlexNet runs on (implicit GEMM on the fp32 MFMA, exact fp32
+ * products; any odd ks, any stride, zero padding, any map size; torch's F.conv2d).  x:[B,Cin,H,W], w:[Cout,Cin,ks,ks] reference layout
+ * (device; repacked into the context's scratch per call), bias:[Cout] or NULL, y:[B,Cout,OH,OW], OH = (H + 2 pad - ks) / stride + 1. */
+int mcvd_op_conv2d_strided(mcvd_ctx* ctx, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, int ks,
+                           int stride, int pad, int relu, float* y);
 /* Which kernel family the calling thread's last conv launch (mcvd_op_conv2d or a model forward) was dispatched to: the ids of the
  * "conv_shape" option (0..3 direct implicit-GEMM tile shapes, 4 / 8 fp32 Winograd, 5 / 6 / 9 fp32 1x1 GEMM, 10 / 11 three-piece bf16
  * Winograd, 12 / 13 two-piece fp16 Winograd, 14 / 15 split-operand 1x1 GEMM); -1 none yet.  A forced "conv_shape" that does not apply to a

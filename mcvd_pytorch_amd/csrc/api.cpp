@@ -19,6 +19,7 @@
 
 #include "model.h"
 #include "conv_kernels.h"
+#include "lpips.h"
 
 using namespace mcvd;
 
@@ -1098,6 +1099,70 @@ int mcvd_frame_metrics(mcvd_ctx* ctx, const float* pred01, const float* real01, 
     if (int rc = ctx->ensure_scratch((size_t)frame_metrics_scratch_bytes(frames, H, W))) return rc;
     return launch_frame_metrics(pred01, real01, frames, C, H, W, (flags & MCVD_METRIC_ROUND_BINARY) ? 1 : 0, mse_out, ssim_out, grey_out,
                                 (double*)ctx->scratch, ctx->stream);
+    API_CATCH
+}
+
+// LPIPS v0.1 on AlexNet (kernels/lpips.cpp)
+int mcvd_lpips_create(mcvd_ctx* ctx, mcvd_lpips** out) {
+    API_TRY
+    MCVD_REQUIRE(ctx && out, "lpips_create: NULL argument");
+    mcvd_lpips* n = new mcvd_lpips();
+    n->ctx = ctx;
+    *out = n;
+    return 0;
+    API_CATCH
+}
+
+void mcvd_lpips_destroy(mcvd_lpips* net) { delete net; }
+
+int mcvd_lpips_set_param(mcvd_lpips* net, const char* name, const void* ptr, const int64_t* shape, int ndim, int on_device) {
+    API_TRY
+    MCVD_REQUIRE(net && name && ptr && shape && ndim >= 1 && ndim <= 8, "lpips_set_param: bad arguments");
+    int64_t numel = 1;
+    for (int i = 0; i < ndim; ++i) {
+        MCVD_REQUIRE(shape[i] > 0 && shape[i] < (1 << 24), "lpips_set_param: bad shape");
+        numel *= shape[i];
+    }
+    MCVD_REQUIRE(numel < (1LL << 28), "lpips_set_param: '%s' is too large", name);
+    if (!on_device) return lpips_set_param(net, name, (const float*)ptr, numel);
+    std::vector<float> host((size_t)numel);
+    MCVD_HIP_CHECK(hipMemcpyAsync(host.data(), ptr, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost, net->ctx->stream));
+    MCVD_HIP_CHECK(hipStreamSynchronize(net->ctx->stream));
+    return lpips_set_param(net, name, host.data(), numel);
+    API_CATCH
+}
+
+int mcvd_lpips_finalize(mcvd_lpips* net) {
+    API_TRY
+    MCVD_REQUIRE(net && net->ctx, "lpips_finalize: NULL net");
+    return lpips_finalize(net);
+    API_CATCH
+}
+
+int mcvd_lpips_frames(mcvd_lpips* net, const float* pred01, const float* real01, int B, int T, int C, int H, int W, float* lpips_out,
+                      uint8_t* resized_out, float* per_tap_out) {
+    API_TRY
+    MCVD_REQUIRE(net && net->ctx && pred01 && real01 && lpips_out, "lpips_frames: NULL argument");
+    MCVD_REQUIRE(C == 1 || C == 3, "lpips_frames: channels must be 1 (L) or 3 (RGB), got %d", C);
+    MCVD_REQUIRE(B > 0 && T > 0 && (int64_t)B * T < (1LL << 24), "lpips_frames: bad B = %d, T = %d", B, T);
+    MCVD_REQUIRE(H > 0 && W > 0 && H <= 16384 && W <= 16384, "lpips_frames: bad frame size %d x %d", H, W);
+    if (!net->finalized) {
+        set_error("lpips_frames before mcvd_lpips_finalize");
+        return MCVD_ESTATE;
+    }
+    return lpips_frames(net, pred01, real01, B, T, C, H, W, lpips_out, resized_out, per_tap_out);
+    API_CATCH
+}
+
+int mcvd_op_conv2d_strided(mcvd_ctx* ctx, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, int ks,
+                           int stride, int pad, int relu, float* y) {
+    API_TRY
+    MCVD_REQUIRE(ctx && x && w && y, "op_conv2d_strided: NULL argument");
+    MCVD_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && ks >= 1 && ks <= 31 && (ks & 1) && Cin <= 65536 && Cout <= 65536, "op_conv2d_strided: bad shape");
+    const size_t wfloats = (size_t)conv_gemm_kp(Cin, ks) * conv_gemm_coutp(Cout);
+    if (int rc = ctx->ensure_scratch(wfloats * sizeof(float))) return rc;
+    if (int rc = launch_pack_conv_gemm(w, ctx->scratch, Cout, Cin, ks, ctx->stream)) return rc;
+    return launch_conv_gemm(x, ctx->scratch, bias, y, B, Cin, H, W, Cout, ks, stride, pad, relu, ctx->stream);
     API_CATCH
 }
 

@@ -91,7 +91,10 @@ class _ToPILImage:
         return Image.fromarray(a[:, :, 0], mode="L") if a.shape[2] == 1 else Image.fromarray(a, mode="RGB")
 
 
-def gen_case(case, subsample=10):
+def gen_case(case, subsample=10, perceptual=None, extra=None, save=True):
+    """perceptual / extra / save: hooks of tools/gen_lpips_golden.py -- `perceptual(R)` builds what replaces eval_models.PerceptualLoss
+    (default: the zero distance), `extra(R, stack)` enters further patches, save=False returns the fixture dict (with the runner's
+    vid_lpips lists) instead of writing it.  The defaults write exactly the fixture described above."""
     spec = CASES[case]
     R = import_real_runner()
     batch, ppt = spec["batch"], spec["ppt"]
@@ -174,14 +177,14 @@ def gen_case(case, subsample=10):
 
     def get_proc_mem():
         f = sys._getframe(1).f_locals
-        for k in ("vid_metrics", "vid_mse", "vid_ssim", "vid_mse2", "vid_ssim2"):
+        for k in ("vid_metrics", "vid_mse", "vid_ssim", "vid_mse2", "vid_ssim2", "vid_lpips", "vid_lpips2"):
             grabbed[k] = f.get(k)
         raise _Cut()
 
     def on_return(frame, event, arg):
         # the "cannot calculate" run returns at :2192 before get_proc_mem: its lists are read from video_gen's frame as it returns
         if event == "return" and frame.f_code.co_name == "video_gen":
-            for k in ("vid_mse", "vid_ssim", "vid_mse2", "vid_ssim2"):
+            for k in ("vid_mse", "vid_ssim", "vid_mse2", "vid_ssim2", "vid_lpips", "vid_lpips2"):
                 grabbed[k] = frame.f_locals.get(k)
 
     log = io.StringIO()
@@ -189,10 +192,12 @@ def gen_case(case, subsample=10):
     root = logging.getLogger()
     root.addHandler(handler)
     root.setLevel(logging.INFO)
+    model_lpips = perceptual(R) if perceptual is not None else _Lpips()      # built before the seed: its construction draws
     torch.manual_seed(1234)
     try:
-        with contextlib.redirect_stdout(io.StringIO()), mock.patch.object(R, "get_dataset", lambda *a, **kw: (ds, ds)), \
-                mock.patch.object(R.eval_models, "PerceptualLoss", lambda *a, **kw: _Lpips()), \
+        with contextlib.ExitStack() as stack, contextlib.redirect_stdout(io.StringIO()), \
+                mock.patch.object(R, "get_dataset", lambda *a, **kw: (ds, ds)), \
+                mock.patch.object(R.eval_models, "PerceptualLoss", lambda *a, **kw: model_lpips), \
                 mock.patch.object(R, "ssim", ssim), mock.patch.object(R.F, "mse_loss", mse_loss), \
                 mock.patch.object(R.Transforms, "ToPILImage", _ToPILImage), mock.patch.object(R, "st", _St()), \
                 mock.patch.object(R, "putText", lambda f, *a, **kw: f), \
@@ -201,6 +206,8 @@ def gen_case(case, subsample=10):
                 mock.patch.object(R, "get_proc_mem", get_proc_mem), \
                 mock.patch.object(R, "conditioning_fn", conditioning_fn), \
                 mock.patch.object(R, "inverse_data_transform", inverse_data_transform):
+            if extra is not None:
+                extra(R, stack)
             try:
                 sys.setprofile(on_return)
                 returned = runner.video_gen(scorenet=net, ckpt=0, train=False)
@@ -240,6 +247,10 @@ def gen_case(case, subsample=10):
         out[k] = np.array(grabbed[k]) if grabbed[k] else None
         out[k + "_list"] = [(int(v) if isinstance(v, int) else float(v)) for v in grabbed[k]]
     out["metric_arrays"], out["intervals"], out["format_p"] = rec["metric_arrays"], rec["intervals"], (fmt or [None])[0]
+    if not save:
+        for k in ("vid_lpips", "vid_lpips2"):
+            out[k + "_list"] = None if grabbed.get(k) is None else [(int(v) if isinstance(v, int) else float(v)) for v in grabbed[k]]
+        return out
     tag = f"video_metrics_{case}"
     _save(tag, out)
     sys.stdout.write(f"wrote {tag}.pt: batches {[len(out['frames'][p]) for p in (1, 2)]}, cannot {out['cannot']}\n  {out['format_p']}\n")
