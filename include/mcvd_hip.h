@@ -316,7 +316,9 @@ int mcvd_fpndm_run(mcvd_model* m, float* x_inout, const float* cond, int subsamp
  * reference computes: x0 = c_x0a*(x - c_x0b*eps); clip; x = c_mean0*x0 + c_mean1*(ddpm: x | ddim: eps) + c_noise*z. */
 int mcvd_sampler_update(mcvd_ctx* ctx, int kind, float* x_inout, const float* eps, const float* noise, float c_x0a,
                         float c_x0b, float c_mean0, float c_mean1, float c_noise, int clip, int64_t n);
-/* z ~ N(0,1) from the same Philox stream mcvd_sampler_run uses: out:[B, per_sample]. */
+/* z ~ N(0,1) from the same Philox stream mcvd_sampler_run uses: out:[B, per_sample], per_sample a multiple of 4.  Row b is keyed by
+ * (seed, sample_offset + b, draw), its float4 i by counter i.  The high word of the sample index shares a counter word with bits 24.. of
+ * the draw word: (sample + 2^32, draw) and (sample, draw ^ 2^24) are the same stream, so global sample indices must stay below 2^32. */
 int mcvd_randn(mcvd_ctx* ctx, float* out, uint64_t seed, uint64_t sample_offset, uint64_t draw, int B,
                int64_t per_sample);
 /* uint8 frame packing of the result side (runners/ncsn_runner.py:2019-2062: each frame BCHW -> HWC, `(frame * 255).astype('uint8')`):
@@ -382,7 +384,8 @@ int mcvd_lpips_frames(mcvd_lpips* net, const float* pred01, const float* real01,
 int mcvd_dsm_loss(mcvd_model* m, const float* x, const int64_t* labels, const float* cond, const int32_t* cond_mask, const float* z,
                   uint64_t seed, uint64_t sample_offset, int flags, float* loss_rows, float* z_out, float* perturbed_out, int B);
 /* Standardised gamma noise of the `gamma=True` samplers (models/__init__.py:273-276, :319-322): out = (g - kt) / sd, g = raw[i]
- * when raw != NULL (a Gamma(k, rate 1/theta).sample() drawn elsewhere) else theta * Gamma(k) from the library's Philox stream;
+ * when raw != NULL (a Gamma(k, rate 1/theta).sample() drawn elsewhere) else theta * Gamma(k) from the library's Philox stream
+ * (Marsaglia-Tsang evaluated in fp64 at any k, the product rounded to fp32 once; the generator of mcvd_dsm_loss's gamma z as well);
  * kt = k * theta and sd = sqrt(1 - alpha_i) are passed as the fp32 scalars the reference computes.  out:[B, per_sample]. */
 int mcvd_gamma_noise(mcvd_ctx* ctx, float* out, const float* raw, float k, float theta, float kt, float sd, uint64_t seed,
                      uint64_t sample_offset, uint64_t draw, int B, int64_t per_sample);

@@ -268,7 +268,7 @@ int launch_frame_metrics(const float* pred, const float* real, int frames, int C
 int launch_randn(float* out, uint64_t seed, uint64_t sample_offset, uint64_t draw, int B, int64_t per_sample,
                  hipStream_t s);
 // standardised gamma variates (models/__init__.py:273-276, :319-322): out = (g - kt) / sd with g = raw[i] when raw != NULL, else
-// g = theta * Gamma(k) drawn from the Philox stream (Marsaglia-Tsang); kt = k * theta and sd = sqrt(1 - alpha) as fp32 scalars
+// g = fl32(theta * Gamma(k)) drawn from the Philox stream (Marsaglia-Tsang in fp64, philox.h); kt = k * theta and sd = sqrt(1 - alpha) as fp32 scalars
 int launch_gamma_noise(float* out, const float* raw, float k, float theta, float kt, float sd, uint64_t seed,
                        uint64_t sample_offset, uint64_t draw, int B, int64_t per_sample, hipStream_t s);
 // noise_in_cond (ncsnpp_more.py:755-768): out[b] = sqrt(alphas[t_b]) * cond[b] + sqrt(1 - alphas[t_b]) * z[b], t_b = labels[b]

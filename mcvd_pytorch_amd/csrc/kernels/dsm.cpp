@@ -25,28 +25,6 @@ constexpr uint64_t DSM_DRAW = 1ull << 40;      // draw word of the loss's z (phi
 constexpr int DSM_THREADS = 256;
 constexpr int DSM_TARGET_BLOCKS = 2048;        // partial-sum workgroups per call: 8 per CU of the 256
 
-// Gamma(k, scale 1) from philox_gamma's stream and counters (philox.h), with the candidate and its acceptance test in fp64.  The loss draws
-// at every label, where k_cum reaches ~2.5e10: there the fp32 test of philox_gamma evaluates d - d v with ulp(d v) ~ 2e3 against a
-// quantity of order 1, accepts nearly at random and narrows the distribution (pooled variance 2 % low at B = 64, labels 0..999, measured).
-// In fp64 the same cancellation leaves ~1e-5.
-__device__ double philox_gamma64(float k, uint64_t seed, uint64_t sample, uint64_t draw, uint64_t elem) {
-    const double kk = k < 1.0f ? (double)k + 1.0 : (double)k;
-    const double d = kk - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
-    double g = d;
-    for (int j = 0; j < 8; ++j) {
-        const float4 u = philox_uniform4(seed, sample, draw, elem * 8 + (uint64_t)j);
-        const double x = sqrt(-2.0 * log((double)u.x)) * cos(6.283185307179586 * (double)u.y);
-        const double t = 1.0 + c * x;
-        const double v = t * t * t;
-        g = d * fmax(v, 1e-300);
-        if (v > 0.0 && log((double)u.z) < 0.5 * x * x + d - d * v + d * log(v)) {
-            if (k < 1.0f) g *= pow((double)u.w, 1.0 / (double)k);
-            break;
-        }
-    }
-    return g;
-}
-
 __device__ __forceinline__ float sqrt_rn(float a) { return (float)sqrt((double)a); }
 __device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
 

@@ -18,7 +18,7 @@ __global__ __launch_bounds__(256) void gamma_noise_kernel(float* out, const floa
             g = raw[i];
         } else {
             const int64_t row = i / per_sample;
-            g = theta * philox_gamma(k, seed, sample_offset + (uint64_t)row, draw, (uint64_t)(i - row * per_sample));
+            g = (float)((double)theta * philox_gamma64(k, seed, sample_offset + (uint64_t)row, draw, (uint64_t)(i - row * per_sample)));
         }
         out[i] = (g - kt) / sd;                       // (z - ks_cum[i] * thetas[i]) / (1 - alphas[i]).sqrt()
     }
