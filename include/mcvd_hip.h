@@ -31,6 +31,10 @@
  *   mcvd_frame_metrics                    <- the per-frame MSE / SSIM loop of video_gen's test mode, runners/ncsn_runner.py:1580-1609
  *   mcvd_lpips_create / _set_param / _finalize / _frames
  *                                         <- eval_models.PerceptualLoss + the per-frame T2 / model_lpips.forward calls, ncsn_runner.py:1431, :1602-1605
+ *   mcvd_fvd_clips                        <- the torch.cat / [::preds_per_test] / to_i3d of the FVD clips, ncsn_runner.py:1918-1982, and
+ *                                            preprocess_single, models/fvd/fvd.py:160-186 (the detector call between is the caller's)
+ *   mcvd_feature_stats                    <- compute_stats (np.mean / np.cov), models/fvd/fvd.py:275-278, and the
+ *                                            fake_embeddings[traj::preds_per_test] row subsets of ncsn_runner.py:2224
  *   mcvd_dsm_loss                         <- anneal_dsm_score_estimation, losses/dsm.py:7-52 (NCSNRunner.test, ncsn_runner.py:2370-2430)
  */
 #ifndef MCVD_HIP_H
@@ -337,6 +341,29 @@ int mcvd_pack_frames_u8(mcvd_ctx* ctx, const float* frames01, uint8_t* out, int 
 #define MCVD_METRIC_ROUND_BINARY 1
 int mcvd_frame_metrics(mcvd_ctx* ctx, const float* pred01, const float* real01, int B, int T, int C, int H, int W, int flags, float* mse_out,
                        double* ssim_out, uint8_t* grey_out);
+/* FVD, the device steps around the detector (the detector -- the reference's TorchScript I3D -- is called by the caller in between).
+ * mcvd_fvd_clips builds the detector's input in one pass: replaces the torch.cat of the clip's parts, the [::preds_per_test] row selection
+ * and to_i3d (runners/ncsn_runner.py:1918-1982) and preprocess_single (models/fvd/fvd.py:160-186).
+ *   parts[k]: nparts (1 to 3) device tensors [B, part_frames[k]*C, H, W] fp32 in [0, 1], in clip order (cond frames, pred or real, future
+ *   frames); part_batch_stride[k]: floats between two batch rows of part k (a part may be a channel slice of a larger tensor).
+ *   Rows row_start, row_start + row_step, ... < B are taken.  out: [Bsel, 3, T, 224, 224] fp32, T = sum part_frames,
+ *   Bsel = ceil((B - row_start) / row_step); C = 1 writes the grey plane to all three channels.  Values: (bilinear(x) - 0.5) * 2 with
+ *   F.interpolate(mode='bilinear', align_corners=False)'s coordinates (src = fl32(fl32(H / 224) * (d + 0.5) - 0.5), one rounding) and lerp
+ *   order, each operation rounded once; for square frames the centre crop is the identity.  No antialiasing, up- and downscaling alike.
+ *   MCVD_EINVAL for C not in {1, 3}, H != W (to_i3d reshapes to image_size^2), nparts outside 1..3, a part of zero frames, a batch stride
+ *   smaller than the part, a row selection outside B or a NULL pointer.  Deterministic: bit-identical run to run.
+ * mcvd_feature_stats: replaces compute_stats (fvd.py:275-278) on a row subset feats[row_start::row_step] (ncsn_runner.py:2224).
+ *   feats: [N, d] on the device, dtype MCVD_F32 or MCVD_F64, ld elements between rows.  mean_out: [d] fp64 (np.mean(axis=0)); sigma_out:
+ *   [d, d] fp64 (np.cov(rowvar=False): unbiased, two passes -- column means, then the centred product on the fp64 matrix instruction).
+ *   All sums in fp64, rows split over workgroups by a rule of (rows, d) alone, partials added in index order: bit-identical run to run;
+ *   the upper triangle is written as the mirror of the lower: exactly symmetric.
+ *   MCVD_EINVAL for d outside 1..2048, ld < d, fewer than 2 selected rows (np.cov of one row is NaN), an unknown dtype or a NULL pointer. */
+#define MCVD_F32 0
+#define MCVD_F64 1
+int mcvd_fvd_clips(mcvd_ctx* ctx, const float* const* parts, const int* part_frames, const int64_t* part_batch_stride, int nparts, int B, int C,
+                   int H, int W, int row_start, int row_step, float* out);
+int mcvd_feature_stats(mcvd_ctx* ctx, const void* feats, int dtype, int64_t N, int d, int64_t ld, int64_t row_start, int64_t row_step,
+                       double* mean_out, double* sigma_out);
 /* LPIPS v0.1 (AlexNet, "net-lin") of video_gen's test mode: replaces the per-frame `T2(...)` / `model_lpips.forward` calls of
  * runners/ncsn_runner.py:1602-1605 (phase (2): :1771-1774), i.e. eval_models.PerceptualLoss -> DistModel -> networks_basic.PNetLin over
  * pretrained_networks.alexnet, one batch-1 forward pair and two Pillow round trips per frame.

@@ -30,6 +30,7 @@ SAMPLER_DDPM, SAMPLER_DDIM = 0, 1
 FLAG_DENOISE, FLAG_CLIP_BEFORE, FLAG_JUST_BETA, FLAG_GAMMA = 1, 2, 4, 8
 METRIC_ROUND_BINARY = 1
 DSM_L1, DSM_GAMMA = 1, 2
+F32, F64 = 0, 1
 
 _vp, _i, _f, _i64, _u64 = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_uint64
 _PROTOS = {
@@ -89,6 +90,8 @@ _PROTOS = {
     "mcvd_lpips_set_param": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i, _i]),
     "mcvd_lpips_finalize": (_i, [_vp]),
     "mcvd_lpips_frames": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mcvd_fvd_clips": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i64), _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "mcvd_feature_stats": (_i, [_vp, _vp, _i, _i64, _i, _i64, _i64, _i64, _vp, _vp]),
     "mcvd_op_conv2d_strided": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mcvd_gamma_noise": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _u64, _u64, _u64, _i, _i64]),
     "mcvd_dsm_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _i]),

@@ -1102,6 +1102,36 @@ int mcvd_frame_metrics(mcvd_ctx* ctx, const float* pred01, const float* real01, 
     API_CATCH
 }
 
+// FVD: the detector's input and the feature statistics (kernels/fvd.cpp); the detector itself is the caller's
+int mcvd_fvd_clips(mcvd_ctx* ctx, const float* const* parts, const int* part_frames, const int64_t* part_batch_stride, int nparts, int B, int C,
+                   int H, int W, int row_start, int row_step, float* out) {
+    API_TRY
+    MCVD_REQUIRE(ctx && parts && part_frames && part_batch_stride && out, "fvd_clips: NULL argument");
+    MCVD_REQUIRE(C == 1 || C == 3, "fvd_clips: channels must be 1 (grey, repeated to RGB) or 3, got %d", C);
+    MCVD_REQUIRE(H == W && H >= 1, "fvd_clips: %d x %d frames are not square (to_i3d reshapes to image_size x image_size)", H, W);
+    MCVD_REQUIRE(nparts >= 1 && nparts <= 3, "fvd_clips: %d parts (1 to 3: cond, pred or real, future)", nparts);
+    for (int k = 0; k < nparts; ++k) MCVD_REQUIRE(part_frames[k] > 0, "fvd_clips: part %d has %d frames", k, part_frames[k]);
+    MCVD_REQUIRE(B > 0 && row_step >= 1 && row_start >= 0 && row_start < B, "fvd_clips: bad rows: B = %d, start %d, step %d", B, row_start, row_step);
+    const int Bsel = (B - row_start + row_step - 1) / row_step;
+    return launch_fvd_clips(parts, part_frames, part_batch_stride, nparts, Bsel, row_start, row_step, C, H, out, ctx->stream);
+    API_CATCH
+}
+
+int mcvd_feature_stats(mcvd_ctx* ctx, const void* feats, int dtype, int64_t N, int d, int64_t ld, int64_t row_start, int64_t row_step,
+                       double* mean_out, double* sigma_out) {
+    API_TRY
+    MCVD_REQUIRE(ctx && feats && mean_out && sigma_out, "feature_stats: NULL argument");
+    MCVD_REQUIRE(dtype == MCVD_F32 || dtype == MCVD_F64, "feature_stats: dtype %d is neither MCVD_F32 nor MCVD_F64", dtype);
+    MCVD_REQUIRE(d >= 1 && d <= 2048 && ld >= d, "feature_stats: bad d = %d (1 to 2048) or leading dimension %lld", d, (long long)ld);
+    MCVD_REQUIRE(row_step >= 1 && row_start >= 0 && row_start < N, "feature_stats: bad rows: N = %lld, start %lld, step %lld", (long long)N,
+                 (long long)row_start, (long long)row_step);
+    const int64_t n = (N - row_start + row_step - 1) / row_step;
+    MCVD_REQUIRE(n >= 2 && n < (1LL << 24), "feature_stats: %lld selected rows (at least 2: np.cov of one row is NaN; fewer than 2^24)", (long long)n);
+    if (int rc = ctx->ensure_scratch((size_t)feature_stats_scratch_bytes((int)n, d))) return rc;
+    return launch_feature_stats(feats, dtype == MCVD_F64, ld, row_start, row_step, (int)n, d, mean_out, sigma_out, (double*)ctx->scratch, ctx->stream);
+    API_CATCH
+}
+
 // LPIPS v0.1 on AlexNet (kernels/lpips.cpp)
 int mcvd_lpips_create(mcvd_ctx* ctx, mcvd_lpips** out) {
     API_TRY

@@ -22,7 +22,8 @@ WINO_OBJS = ("conv_wino.o", "conv_wino3.o", "conv_wino2h.o", "conv_wino3p.o")
 HOST_ONLY_FLAGS = {"model.cpp": ["-ffp-contract=off"], "api.cpp": ["-ffp-contract=off"],
                    "sampler.cpp": ["-ffp-contract=off"],      # sampler update kernels: one rounding per operation
                    "dsm.cpp": ["-ffp-contract=off"],          # the loss's perturbation: the reference's separate roundings, same Philox bits
-                   "lpips.cpp": ["-ffp-contract=off"]}        # Pillow's resize tables: the same double expressions, one rounding each
+                   "lpips.cpp": ["-ffp-contract=off"],        # Pillow's resize tables: the same double expressions, one rounding each
+                   "fvd.cpp": ["-ffp-contract=off"]}          # torch's bilinear coordinates and lerp: one rounding per operation
 
 
 def sources():

@@ -265,6 +265,14 @@ int launch_pack_frames_u8(const float* in, uint8_t* out, int B, int T, int C, in
 int64_t frame_metrics_scratch_bytes(int frames, int H, int W);
 int launch_frame_metrics(const float* pred, const float* real, int frames, int C, int H, int W, int binary, float* mse_out, double* ssim_out,
                          unsigned char* grey_out, double* part, hipStream_t s);
+// FVD's device steps around the caller's detector, kernels/fvd.cpp.  fvd_clips: up to three parts [B, frames[k]*C, S, S] (batch stride in
+// floats) -> out [Bsel, 3, sum frames, 224, 224]; feature_stats: fp64 mean [d] and unbiased covariance [d, d] of n strided rows;
+// scratch: feature_stats_scratch_bytes of device scratch
+int launch_fvd_clips(const float* const* parts, const int* frames, const int64_t* bstride, int nparts, int Bsel, int row_start, int row_step,
+                     int C, int S, float* out, hipStream_t s);
+int64_t feature_stats_scratch_bytes(int n, int d);
+int launch_feature_stats(const void* x, int is_f64, int64_t ld, int64_t row_start, int64_t row_step, int n, int d, double* mean, double* sigma,
+                         double* scratch, hipStream_t s);
 int launch_randn(float* out, uint64_t seed, uint64_t sample_offset, uint64_t draw, int B, int64_t per_sample,
                  hipStream_t s);
 // standardised gamma variates (models/__init__.py:273-276, :319-322): out = (g - kt) / sd with g = raw[i] when raw != NULL, else

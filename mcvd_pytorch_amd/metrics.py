@@ -1,17 +1,29 @@
-"""The numbers video_gen's test mode reports per phase: MSE, PSNR, SSIM and LPIPS (runners/ncsn_runner.py:1580-1609, :1749-1778,
-:2195-2255), with the per-frame work on the device (mcvd_frame_metrics, kernels/metrics.cpp; mcvd_lpips_frames, kernels/lpips.cpp) and the
-per-video / summary arithmetic on the host in the reference's dtypes and order.
+"""The numbers video_gen's test mode reports per phase: MSE, PSNR, SSIM, LPIPS and FVD (runners/ncsn_runner.py:1580-1609, :1749-1778,
+:1918-1982, :2195-2278), with the per-frame work on the device (mcvd_frame_metrics, kernels/metrics.cpp; mcvd_lpips_frames,
+kernels/lpips.cpp; mcvd_fvd_clips and mcvd_feature_stats, kernels/fvd.cpp) and the per-video / summary arithmetic on the host in the
+reference's dtypes and order.
 
 LPIPS (v0.1, AlexNet, "net-lin") is computed when the caller hands VideoMetrics an LpipsNet that holds the weights: the backbone is
 torchvision's AlexNet `features` state dict and the five lin layers are the reference's models/weights/v0.1/alex.pth, both supplied by the
 caller as a MCVD checkpoint is -- the package ships no weights, downloads none and has no default.  The ScalingLayer's six constants are
-part of the architecture (models/networks_basic.py:93-94) and are set at construction.  FVD is not computed: its I3D network is a
-TorchScript file, not an architecture one can restate.
+part of the architecture (models/networks_basic.py:93-94) and are set at construction.
+
+FVD is computed when the caller hands VideoMetrics the detector as a callable (`fvd=`): the reference's I3D is a TorchScript file
+(models/fvd/fvd.py:30-38), not an architecture one can restate, so the package holds no detector, ships none and downloads none -- the
+caller brings `torch.jit.load(...)` of that file on the GPU, or any callable of the same call shape.  Everything around that one call is
+here: the gates (fvd_gates), the clip assembly and preprocess_single on the device (fvd_clips), the batching in tens, the fp64 feature
+statistics on the device (feature_stats), the Frechet distance (frechet_distance), the per-trajectory values and the three key groups.
 
 Deliberate divergences from the reference:
   * frames of 2 or 4 channels (torchvision's LA / RGBA images) are refused with ValueError: no MCVD dataset has them;
   * :1742-1747: phase (2) tests phase (1)'s `real` / `pred` shapes and, when it cannot compute, appends its zeros to phase (1)'s lists.
-    Here phase (2) tests its own frames and appends to its own lists.
+    Here phase (2) tests its own frames and appends to its own lists;
+  * :2222: the per-trajectory FVDs are taken in the order np.random.choice(arange(ppt), (ppt,), replace=False) draws -- a permutation of
+    all of them, of which mean, std and sem do not depend beyond rounding.  Here they are taken in order 0 .. ppt - 1 and numpy's global
+    RNG is not touched;
+  * frechet_distance takes tr sqrtm(S_g S_r) as the sum of Re sqrt(lambda_i) over the eigenvalues of the product (no scipy): 1e-14 .. 1e-12
+    relative to the reference's scipy route where both covariances have full rank, 1e-9 where they are singular (rows <= d), where
+    scipy's sqrtm is itself only defined to about sqrt(eps).
 """
 import ctypes as C
 import math
@@ -259,6 +271,145 @@ def summarize_lpips(vid_lpips, preds_per_test=1, suffix=""):
     return {f"lpips{suffix}": avg, f"lpips{suffix}_std": std, f"lpips{suffix}_conf95": c95}
 
 
+def fvd_gates(config):
+    """(calc_fvd1, calc_fvd2, calc_fvd3) as video_gen sets them (:1308-1340): which of (1) prediction / interpolation, (2) prediction
+    with the future masked and (3) unconditional generation get an FVD.  All False without `sampling.fvd`."""
+    d, s = config.data, config.sampling
+    if not getattr(s, "fvd", False):
+        return False, False, False
+    condf, futrf = int(d.num_frames_cond), int(getattr(d, "num_frames_future", 0))
+    condp, futrp = float(getattr(d, "prob_mask_cond", 0.0)), float(getattr(d, "prob_mask_future", 0.0))
+    sync = bool(getattr(d, "prob_mask_sync", False))
+    pred10 = condf + int(s.num_frames_pred) >= 10
+    interp10 = condf + int(d.num_frames) + futrf >= 10
+    if condp == 0.0 and futrf == 0:                         # (1) Prediction, :1313
+        return pred10, False, False
+    if condp == 0.0 and futrf > 0 and futrp == 0.0:         # (1) Interpolation, :1316
+        return interp10, False, False
+    if condp == 0.0 and futrf > 0 and futrp > 0.0:          # (1) Interp + (2) Pred, :1319
+        return interp10, pred10, False
+    if condp > 0.0 and futrf == 0:                          # (1) Pred + (3) Gen, :1323
+        return pred10, False, pred10
+    if condp > 0.0 and futrf > 0 and futrp > 0.0 and not sync:      # (1) Interp + (2) Pred + (3) Gen, :1326
+        return interp10, pred10, pred10
+    if condp > 0.0 and futrf > 0 and futrp > 0.0 and sync:          # (1) Interp + (3) Gen, :1329
+        return interp10, False, pred10
+    # condp > 0, futrf > 0, futrp == 0: none of the reference's branches (it fails on an unbound name at :1334)
+    raise ValueError("fvd_gates: prob_mask_cond > 0 with future frames needs prob_mask_future > 0 (the reference has no branch for it)")
+
+
+def _ctx_of(dev, scorenet):
+    if scorenet is not None:
+        scorenet._bind_stream()
+        return scorenet._ctx
+    return _package_ctx(dev)
+
+
+@torch.no_grad()
+def fvd_clips(parts, channels, row_step=1, scorenet=None):
+    """The detector's input, built on the device in one pass: `parts` = up to three [B, T_k*C, S, S] tensors in [0, 1], in clip order
+    (cond frames, pred or real, future frames) -> [ceil(B / row_step), 3, sum T_k, 224, 224] fp32 in [-1, 1].  Replaces the torch.cat,
+    the [::preds_per_test] of the real clips (`row_step`), to_i3d (:1918-1923: grey repeated to RGB, BTCHW -> BCTHW) and
+    preprocess_single (models/fvd/fvd.py:160-186: bilinear resize to 224, centre crop, [0, 1] -> [-1, 1]).  Square frames only.  A part
+    may be a channel slice of a larger tensor (cond_original[:, :nc*C]): it is read in place."""
+    parts = list(parts)
+    if not 1 <= len(parts) <= 3:
+        raise ValueError(f"fvd_clips: {len(parts)} parts (1 to 3: cond, pred or real, future)")
+    dev = scorenet.device if scorenet is not None else (parts[0].device if parts[0].is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    ts = []
+    for t in parts:
+        t = t.to(device=dev, dtype=torch.float32)
+        if t.dim() != 4:
+            raise ValueError(f"fvd_clips: a part of shape {tuple(t.shape)} is not [B, T*C, S, S]")
+        if t.shape[0] and (not t[0].is_contiguous() or (t.shape[0] > 1 and t.stride(0) < t[0].numel())):
+            t = t.contiguous()                                  # rows may lie apart (a channel slice), but each row's frames are dense
+        ts.append(t)
+    B, _, H, W = ts[0].shape
+    for t in ts:
+        if t.shape[0] != B or tuple(t.shape[2:]) != (H, W):
+            raise ValueError(f"fvd_clips: parts {[tuple(x.shape) for x in ts]} differ in rows or frame size")
+        if channels in (1, 3) and t.shape[1] % channels:
+            raise ValueError(f"{t.shape[1]} channels is not a multiple of {channels}")
+    if row_step < 1:
+        raise ValueError(f"fvd_clips: row_step must be at least 1, got {row_step!r}")
+    frames = [t.shape[1] // max(channels, 1) for t in ts]       # the library refuses channels outside {1, 3} and parts of no frames
+    n = len(ts)
+    out = torch.empty((-(-B // row_step), 3, sum(frames), 224, 224), dtype=torch.float32, device=dev)
+    ptrs = (C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    nfr = (C.c_int * n)(*frames)
+    strides = (C.c_int64 * n)(*[t.stride(0) if B > 1 else t[0].numel() for t in ts])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.mcvd_fvd_clips(_ctx_of(dev, scorenet), ptrs, nfr, strides, n, B, channels, H, W, 0, row_step,
+                                           C.c_void_p(out.data_ptr())), "fvd_clips")
+    return out
+
+
+@torch.no_grad()
+def feature_stats(feats, start=0, step=1, scorenet=None):
+    """(mu [d], sigma [d, d]) of feats[start::step] as fp64 device tensors: compute_stats (models/fvd/fvd.py:275-278) --
+    np.mean(axis=0) and np.cov(rowvar=False) -- on the device in fp64 (mcvd_feature_stats).  feats: [N, d] fp32 or fp64, d <= 2048; at
+    least two selected rows (np.cov of one row is NaN; refused)."""
+    dev = scorenet.device if scorenet is not None else (feats.device if feats.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+    x = torch.as_tensor(feats)
+    if x.dtype not in (torch.float32, torch.float64):
+        x = x.to(torch.float64)
+    x = x.to(dev)
+    if x.dim() != 2:
+        raise ValueError(f"feature_stats: features of shape {tuple(x.shape)} are not [N, d]")
+    if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    N, d = x.shape
+    mu = torch.empty((d,), dtype=torch.float64, device=dev)
+    sigma = torch.empty((d, d), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.mcvd_feature_stats(_ctx_of(dev, scorenet), C.c_void_p(x.data_ptr()), _lib.F64 if x.dtype == torch.float64 else _lib.F32,
+                                               N, d, x.stride(0), start, step, C.c_void_p(mu.data_ptr()), C.c_void_p(sigma.data_ptr())),
+                   "feature_stats")
+    return mu, sigma
+
+
+def frechet_from_stats(mu_gen, sigma_gen, mu_real, sigma_real):
+    """The host part of frechet_distance (models/fvd/fvd.py:284-287) from the two (mean, covariance) pairs, in fp64 on the CPU:
+    m + tr(S_g) + tr(S_r) - 2 tr sqrtm(S_g S_r), the last as the sum of Re sqrt(lambda_i) over the eigenvalues of S_g S_r."""
+    mu_g, mu_r = (torch.as_tensor(v).detach().to("cpu", torch.float64) for v in (mu_gen, mu_real))
+    s_g, s_r = (torch.as_tensor(v).detach().to("cpu", torch.float64) for v in (sigma_gen, sigma_real))
+    m = torch.square(mu_g - mu_r).sum()
+    lam = torch.linalg.eigvals(s_g @ s_r)
+    tr_sqrt = torch.sqrt(lam).real.sum()
+    return float(m + torch.trace(s_g) + torch.trace(s_r) - 2.0 * tr_sqrt)
+
+
+def frechet_distance(feats_fake, feats_real, start=0, step=1, scorenet=None):
+    """frechet_distance(feats_fake[start::step], feats_real) of models/fvd/fvd.py:281-287: the statistics on the device
+    (feature_stats), the rest on the host in fp64 (frechet_from_stats).  Usable for any features up to d = 2048."""
+    mu_g, s_g = feature_stats(feats_fake, start, step, scorenet=scorenet)
+    mu_r, s_r = feature_stats(feats_real, scorenet=scorenet)
+    return frechet_from_stats(mu_g, s_g, mu_r, s_r)
+
+
+def fvd_stuff(fake_embeddings, real_embeddings, preds_per_test=1, distance=frechet_distance):
+    """(fvd, fvd_traj_mean, fvd_traj_std, fvd_traj_conf95) of :2217-2229: the distance over all rows, then over each of the
+    `preds_per_test` strided subsets fake[traj::ppt] (in order -- see the module docstring), np.mean / np.std of those and
+    conf95 = mean - norm.interval(0.95, loc=mean, scale=sem)[0]; -1, -1, -1 when preds_per_test == 1."""
+    avg = distance(fake_embeddings, real_embeddings)
+    if preds_per_test <= 1:
+        return avg, -1, -1, -1
+    fvds = [distance(fake_embeddings, real_embeddings, traj, preds_per_test) for traj in range(preds_per_test)]
+    mean, std = float(np.mean(fvds)), float(np.std(fvds))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        scale = np.float64(np.std(fvds, ddof=1) / len(fvds) ** 0.5)
+    lo = _NDTRI_Q1 * scale + mean if (scale > 0 and mean == mean) else math.nan
+    return avg, mean, std, mean - float(lo)
+
+
+def summarize_fvd(fake_embeddings, real_embeddings, preds_per_test=1, suffix="", distance=frechet_distance):
+    """The fvd keys of the reference's summary (:2239, :2262, :2269): fvd, fvd_traj_mean, fvd_traj_std, fvd_traj_conf95 with `suffix`
+    ("2", "3") after "fvd"."""
+    avg, mean, std, c95 = fvd_stuff(fake_embeddings, real_embeddings, preds_per_test, distance)
+    k = f"fvd{suffix}"
+    return {k: avg, f"{k}_traj_mean": mean, f"{k}_traj_std": std, f"{k}_traj_conf95": c95}
+
+
 class VideoMetrics:
     """Accumulates video_gen's metric lists over batches and summarises them as NCSNRunner.video_gen does in test mode.
 
@@ -269,11 +420,18 @@ class VideoMetrics:
     With `lpips=LpipsNet` it also keeps vid_lpips / vid_lpips2 (zeros under "cannot calculate") and the summary gains lpips, lpips_std,
     lpips_conf95 (and lpips2...).  Without it nothing of LPIPS is computed and the key set is the one above.
 
+    With `fvd=detector` (and `sampling.fvd` in the config) it also keeps the FVD embeddings.  The detector is the caller's: it is called
+    as the reference calls its I3D (models/fvd/fvd.py:43-48), `detector(x, rescale=False, resize=False, return_features=True) -> [b, d]`
+    with x the [b, 3, T, 224, 224] fp32 device tensor, on batches of `fvd_batch` clips.  update() then needs `cond01`
+    (inverse_data_transform of the cond frames: cond_original / cond_original2), and update_gen(pred_uncond01) adds phase (3).  The summary
+    gains fvd, fvd_traj_mean, fvd_traj_std, fvd_traj_conf95 and the fvd2... / fvd3... groups where their gates (fvd_gates) are on;
+    embeddings() returns the arrays of the reference's video_embeddings_{ckpt}.npz.  Without `fvd=` nothing changes.
+
     Rows are grouped in consecutive runs of `preds_per_test` (the reference's collate repeat_interleaves each clip).  When `real01` has
     fewer frames than `pred01` the phase appends 0 for every row instead (:1573-1578); after that in phase (1) the reference reports no
     summary at all, and summary() returns None.  The MNIST rule follows config.data.dataset."""
 
-    def __init__(self, config, preds_per_test=1, scorenet=None, lpips=None):
+    def __init__(self, config, preds_per_test=1, scorenet=None, lpips=None, fvd=None, fvd_batch=10):
         self.channels = int(config.data.channels)
         self.binary = str(getattr(config.data, "dataset", "")).upper() in _MNIST
         self.preds_per_test = int(preds_per_test)
@@ -282,8 +440,47 @@ class VideoMetrics:
         self.vid = {1: ([], []), 2: ([], [])}
         self.vid_lpips = {1: [], 2: []}
         self.cannot = {1: False, 2: False}      # the phase appended zeros ("cannot calculate")
+        self.fvd = fvd
+        self.fvd_batch = int(fvd_batch)
+        if fvd is not None:
+            if self.fvd_batch < 1:
+                raise ValueError(f"fvd_batch must be at least 1, got {fvd_batch!r}")
+            self.gates = fvd_gates(config)
+            self.n_cond = int(config.data.num_frames_cond)
+            self.n_future = int(getattr(config.data, "num_frames_future", 0))
+            # :1615-1618: phase (2) runs
+            self.second_calc = (self.n_future > 0 and float(getattr(config.data, "prob_mask_future", 0.0)) > 0.0
+                                and not getattr(config.data, "prob_mask_sync", False))
+            # real / fake embeddings per batch, fp64 on the device: keys 1, 2, 3 = the reference's (real|fake)_embeddings, ...2, ..._uncond
+            self.emb = {k: ([], []) for k in (1, 2, 3)}
+            self._last_real = None              # the real embeddings of the current batch that phase (3) reuses (:1977)
 
-    def update(self, pred01, real01, phase=1):
+    def _detect(self, clips):
+        """get_feats (models/fvd/fvd.py:41-49) on preprocessed clips: batches of fvd_batch, stacked as float64."""
+        out = []
+        for i in range(0, len(clips), self.fvd_batch):
+            f = self.fvd(clips[i:i + self.fvd_batch], rescale=False, resize=False, return_features=True)
+            out.append(torch.as_tensor(f).detach().to(device=clips.device, dtype=torch.float64).reshape(len(clips[i:i + self.fvd_batch]), -1))
+        return torch.cat(out)
+
+    def _update_fvd(self, pred01, real01, cond01, phase):
+        calc1, calc2, calc3 = self.gates
+        # :1925 -- (1) embeds under calc_fvd1, or under calc_fvd3 when there is no phase (2); :1956 -- (2) under calc_fvd2 or calc_fvd3
+        on = (calc1 or (calc3 and not self.second_calc)) if phase == 1 else (calc2 or calc3)
+        if not on:
+            return
+        if cond01 is None:
+            raise ValueError("VideoMetrics.update: a detector is set (fvd=) and this phase's FVD gate is on: cond01 is needed")
+        Cc = self.channels
+        cond = cond01[:, :self.n_cond * Cc]
+        futr = [cond01[:, cond01.shape[1] - self.n_future * Cc:]] if (phase == 1 and self.n_future > 0) else []
+        real = self._detect(fvd_clips([cond, real01] + futr, Cc, row_step=self.preds_per_test, scorenet=self.scorenet))
+        fake = self._detect(fvd_clips([cond, pred01] + futr, Cc, scorenet=self.scorenet))
+        self.emb[phase][0].append(real)
+        self.emb[phase][1].append(fake)
+        self._last_real = real
+
+    def update(self, pred01, real01, phase=1, cond01=None):
         if phase not in (1, 2):
             raise ValueError(f"phase must be 1 or 2, got {phase!r}")
         vid_mse, vid_ssim = self.vid[phase]
@@ -294,6 +491,8 @@ class VideoMetrics:
                 self.vid_lpips[phase].extend([0] * len(pred01))
             self.cannot[phase] = True
             return
+        if self.fvd is not None:                                # the whole of `real`, before it is cut to the predicted frames (:1925-1972)
+            self._update_fvd(pred01, real01, cond01, phase)
         real01 = real01[:, :pred01.shape[1]]                    # frames jj < num_frames_pred only
         mse, ssim = frame_metrics(pred01, real01, self.channels, binary=self.binary, scorenet=self.scorenet)
         m, s = video_values(mse, ssim)
@@ -302,17 +501,57 @@ class VideoMetrics:
         if self.lpips is not None:
             self.vid_lpips[phase].extend(video_lpips(frame_lpips(pred01, real01, self.channels, self.lpips)))
 
+    def update_gen(self, pred_uncond01):
+        """Phase (3), unconditional generation (:1974-1982), after the batch's update() calls: the fake clips are the unconditional
+        prediction alone (no cond frames prepended); the real embeddings of the batch are those phase (2) made if it ran, else phase
+        (1)'s -- reused, not recomputed."""
+        if self.fvd is None:
+            raise ValueError("VideoMetrics.update_gen: no detector (fvd=) was given")
+        if not self.gates[2]:
+            return
+        if self._last_real is None:
+            raise ValueError("VideoMetrics.update_gen before this batch's update(): phase (3) reuses that call's real embeddings")
+        self.emb[3][0].append(self._last_real)
+        self.emb[3][1].append(self._detect(fvd_clips([pred_uncond01], self.channels, scorenet=self.scorenet)))
+
+    def _cat(self, k, which):
+        return torch.cat(self.emb[k][which]) if self.emb[k][which] else None
+
+    def embeddings(self):
+        """The six arrays of the reference's video_embeddings_{ckpt}.npz (:2271-2278) as float64 numpy arrays; a group that was not
+        computed is an empty list, as the reference saves it."""
+        if self.fvd is None:
+            raise ValueError("VideoMetrics.embeddings: no detector (fvd=) was given")
+        out = {}
+        for k, suffix in ((1, ""), (2, "2"), (3, "3")):
+            for which, name in ((0, "real"), (1, "fake")):
+                e = self._cat(k, which)
+                out[f"{name}_embeddings{suffix}"] = [] if e is None else e.cpu().numpy()
+        return out
+
+    def _fvd_keys(self, k, suffix):
+        dist = lambda fake, real, start=0, step=1: frechet_distance(fake, real, start, step, scorenet=self.scorenet)      # noqa: E731
+        return summarize_fvd(self._cat(k, 1), self._cat(k, 0), self.preds_per_test, suffix, dist)
+
     def summary(self):
-        """The reference's vid_metrics without ckpt (and without the lpips keys unless an LpipsNet was given); None where phase (1) could not calculate (video_gen returns None there,
-        :1987-1989, :2192)."""
+        """The reference's vid_metrics without ckpt (without the lpips keys unless an LpipsNet was given, without the fvd keys unless a
+        detector was given and the gates are on), in the reference's key order; None where phase (1) could not calculate (video_gen
+        returns None there, :1987-1989, :2192)."""
         if self.cannot[1]:
             return None
         out = {"preds_per_test": self.preds_per_test}
         out.update(summarize(*self.vid[1], self.preds_per_test))
         if self.lpips is not None:
             out.update(summarize_lpips(self.vid_lpips[1], self.preds_per_test))
+        gates = self.gates if self.fvd is not None else (False, False, False)
+        if gates[0]:
+            out.update(self._fvd_keys(1, ""))
         if self.vid[2][0]:
             out.update(summarize(*self.vid[2], self.preds_per_test, suffix="2"))
             if self.lpips is not None:
                 out.update(summarize_lpips(self.vid_lpips[2], self.preds_per_test, suffix="2"))
+            if gates[1]:
+                out.update(self._fvd_keys(2, "2"))
+        if gates[2]:
+            out.update(self._fvd_keys(3, "3"))
         return out
