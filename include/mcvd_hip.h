@@ -35,6 +35,8 @@
  *                                            preprocess_single, models/fvd/fvd.py:160-186 (the detector call between is the caller's)
  *   mcvd_feature_stats                    <- compute_stats (np.mean / np.cov), models/fvd/fvd.py:275-278, and the
  *                                            fake_embeddings[traj::preds_per_test] row subsets of ncsn_runner.py:2224
+ *   mcvd_knn_radii / mcvd_manifold_hits   <- calculate_precision_recall_full / _part (torch.cdist, kthvalue, <=, any),
+ *                                            evaluation/fid_PR.py:209-259 (NCSNRunner.fast_fid, ncsn_runner.py:2432-2586)
  *   mcvd_dsm_loss                         <- anneal_dsm_score_estimation, losses/dsm.py:7-52 (NCSNRunner.test, ncsn_runner.py:2370-2430)
  */
 #ifndef MCVD_HIP_H
@@ -364,6 +366,29 @@ int mcvd_fvd_clips(mcvd_ctx* ctx, const float* const* parts, const int* part_fra
                    int H, int W, int row_start, int row_step, float* out);
 int mcvd_feature_stats(mcvd_ctx* ctx, const void* feats, int dtype, int64_t N, int d, int64_t ld, int64_t row_start, int64_t row_step,
                        double* mean_out, double* sigma_out);
+/* Improved precision and recall of fast_fid (k-nearest-neighbour manifolds, evaluation/fid_PR.py:209-259), the two device steps.  The
+ * reference builds three pairwise-distance matrices with torch.cdist (r x r, g x g, g x r) and moves every block to the CPU for a kthvalue
+ * and an any; here no Nq x Nr matrix is ever written: workspace is O((Nq + Nr) * splits * 8) in the context's scratch.
+ * mcvd_knn_radii: radii2_out[i] (fp64, [N]) = the (k+1)-th smallest of the squared Euclidean distances from row i to all N rows, row i
+ *   itself included: cdist(X, X).kthvalue(k + 1).values ** 2 (:251).
+ * mcvd_manifold_hits: hit_out[i] (uint8, [Nq]) = 1 iff some ref row j has dist2(query_i, ref_j) <= ref_radii2[j], else 0:
+ *   (dist <= NNk).any(dim=1) (:256, :258) -- the comparison is <=, on squared distances (squaring is monotone on distances).
+ *   feats / query / ref: [N, d] on the device, dtype MCVD_F32 or MCVD_F64 (query and ref may differ), ld elements between rows.
+ *   Arithmetic: fp64 throughout, because the outputs are threshold verdicts.  Row norms |x|^2 by a first small kernel; the Gram tiles on the
+ *   fp64 matrix instruction (v_mfma_f64_16x16x4_f64), the rows whose result is wanted on its column axis so that one lane keeps one row's
+ *   sorted list of its 8 smallest values (or its OR-ed flag) in registers; d2 = max(0, (|a|^2 + |b|^2) - 2 a.b).  Against the direct form
+ *   sum (a - b)^2 that is |delta d2| <= gamma_(d+3) (|a| + |b|)^2, gamma_n = n 2^-53 / (1 - n 2^-53), whatever the accumulation order.
+ *   The swept axis is split over workgroups by a rule of the two row counts alone (64-row tiles; splits = min(tiles, 256,
+ *   ceil(512 / ceil(owners / 64))), re-balanced so that every split has a tile) and a second small launch merges the partial lists or
+ *   flags in split order.  Selection of the smallest values and OR do not depend on order: results are bit-identical run to run AND
+ *   independent of the split, and rows handed over in several calls get the verdicts of one call.
+ *   Duplicate rows are legal; a radius of exactly 0 (k + 1 or more copies of a row) is then decided by the rounding of the Gram form --
+ *   the copies' d2 may come out as 0 or as a few ulps of |a|^2 -- and is not special-cased.
+ *   MCVD_EINVAL, before any launch, for k outside 1..7, N < k + 1 (the reference's kthvalue raises there), d outside 1..2048, ld < d, zero
+ *   rows (2^24 or more are refused too), an unknown dtype or a NULL pointer. */
+int mcvd_knn_radii(mcvd_ctx* ctx, const void* feats, int dtype, int64_t N, int d, int64_t ld, int k, double* radii2_out);
+int mcvd_manifold_hits(mcvd_ctx* ctx, const void* query, int q_dtype, int64_t Nq, int64_t ldq, const void* ref, int r_dtype, int64_t Nr,
+                       int64_t ldr, int d, const double* ref_radii2, uint8_t* hit_out);
 /* LPIPS v0.1 (AlexNet, "net-lin") of video_gen's test mode: replaces the per-frame `T2(...)` / `model_lpips.forward` calls of
  * runners/ncsn_runner.py:1602-1605 (phase (2): :1771-1774), i.e. eval_models.PerceptualLoss -> DistModel -> networks_basic.PNetLin over
  * pretrained_networks.alexnet, one batch-1 forward pair and two Pillow round trips per frame.

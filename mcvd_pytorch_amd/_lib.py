@@ -92,6 +92,8 @@ _PROTOS = {
     "mcvd_lpips_frames": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "mcvd_fvd_clips": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i64), _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mcvd_feature_stats": (_i, [_vp, _vp, _i, _i64, _i, _i64, _i64, _i64, _vp, _vp]),
+    "mcvd_knn_radii": (_i, [_vp, _vp, _i, _i64, _i, _i64, _i, _vp]),
+    "mcvd_manifold_hits": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp]),
     "mcvd_op_conv2d_strided": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mcvd_gamma_noise": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _u64, _u64, _u64, _i, _i64]),
     "mcvd_dsm_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _i]),

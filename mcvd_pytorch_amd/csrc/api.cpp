@@ -1132,6 +1132,36 @@ int mcvd_feature_stats(mcvd_ctx* ctx, const void* feats, int dtype, int64_t N, i
     API_CATCH
 }
 
+// fast_fid's precision and recall: k-nearest-neighbour radii and manifold membership (kernels/prdc.cpp)
+int mcvd_knn_radii(mcvd_ctx* ctx, const void* feats, int dtype, int64_t N, int d, int64_t ld, int k, double* radii2_out) {
+    API_TRY
+    MCVD_REQUIRE(ctx && feats && radii2_out, "knn_radii: NULL argument");
+    MCVD_REQUIRE(dtype == MCVD_F32 || dtype == MCVD_F64, "knn_radii: dtype %d is neither MCVD_F32 nor MCVD_F64", dtype);
+    MCVD_REQUIRE(k >= 1 && k <= 7, "knn_radii: k = %d is outside 1..7", k);
+    MCVD_REQUIRE(d >= 1 && d <= 2048 && ld >= d, "knn_radii: bad d = %d (1 to 2048) or leading dimension %lld", d, (long long)ld);
+    MCVD_REQUIRE(N >= k + 1 && N < (1LL << 24), "knn_radii: %lld rows (at least k + 1 = %d: kthvalue raises below that; fewer than 2^24)",
+                 (long long)N, k + 1);
+    if (int rc = ctx->ensure_scratch((size_t)knn_radii_scratch_bytes((int)N))) return rc;
+    return launch_knn_radii(feats, dtype == MCVD_F64, ld, (int)N, d, k, radii2_out, ctx->scratch, ctx->stream);
+    API_CATCH
+}
+
+int mcvd_manifold_hits(mcvd_ctx* ctx, const void* query, int q_dtype, int64_t Nq, int64_t ldq, const void* ref, int r_dtype, int64_t Nr,
+                       int64_t ldr, int d, const double* ref_radii2, uint8_t* hit_out) {
+    API_TRY
+    MCVD_REQUIRE(ctx && query && ref && ref_radii2 && hit_out, "manifold_hits: NULL argument");
+    MCVD_REQUIRE((q_dtype == MCVD_F32 || q_dtype == MCVD_F64) && (r_dtype == MCVD_F32 || r_dtype == MCVD_F64),
+                 "manifold_hits: dtypes %d, %d: each must be MCVD_F32 or MCVD_F64", q_dtype, r_dtype);
+    MCVD_REQUIRE(d >= 1 && d <= 2048 && ldq >= d && ldr >= d, "manifold_hits: bad d = %d (1 to 2048) or leading dimensions %lld, %lld", d,
+                 (long long)ldq, (long long)ldr);
+    MCVD_REQUIRE(Nq >= 1 && Nq < (1LL << 24) && Nr >= 1 && Nr < (1LL << 24), "manifold_hits: %lld query and %lld ref rows (1 to 2^24 - 1 each)",
+                 (long long)Nq, (long long)Nr);
+    if (int rc = ctx->ensure_scratch((size_t)manifold_hits_scratch_bytes((int)Nq, (int)Nr))) return rc;
+    return launch_manifold_hits(query, q_dtype == MCVD_F64, ldq, (int)Nq, ref, r_dtype == MCVD_F64, ldr, (int)Nr, d, ref_radii2, hit_out,
+                                ctx->scratch, ctx->stream);
+    API_CATCH
+}
+
 // LPIPS v0.1 on AlexNet (kernels/lpips.cpp)
 int mcvd_lpips_create(mcvd_ctx* ctx, mcvd_lpips** out) {
     API_TRY

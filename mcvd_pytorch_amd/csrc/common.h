@@ -273,6 +273,14 @@ int launch_fvd_clips(const float* const* parts, const int* frames, const int64_t
 int64_t feature_stats_scratch_bytes(int n, int d);
 int launch_feature_stats(const void* x, int is_f64, int64_t ld, int64_t row_start, int64_t row_step, int n, int d, double* mean, double* sigma,
                          double* scratch, hipStream_t s);
+// Precision / recall manifolds of fast_fid, kernels/prdc.cpp.  knn_radii: radii2[i] = the (k+1)-th smallest squared distance of row i to
+// the n rows (itself included); manifold_hits: hit[i] = some ref row j has dist2(q_i, r_j) <= ref_radii2[j].  fp64 throughout, the pairwise
+// matrix is never stored; scratch: *_scratch_bytes of device scratch
+int64_t knn_radii_scratch_bytes(int n);
+int64_t manifold_hits_scratch_bytes(int nq, int nr);
+int launch_knn_radii(const void* x, int is_f64, int64_t ld, int n, int d, int k, double* radii2, void* scratch, hipStream_t s);
+int launch_manifold_hits(const void* q, int q_f64, int64_t ldq, int nq, const void* r, int r_f64, int64_t ldr, int nr, int d,
+                         const double* ref_radii2, uint8_t* hit, void* scratch, hipStream_t s);
 int launch_randn(float* out, uint64_t seed, uint64_t sample_offset, uint64_t draw, int B, int64_t per_sample,
                  hipStream_t s);
 // standardised gamma variates (models/__init__.py:273-276, :319-322): out = (g - kt) / sd with g = raw[i] when raw != NULL, else

@@ -14,6 +14,11 @@ caller brings `torch.jit.load(...)` of that file on the GPU, or any callable of 
 here: the gates (fvd_gates), the clip assembly and preprocess_single on the device (fvd_clips), the batching in tens, the fp64 feature
 statistics on the device (feature_stats), the Frechet distance (frechet_distance), the per-trajectory values and the three key groups.
 
+fast_fid's scores (evaluation/fid_PR.py, NCSNRunner.fast_fid) are at the end of the module: FID from the same feature_stats /
+frechet_from_stats, and the improved precision and recall (k-nearest-neighbour manifolds) in fp64 on the device without the pairwise
+distance matrices (mcvd_knn_radii, mcvd_manifold_hits, kernels/prdc.cpp).  The detector (the reference's InceptionV3) is the caller's, as
+with FVD.
+
 Deliberate divergences from the reference:
   * frames of 2 or 4 channels (torchvision's LA / RGBA images) are refused with ValueError: no MCVD dataset has them;
   * :1742-1747: phase (2) tests phase (1)'s `real` / `pred` shapes and, when it cannot compute, appends its zeros to phase (1)'s lists.
@@ -555,3 +560,152 @@ class VideoMetrics:
         if gates[2]:
             out.update(self._fvd_keys(3, "3"))
         return out
+
+
+# ---- fast_fid: FID, precision and recall (evaluation/fid_PR.py) --------------------------------------------------------------------------
+
+def _feature_rows(x, dev, what):
+    """[N, d] fp32 / fp64 rows on `dev` with unit column stride (a column slice of a wider matrix is read in place)."""
+    x = torch.as_tensor(x)
+    if x.dtype not in (torch.float32, torch.float64):
+        x = x.to(torch.float64)
+    if x.dim() != 2:
+        raise ValueError(f"{what}: features of shape {tuple(x.shape)} are not [N, d]")
+    x = x.detach().to(dev)
+    if x.stride(1) != 1 or x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    return x
+
+
+def _feature_device(scorenet, *tensors):
+    if scorenet is not None:
+        return scorenet.device
+    for t in tensors:
+        if torch.is_tensor(t) and t.is_cuda:
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _dtype_code(x):
+    return _lib.F64 if x.dtype == torch.float64 else _lib.F32
+
+
+@torch.no_grad()
+def knn_radii(feats, k=3, scorenet=None):
+    """Squared k-nearest-neighbour radii, an fp64 [N] device tensor: radii2[i] = the (k+1)-th smallest squared distance from row i to all
+    rows, itself included -- cdist(X, X).kthvalue(k + 1).values ** 2 of calculate_precision_recall_full (evaluation/fid_PR.py:251) -- in
+    fp64 on the device without the N x N matrix (mcvd_knn_radii).  feats: [N, d] fp32 or fp64, d <= 2048, 1 <= k <= 7, N >= k + 1."""
+    dev = _feature_device(scorenet, feats)
+    x = _feature_rows(feats, dev, "knn_radii")
+    N, d = x.shape
+    out = torch.empty((N,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.mcvd_knn_radii(_ctx_of(dev, scorenet), C.c_void_p(x.data_ptr()), _dtype_code(x), N, d, x.stride(0), int(k),
+                                           C.c_void_p(out.data_ptr())), "knn_radii")
+    return out
+
+
+@torch.no_grad()
+def manifold_hits(query, ref, ref_radii2, scorenet=None):
+    """bool [Nq] on the device: query row i lies within the radius of some ref row, dist2(query_i, ref_j) <= ref_radii2[j] --
+    (dist <= NNk).any(dim=1) of fid_PR.py:256 / :258 on squared distances, in fp64, without the Nq x Nr matrix (mcvd_manifold_hits).
+    The verdict of a row does not depend on the other query rows: queries handed over in several calls get the same verdicts."""
+    dev = _feature_device(scorenet, query, ref)
+    q, r = _feature_rows(query, dev, "manifold_hits"), _feature_rows(ref, dev, "manifold_hits")
+    if q.shape[1] != r.shape[1]:
+        raise ValueError(f"manifold_hits: query rows have {q.shape[1]} features, ref rows {r.shape[1]}")
+    rad = torch.as_tensor(ref_radii2).detach().to(device=dev, dtype=torch.float64).contiguous()
+    if rad.shape != (r.shape[0],):
+        raise ValueError(f"manifold_hits: {tuple(rad.shape)} radii for {r.shape[0]} ref rows")
+    out = torch.empty((q.shape[0],), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.mcvd_manifold_hits(_ctx_of(dev, scorenet), C.c_void_p(q.data_ptr()), _dtype_code(q), q.shape[0], q.stride(0),
+                                               C.c_void_p(r.data_ptr()), _dtype_code(r), r.shape[0], r.stride(0), q.shape[1],
+                                               C.c_void_p(rad.data_ptr()), C.c_void_p(out.data_ptr())), "manifold_hits")
+    return out.bool()
+
+
+@torch.no_grad()
+def precision_recall(feat_r, feat_g, k=3, return_rows=False, scorenet=None):
+    """(precision, recall) of calculate_precision_recall (fid_PR.py:262-269) as Python floats: precision = the share of generated rows
+    inside the real manifold (the union of the balls around every real row up to its k-th neighbour), recall = the share of real rows
+    inside the generated manifold; hits.sum() / N.  The reference's `save_cpu_ram` / `batch_size` choose between two ways of holding its
+    distance matrices, which do not exist here.  return_rows=True: (precision, recall, precision rows [Ng] bool, recall rows [Nr] bool)."""
+    dev = _feature_device(scorenet, feat_r, feat_g)
+    r, g = _feature_rows(feat_r, dev, "precision_recall"), _feature_rows(feat_g, dev, "precision_recall")
+    p_rows = manifold_hits(g, r, knn_radii(r, k, scorenet=scorenet), scorenet=scorenet)
+    r_rows = manifold_hits(r, g, knn_radii(g, k, scorenet=scorenet), scorenet=scorenet)
+    precision, recall = int(p_rows.sum()) / len(p_rows), int(r_rows.sum()) / len(r_rows)
+    return (precision, recall, p_rows, r_rows) if return_rows else (precision, recall)
+
+
+def fid_from_features(feat_r, feat_g, scorenet=None):
+    """FID of two feature sets (the FID lines of get_fid_PR, fid_PR.py:295-298): feature_stats of each on the device, frechet_from_stats
+    on the host."""
+    mu_r, s_r = feature_stats(feat_r, scorenet=scorenet)
+    mu_g, s_g = feature_stats(feat_g, scorenet=scorenet)
+    return frechet_from_stats(mu_g, s_g, mu_r, s_r)
+
+
+def fid_from_stats(stats, feats, scorenet=None):
+    """FID of a feature set against stored statistics -- fast_fid's --no_pr branch (get_fid, fid_PR.py:315-321).  stats: (mu, sigma) or
+    the path of an .npz with the keys `mu` and `sigma` (the reference's fid_stats_*.npz)."""
+    if isinstance(stats, str):
+        if not stats.endswith(".npz"):
+            raise ValueError(f"fid_from_stats: {stats!r} is not an .npz path")
+        with np.load(stats) as f:
+            mu, sigma = f["mu"][:], f["sigma"][:]
+    else:
+        mu, sigma = stats
+    mu_g, s_g = feature_stats(feats, scorenet=scorenet)
+    return frechet_from_stats(mu_g, s_g, mu, sigma)
+
+
+@torch.no_grad()
+def get_activations(x, detector=None, batch_size=50):
+    """Features [n, dims] of one fid_pr argument (get_activations / calculate_activations, fid_PR.py:272-279, :110-167):
+
+      * a `.pt` / `.pth` path: torch.load of a feature tensor;
+      * a tensor [n, dims]: features, returned as they are;
+      * a tensor [n, C, H, W] of images in [0, 1]: `detector(batch)` on batches of `batch_size` rows (shrunk to n when larger, :133-136),
+        each batch handed over on the device it is on.  A list or tuple result is indexed [0] (:155); a 4-D result whose H x W is not
+        1 x 1 is averaged with adaptive_avg_pool2d (:159-160); rows are stored as fp32, as the reference's `pred_arr`."""
+    if isinstance(x, str):
+        if not (x.endswith(".pt") or x.endswith(".pth")):
+            raise ValueError(f"fid_pr: {x!r} is not a .pt or .pth path")
+        x = torch.load(x, map_location="cpu", weights_only=True)
+    if not torch.is_tensor(x):
+        raise TypeError(f"fid_pr: a feature tensor, an image tensor or a .pt / .pth path is needed, got {type(x).__name__}")
+    if x.dim() == 2:
+        return x
+    if x.dim() != 4:
+        raise ValueError(f"fid_pr: a tensor of shape {tuple(x.shape)} is neither features [n, dims] nor images [n, C, H, W]")
+    if detector is None:
+        raise ValueError("fid_pr: an image tensor needs a detector (the package holds no Inception: the detector is the caller's)")
+    n = len(x)
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError(f"fid_pr: batch_size must be at least 1, got {batch_size}")
+    batch_size = min(batch_size, n)
+    out = []
+    for i in range(0, n, batch_size):
+        pred = detector(x[i:i + batch_size])
+        if isinstance(pred, (list, tuple)):
+            pred = pred[0]
+        pred = torch.as_tensor(pred).detach()
+        if pred.dim() == 4 and (pred.shape[2] != 1 or pred.shape[3] != 1):
+            pred = torch.nn.functional.adaptive_avg_pool2d(pred, output_size=(1, 1))
+        out.append(pred.reshape(pred.shape[0], -1).float())
+    return torch.cat(out)
+
+
+def fid_pr(real, fake, detector=None, k=3, batch_size=50, save_feats_path=None, scorenet=None):
+    """(fid, precision, recall) of get_fid_PR (fid_PR.py:282-299).  `real` and `fake` are each a feature tensor, a `.pt` / `.pth` path of
+    features or an image tensor (see get_activations; images need `detector`, which is the caller's as with VideoMetrics' `fvd=`).
+    save_feats_path: the generated features are torch.save()d there (on the CPU), as the reference does for its feats_{ckpt}.pt."""
+    feat_r = get_activations(real, detector, batch_size)
+    feat_g = get_activations(fake, detector, batch_size)
+    if save_feats_path is not None:
+        torch.save(feat_g.detach().cpu(), save_feats_path)
+    precision, recall = precision_recall(feat_r, feat_g, k, scorenet=scorenet)
+    return fid_from_features(feat_r, feat_g, scorenet=scorenet), precision, recall

@@ -328,6 +328,158 @@ def test_checkpoints(config, scorenet, batches, log_path, ckpts=None, loss_fn=No
     return out
 
 
+@torch.no_grad()
+def fast_fid(config, scorenet, real, detector=None, cond_batches=None, ckpts=None, ckpt_dir=None, out_dir=None, no_pr=False,
+             init_noise_fn=None, sampler=None, log=None):
+    """The checkpoint sweep of NCSNRunner.fast_fid (runners/ncsn_runner.py:2432-2586): for each checkpoint, `fast_fid.num_samples` frames
+    sampled on the device and scored against `real` with FID and the improved precision and recall ->
+    {"fids": {ckpt: v}, "precisions": {ckpt: v}, "recalls": {ckpt: v}} (the last two empty with `no_pr`).
+
+      * ckpts: default range(fast_fid.begin_ckpt, fast_fid.end_ckpt + 1, getattr(fast_fid, "freq", 5000)); checkpoint_{ckpt}.pt is read from
+        `ckpt_dir` -- with model.ema the EMA shadow states[-1] (register, load_state_dict, ema), else load_state_dict(states[0]) (:2489-2498);
+      * sampling (:2502-2551): num_iters = num_samples // batch_size sampler calls of fast_fid.batch_size rows.  z: torch.randn on the device
+        (`init_noise_fn(i, shape, device)` replaces it); cond: the next batch of `cond_batches` -- any iterable of (x, y) with x
+        [B, T, C, H, W] in [0, 1], started over when it runs out (:2524-2530) -- through data_transform and conditioning_fn, cut to
+        batch_size rows; `sampler` (default get_sampler(config)) with final_only=True and sampling.denoise / subsample / clip_before and
+        model.gamma; inverse_data_transform; at the end everything reshaped to (-1, C, S, S).  The samples stay on the device;
+      * scoring: metrics.fid_pr(real, samples, detector, k=fast_fid.pr_nn_k) -- `real` is the dataset's features (a tensor or a .pt / .pth
+        path) or images --, or with `no_pr` metrics.fid_from_stats(real, features of the samples) with `real` = (mu, sigma) or an .npz path.
+        The detector is the caller's (see metrics.fid_pr); the dataset feature files and the stats download of get_feats_path /
+        get_stats_path stay with the caller;
+      * files, only with `out_dir`: samples_{ckpt}.pt (CPU tensor) and, without `no_pr`, feats_{ckpt}.pt are written, and reused when present,
+        features first, then samples (:2477-2484) -- a checkpoint whose features are there is neither loaded nor sampled.  The image grid,
+        the pickles and the YAML files are not written (DESIGN.md section 8);
+      * `log` (default logging.info) receives the reference's "ckpt: ..., fid: ..." line per checkpoint.
+
+    Three defects of the reference are documented and not reproduced: `cond_mask` is unbound for an unconditional config (:2536) -- None is
+    passed; the model.gamma branch reads an undefined `real` (:2516) -- z is drawn as video_gen draws it for gamma, the centred variate
+    Gamma(k_cum[0], rate 1 / theta_t[0]) - k_cum[0] theta_t[0] on the CPU generator; a cond batch shorter than fast_fid.batch_size
+    mis-shapes the sampler call -- ValueError.  With `no_pr` and cached features the reference hands get_fid a .pt path, which it refuses
+    (:197); here the cached features are scored.
+    `fast_fid.ensemble` and model.version SMLD raise NotImplementedError (the NCSN nets of fast_ensemble_fid are not constructible here)."""
+    import logging
+    import os
+    from . import metrics
+    log = log or logging.info
+    ff, d, s, m = config.fast_fid, config.data, config.sampling, config.model
+    if getattr(ff, "ensemble", False):
+        raise NotImplementedError("fast_fid.ensemble (fast_ensemble_fid, :2588) builds NCSN nets, which are not on the HIP path (DESIGN.md section 8)")
+    if str(getattr(m, "version", "DDPM")).upper() == "SMLD":
+        raise NotImplementedError("fast_fid with model.version SMLD is not on the HIP path (DESIGN.md section 8)")
+    batch = int(ff.batch_size)
+    if batch < 1:
+        raise ValueError(f"fast_fid.batch_size must be at least 1, got {batch}")
+    num_iters = int(ff.num_samples) // batch
+    if num_iters < 1:
+        raise ValueError(f"fast_fid.num_samples = {ff.num_samples} is smaller than fast_fid.batch_size = {batch}: nothing would be sampled")
+    if ckpts is None:
+        ckpts = range(ff.begin_ckpt, ff.end_ckpt + 1, getattr(ff, "freq", 5000))
+    ckpts = list(ckpts)
+    conditional = d.num_frames_cond > 0
+    if no_pr:
+        if not (isinstance(real, str) and real.endswith(".npz")) and not (isinstance(real, (tuple, list)) and len(real) == 2):
+            raise ValueError("fast_fid(no_pr=True): `real` must be (mu, sigma) or the path of an .npz with the keys mu and sigma")
+    elif isinstance(real, str):
+        if not (real.endswith(".pt") or real.endswith(".pth")):
+            raise ValueError(f"fast_fid: {real!r} is not a .pt or .pth path of features")
+    elif not torch.is_tensor(real) or real.dim() not in (2, 4):
+        raise ValueError("fast_fid: `real` must be features [n, dims], images [n, C, H, W] or a .pt / .pth path of features")
+    elif real.dim() == 4 and detector is None:
+        raise ValueError("fast_fid: `real` holds images: a detector is needed")
+
+    def cached(kind, ckpt):
+        path = None if out_dir is None else os.path.join(out_dir, f"{kind}_{ckpt}.pt")
+        return path, path is not None and os.path.exists(path)
+    for ckpt in ckpts:                                        # every argument error before any device work
+        if cached("feats", ckpt)[1]:
+            continue
+        if detector is None:
+            raise ValueError(f"fast_fid: ckpt {ckpt} has no cached features: a detector is needed to score its samples")
+        if cached("samples", ckpt)[1]:
+            continue
+        if ckpt_dir is None:
+            raise ValueError(f"fast_fid: ckpt {ckpt} has to be sampled: ckpt_dir is needed")
+        if conditional and cond_batches is None:
+            raise ValueError("fast_fid: data.num_frames_cond > 0: cond_batches is needed")
+
+    net = scorenet.module if hasattr(scorenet, "module") else scorenet
+    dev = net.device
+    C, nf, S = d.channels, d.num_frames, d.image_size
+    shape = (batch, C * nf, S, S)
+    gamma = bool(getattr(m, "gamma", False))
+    cond_iter = [None]
+
+    def next_cond():
+        for attempt in range(2):                              # :2524-2530: a loader that has run out is started over
+            if cond_iter[0] is None:
+                cond_iter[0] = iter(cond_batches)
+            try:
+                return next(cond_iter[0])[0]
+            except StopIteration:
+                cond_iter[0] = None
+        raise ValueError("fast_fid: cond_batches is empty")
+
+    def draw_z(i):
+        if init_noise_fn is not None:
+            return init_noise_fn(i, shape, dev)
+        if gamma:                                             # as video_gen (:1470-1474); the reference's own line reads an undefined `real`
+            k0, th0 = float(net.k_cum[0]), float(net.theta_t[0])
+            g = torch.distributions.gamma.Gamma(torch.full(shape, k0), torch.full(shape, 1.0 / th0)).sample().to(dev)
+            return g - k0 * th0
+        return torch.randn(shape, device=dev)
+
+    score_net = None if getattr(net, "plan_only", False) else net       # the scores run on the net's context and stream
+    out = {"fids": {}, "precisions": {}, "recalls": {}}
+    for ckpt in ckpts:
+        feats_path, have_feats = cached("feats", ckpt)
+        samples_path, have_samples = cached("samples", ckpt)
+        save_feats_path = None
+        if have_feats:                                        # :2477-2479
+            gen = feats_path
+        elif have_samples:                                    # :2482-2484
+            gen = torch.load(samples_path, map_location="cpu", weights_only=True).to(dev)
+            save_feats_path = feats_path
+        else:
+            states = torch.load(os.path.join(ckpt_dir, f"checkpoint_{ckpt}.pt"), map_location="cpu", weights_only=False)
+            if getattr(m, "ema", False):
+                _apply_ema_shadow(net, states[-1])
+            else:
+                net.load_state_dict(states[0])
+            net.eval()
+            run = sampler or get_sampler(config)
+            parts = []
+            for i in range(num_iters):
+                z = draw_z(i)
+                cond = None
+                if conditional:
+                    x = data_transform(config, next_cond().to(dev))
+                    _, cond, _ = conditioning_fn(config, x, conditional=True)
+                    if len(cond) < batch:
+                        raise ValueError(f"fast_fid: a cond batch of {len(cond)} rows is shorter than fast_fid.batch_size = {batch}")
+                    cond = cond[:batch]                       # :2534
+                all_samples = run(z, scorenet, cond=cond, cond_mask=None, final_only=True, denoise=getattr(s, "denoise", True),
+                                  subsample_steps=getattr(s, "subsample", None), clip_before=getattr(s, "clip_before", True),
+                                  verbose=getattr(ff, "verbose", False), gamma=gamma)
+                final = all_samples[-1].reshape(all_samples[-1].shape[0], C * nf, S, S)       # :2545-2546
+                parts.append(inverse_data_transform(config, final))
+            gen = torch.cat(parts, dim=0).reshape(-1, C, S, S)                                 # :2551
+            if samples_path is not None:
+                torch.save(gen.detach().cpu(), samples_path)
+            save_feats_path = feats_path
+        if no_pr:                                             # :2562-2567
+            feats = metrics.get_activations(gen, detector, 50)
+            fid = metrics.fid_from_stats(real, feats, scorenet=score_net)
+            out["fids"][ckpt] = fid
+            log("ckpt: {}, fid: {}".format(ckpt, fid))
+        else:                                                 # :2572-2579
+            k = ff.pr_nn_k
+            fid, precision, recall = metrics.fid_pr(real, gen, detector, k=k, save_feats_path=save_feats_path,
+                                                    scorenet=score_net)
+            out["fids"][ckpt], out["precisions"][ckpt], out["recalls"][ckpt] = fid, precision, recall
+            log("ckpt: {}, fid: {}, precision: {}, recall: {}".format(ckpt, fid, precision, recall))
+    return out
+
+
 def frames_to_uint8(scorenet, frames01, channels):
     """[B, T*C, H, W] frames in [0, 1] (after `inverse_data_transform`) -> uint8 [B, T, H, W, C] on the device: the packing the
     reference applies to every frame before it writes GIFs / PNGs (`(frame * 255).astype('uint8')` on the HWC view,
