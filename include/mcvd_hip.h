@@ -37,6 +37,9 @@
  *                                            fake_embeddings[traj::preds_per_test] row subsets of ncsn_runner.py:2224
  *   mcvd_knn_radii / mcvd_manifold_hits   <- calculate_precision_recall_full / _part (torch.cdist, kthvalue, <=, any),
  *                                            evaluation/fid_PR.py:209-259 (NCSNRunner.fast_fid, ncsn_runner.py:2432-2586)
+ *   mcvd_knn_search / mcvd_hflip_u8 / mcvd_nn_collect
+ *                                         <- get_nearest_neighbors (torch.cdist x 2, torch.min, topk; the ToPILImage / flip / ToTensor
+ *                                            round trip; the data set kept on the host), evaluation/nearest_neighbor.py:70-114
  *   mcvd_dsm_loss                         <- anneal_dsm_score_estimation, losses/dsm.py:7-52 (NCSNRunner.test, ncsn_runner.py:2370-2430)
  */
 #ifndef MCVD_HIP_H
@@ -389,6 +392,48 @@ int mcvd_feature_stats(mcvd_ctx* ctx, const void* feats, int dtype, int64_t N, i
 int mcvd_knn_radii(mcvd_ctx* ctx, const void* feats, int dtype, int64_t N, int d, int64_t ld, int k, double* radii2_out);
 int mcvd_manifold_hits(mcvd_ctx* ctx, const void* query, int q_dtype, int64_t Nq, int64_t ldq, const void* ref, int r_dtype, int64_t Nr,
                        int64_t ldr, int d, const double* ref_radii2, uint8_t* hit_out);
+/* Nearest neighbours of samples in a data set (get_nearest_neighbors, evaluation/nearest_neighbor.py:70-114): "are the generated frames
+ * copies of training frames?".  The reference keeps every data image and feature row on the host, forms two n x N fp32 distance matrices
+ * with torch.cdist, takes their torch.min and a topk; here the data set is handed over in pieces that may be freed after each call.
+ * mcvd_knn_search: the k nearest ref rows of every query row -- replaces torch.cdist x 2, torch.min and topk(-d, k) of :102-109.
+ *   query [Nq, d], query2 NULL or a second view [Nq, d] of the same queries (the mirrored samples), ref [Nr, d]: on the device, each
+ *   MCVD_F32 or MCVD_F64 with its own leading dimension (elements between rows); q2_dtype and ldq2 are not read when query2 is NULL.
+ *   The distance of pair (i, j) is min(d2(query_i, ref_j), d2(query2_i, ref_j)) on SQUARED distances (squaring is monotone: the
+ *   reference's torch.min of the two distances).  dist2_io [Nq, k] fp64 and index_io [Nq, k] int64 (index_base + j): every row ascending
+ *   by (d2, index) -- equal d2: the lower index first, a rule of this library (topk leaves ties unspecified).  With fewer than k
+ *   candidates the tail slots hold +inf and -1.
+ *   merge = 0: the outputs are written from this call alone.  merge = 1: they hold the lists of earlier calls (slots with index -1 are
+ *   empty) and receive the k smallest of the union.  A data set handed over in any number of pieces of any sizes gives the indices AND the
+ *   bit pattern of the distances of one call over the whole set: the d2 of a pair depends on its two rows alone -- row norms from a
+ *   first small kernel, one fixed accumulation order over d -- never on the tile, split or call it falls in, and selection under a
+ *   total order does not depend on order.  So results are also bit-identical run to run and independent of the split.
+ *   Arithmetic as mcvd_knn_radii: fp64 throughout, d2 = max(0, (|a|^2 + |b|^2) - 2 a.b) on v_mfma_f64_16x16x4_f64, within
+ *   gamma_(d+3) (|a| + |b|)^2 of the direct form; the queries sit on the instruction's column axis, so a lane owns one query for the
+ *   whole sweep and keeps 16 (d2, row) pairs in registers; both views are multiplied against the same staged ref chunk; the four lanes of
+ *   a query merge with wave shuffles; the ref axis is split by mcvd_knn_radii's rule and a second small launch merges the split lists (and
+ *   the caller's).  Workspace: O((2 Nq + Nr) * 8 + Nq * splits * 192) bytes in the context's scratch.  Only ordinary vector stores.
+ *   Features that are not finite are the caller's error: a NaN d2 compares false and is never selected (a view whose d2 is NaN is
+ *   passed over when the other view's is not).
+ *   MCVD_EINVAL, before any launch, for k outside 1..16, d outside 1..2048, a leading dimension smaller than d, zero rows or 2^24 or more
+ *   rows in one call (query or ref), an unknown dtype or a NULL required pointer.
+ * mcvd_hflip_u8: the mirrored view, to_tensor(flipper(to_pil(img))) of :81-83, :95 -- the image goes through 8 bits: x.mul(255).byte()
+ *   (the fp32 product truncated toward zero, mcvd_pack_frames_u8's rule), mirrored along W, / 255 in fp32.  images01 [n, C, H, W] fp32 in
+ *   [0, 1] -> out [n, C, H, W] fp32, any C.  Only the mirrored copy is quantised; the reference hands the unmirrored samples to its
+ *   detector as they are, and so does a caller of this entry.  DEVIATION: values outside [0, 1] are clamped to 0 / 255 (the reference's
+ *   .byte() of such a value is not defined).  MCVD_EINVAL for an empty shape, a NULL pointer or out == images01.
+ * mcvd_nn_collect: the neighbours' images without the data set -- replaces data.append(x.cpu()), torch.cat and data[ind] of :85-92,
+ *   :110-111.  After a mcvd_knn_search call over a piece: held [Nq, k, C, H, W] fp32 with held_index [Nq, k] (the lists BEFORE the call;
+ *   both NULL: nothing is held yet), new_index [Nq, k] (the lists after it), piece [n, C, H, W] fp32 whose first row is index_base.
+ *   out [Nq, k, C, H, W] in the new slot order: a slot whose index lies in the piece is copied from the piece, otherwise from the held slot
+ *   of the same query with that index; index -1 (or an index found in neither) gives zeros.  The k held indices are searched on the
+ *   device: no host synchronisation.  MCVD_EINVAL if out overlaps held or the piece, for k outside 1..16, an empty shape, 2^24 or more
+ *   queries or piece rows, held without held_index (or the reverse) or a NULL required pointer. */
+int mcvd_knn_search(mcvd_ctx* ctx, const void* query, int q_dtype, int64_t ldq, const void* query2, int q2_dtype, int64_t ldq2, int64_t Nq,
+                    const void* ref, int r_dtype, int64_t ldr, int64_t Nr, int d, int k, int64_t index_base, int merge, double* dist2_io,
+                    int64_t* index_io);
+int mcvd_hflip_u8(mcvd_ctx* ctx, const float* images01, float* out, int64_t n, int C, int H, int W);
+int mcvd_nn_collect(mcvd_ctx* ctx, const float* held, const int64_t* held_index, const int64_t* new_index, const float* piece, int64_t n,
+                    int64_t index_base, int64_t Nq, int k, int C, int H, int W, float* out);
 /* LPIPS v0.1 (AlexNet, "net-lin") of video_gen's test mode: replaces the per-frame `T2(...)` / `model_lpips.forward` calls of
  * runners/ncsn_runner.py:1602-1605 (phase (2): :1771-1774), i.e. eval_models.PerceptualLoss -> DistModel -> networks_basic.PNetLin over
  * pretrained_networks.alexnet, one batch-1 forward pair and two Pillow round trips per frame.

@@ -94,6 +94,9 @@ _PROTOS = {
     "mcvd_feature_stats": (_i, [_vp, _vp, _i, _i64, _i, _i64, _i64, _i64, _vp, _vp]),
     "mcvd_knn_radii": (_i, [_vp, _vp, _i, _i64, _i, _i64, _i, _vp]),
     "mcvd_manifold_hits": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i, _i64, _i64, _i, _vp, _vp]),
+    "mcvd_knn_search": (_i, [_vp, _vp, _i, _i64, _vp, _i, _i64, _i64, _vp, _i, _i64, _i64, _i, _i, _i64, _i, _vp, _vp]),
+    "mcvd_hflip_u8": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i]),
+    "mcvd_nn_collect": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i, _i, _i, _i, _vp]),
     "mcvd_op_conv2d_strided": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mcvd_gamma_noise": (_i, [_vp, _vp, _vp, _f, _f, _f, _f, _u64, _u64, _u64, _i, _i64]),
     "mcvd_dsm_loss": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _i]),

@@ -1162,6 +1162,51 @@ int mcvd_manifold_hits(mcvd_ctx* ctx, const void* query, int q_dtype, int64_t Nq
     API_CATCH
 }
 
+// nearest neighbours of samples in a data set (evaluation/nearest_neighbor.py; kernels/prdc.cpp)
+int mcvd_knn_search(mcvd_ctx* ctx, const void* query, int q_dtype, int64_t ldq, const void* query2, int q2_dtype, int64_t ldq2, int64_t Nq,
+                    const void* ref, int r_dtype, int64_t ldr, int64_t Nr, int d, int k, int64_t index_base, int merge, double* dist2_io,
+                    int64_t* index_io) {
+    API_TRY
+    MCVD_REQUIRE(ctx && query && ref && dist2_io && index_io, "knn_search: NULL argument");
+    MCVD_REQUIRE((q_dtype == MCVD_F32 || q_dtype == MCVD_F64) && (r_dtype == MCVD_F32 || r_dtype == MCVD_F64) &&
+                     (!query2 || q2_dtype == MCVD_F32 || q2_dtype == MCVD_F64),
+                 "knn_search: dtypes %d, %d, %d: each must be MCVD_F32 or MCVD_F64", q_dtype, q2_dtype, r_dtype);
+    MCVD_REQUIRE(k >= 1 && k <= 16, "knn_search: k = %d is outside 1..16", k);
+    MCVD_REQUIRE(d >= 1 && d <= 2048 && ldq >= d && ldr >= d && (!query2 || ldq2 >= d),
+                 "knn_search: bad d = %d (1 to 2048) or leading dimensions %lld, %lld, %lld", d, (long long)ldq, (long long)ldq2, (long long)ldr);
+    MCVD_REQUIRE(Nq >= 1 && Nq < (1LL << 24) && Nr >= 1 && Nr < (1LL << 24), "knn_search: %lld query and %lld ref rows (1 to 2^24 - 1 each in one call)",
+                 (long long)Nq, (long long)Nr);
+    if (int rc = ctx->ensure_scratch((size_t)knn_search_scratch_bytes((int)Nq, (int)Nr))) return rc;
+    return launch_knn_search(query, q_dtype == MCVD_F64, ldq, query2, q2_dtype == MCVD_F64, ldq2, (int)Nq, ref, r_dtype == MCVD_F64, ldr, (int)Nr, d,
+                             k, index_base, merge ? 1 : 0, dist2_io, index_io, ctx->scratch, ctx->stream);
+    API_CATCH
+}
+
+int mcvd_hflip_u8(mcvd_ctx* ctx, const float* images01, float* out, int64_t n, int C, int H, int W) {
+    API_TRY
+    MCVD_REQUIRE(ctx && images01 && out, "hflip_u8: NULL argument");
+    MCVD_REQUIRE(n >= 1 && C >= 1 && H >= 1 && W >= 1 && n * C < (1LL << 40), "hflip_u8: bad shape [%lld, %d, %d, %d]", (long long)n, C, H, W);
+    MCVD_REQUIRE(images01 != out, "hflip_u8: the output aliases the input");
+    return launch_hflip_u8(images01, out, n * C * H, W, ctx->stream);
+    API_CATCH
+}
+
+int mcvd_nn_collect(mcvd_ctx* ctx, const float* held, const int64_t* held_index, const int64_t* new_index, const float* piece, int64_t n,
+                    int64_t index_base, int64_t Nq, int k, int C, int H, int W, float* out) {
+    API_TRY
+    MCVD_REQUIRE(ctx && new_index && piece && out, "nn_collect: NULL argument");
+    MCVD_REQUIRE((held == nullptr) == (held_index == nullptr), "nn_collect: held images and held indices come together (both NULL: nothing is held)");
+    MCVD_REQUIRE(k >= 1 && k <= 16, "nn_collect: k = %d is outside 1..16", k);
+    MCVD_REQUIRE(Nq >= 1 && Nq < (1LL << 24) && n >= 1 && n < (1LL << 24), "nn_collect: %lld queries and %lld piece rows (1 to 2^24 - 1 each)",
+                 (long long)Nq, (long long)n);
+    MCVD_REQUIRE(C >= 1 && H >= 1 && W >= 1, "nn_collect: bad image shape [%d, %d, %d]", C, H, W);
+    const int64_t chw = (int64_t)C * H * W, total = Nq * k * chw;
+    MCVD_REQUIRE(!held || (out + total <= held || held + total <= out), "nn_collect: the output aliases the held buffer");
+    MCVD_REQUIRE(out + total <= piece || piece + n * chw <= out, "nn_collect: the output aliases the piece");
+    return launch_nn_collect(held, held_index, new_index, piece, n, index_base, Nq * k, k, chw, out, ctx->stream);
+    API_CATCH
+}
+
 // LPIPS v0.1 on AlexNet (kernels/lpips.cpp)
 int mcvd_lpips_create(mcvd_ctx* ctx, mcvd_lpips** out) {
     API_TRY

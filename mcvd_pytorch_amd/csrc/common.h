@@ -281,6 +281,17 @@ int64_t manifold_hits_scratch_bytes(int nq, int nr);
 int launch_knn_radii(const void* x, int is_f64, int64_t ld, int n, int d, int k, double* radii2, void* scratch, hipStream_t s);
 int launch_manifold_hits(const void* q, int q_f64, int64_t ldq, int nq, const void* r, int r_f64, int64_t ldr, int nr, int d,
                          const double* ref_radii2, uint8_t* hit, void* scratch, hipStream_t s);
+// Nearest neighbours of samples in a data set (evaluation/nearest_neighbor.py:70-114), kernels/prdc.cpp.  knn_search: the k smallest
+// (d2, row) of every query over the ref rows, d2 the smaller of one or two query views (q2 may be NULL), merged into the caller's lists
+// when `merge`; hflip_u8: the 8-bit mirrored copy of `rows` image rows of W floats; nn_collect: the images of `slots` = Nq * k list slots
+// from the current piece or the held buffer
+int64_t knn_search_scratch_bytes(int nq, int nr);
+int launch_knn_search(const void* q, int q_f64, int64_t ldq, const void* q2, int q2_f64, int64_t ldq2, int nq, const void* r, int r_f64,
+                      int64_t ldr, int nr, int d, int k, int64_t index_base, int merge, double* dist2_io, int64_t* index_io, void* scratch,
+                      hipStream_t s);
+int launch_hflip_u8(const float* in, float* out, int64_t rows, int W, hipStream_t s);
+int launch_nn_collect(const float* held, const int64_t* held_index, const int64_t* new_index, const float* piece, int64_t n, int64_t index_base,
+                      int64_t slots, int k, int64_t chw, float* out, hipStream_t s);
 int launch_randn(float* out, uint64_t seed, uint64_t sample_offset, uint64_t draw, int B, int64_t per_sample,
                  hipStream_t s);
 // standardised gamma variates (models/__init__.py:273-276, :319-322): out = (g - kt) / sd with g = raw[i] when raw != NULL, else

@@ -709,3 +709,142 @@ def fid_pr(real, fake, detector=None, k=3, batch_size=50, save_feats_path=None, 
         torch.save(feat_g.detach().cpu(), save_feats_path)
     precision, recall = precision_recall(feat_r, feat_g, k, scorenet=scorenet)
     return fid_from_features(feat_r, feat_g, scorenet=scorenet), precision, recall
+
+
+# ---- nearest neighbours of samples in a data set (evaluation/nearest_neighbor.py) -----------------------------------------------------------
+
+@torch.no_grad()
+def knn_search(query, ref, k=10, query2=None, index_base=0, state=None, scorenet=None):
+    """(dist2 [Nq, k] fp64, index [Nq, k] int64) on the device: the k ref rows nearest to every query row -- torch.cdist, torch.min and
+    topk(-d, k) of get_nearest_neighbors (nearest_neighbor.py:102-109) in fp64 without the Nq x Nr matrices (mcvd_knn_search).  With
+    `query2`, a second view of the same queries, a pair's distance is the smaller of the two.  Rows are ascending by (squared distance,
+    index), equal distances lower index first; index = index_base + the ref row; with fewer than k candidates the tail holds +inf / -1.
+    state=(dist2, index) of an earlier call continues that search: pieces of a data set in any split give the result of one call, bit
+    for bit.  query / query2 / ref: [N, d] fp32 or fp64, d <= 2048, 1 <= k <= 16."""
+    dev = _feature_device(scorenet, query, ref)
+    q, r = _feature_rows(query, dev, "knn_search"), _feature_rows(ref, dev, "knn_search")
+    q2 = None if query2 is None else _feature_rows(query2, dev, "knn_search")
+    if q.shape[1] != r.shape[1]:
+        raise ValueError(f"knn_search: query rows have {q.shape[1]} features, ref rows {r.shape[1]}")
+    if q2 is not None and q2.shape != q.shape:
+        raise ValueError(f"knn_search: the second view is {tuple(q2.shape)}, the first {tuple(q.shape)}")
+    k = int(k)
+    Nq = q.shape[0]
+    if state is None:
+        dist2 = torch.empty((Nq, max(k, 0)), dtype=torch.float64, device=dev)
+        index = torch.empty((Nq, max(k, 0)), dtype=torch.int64, device=dev)
+    else:
+        dist2, index = (torch.as_tensor(t).detach().to(device=dev, dtype=dt).contiguous().clone()
+                        for t, dt in zip(state, (torch.float64, torch.int64)))
+        if tuple(dist2.shape) != (Nq, k) or tuple(index.shape) != (Nq, k):
+            raise ValueError(f"knn_search: state of shapes {tuple(dist2.shape)}, {tuple(index.shape)} for {Nq} queries and k = {k}")
+    P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.mcvd_knn_search(_ctx_of(dev, scorenet), P(q), _dtype_code(q), q.stride(0), P(q2), _dtype_code(q2) if q2 is not None else 0,
+                                            q2.stride(0) if q2 is not None else 0, Nq, P(r), _dtype_code(r), r.stride(0), r.shape[0], q.shape[1], k,
+                                            int(index_base), 0 if state is None else 1, P(dist2), P(index)), "knn_search")
+    return dist2, index
+
+
+@torch.no_grad()
+def hflip_u8(images01, scorenet=None):
+    """The mirrored view of get_nearest_neighbors, to_tensor(flipper(to_pil(img))) (nearest_neighbor.py:81-83, :95), on the device
+    (mcvd_hflip_u8): x.mul(255).byte(), mirrored along W, / 255.  images01: [n, C, H, W] in [0, 1] -> fp32 [n, C, H, W]."""
+    dev = _feature_device(scorenet, images01)
+    x = torch.as_tensor(images01).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if x.dim() != 4:
+        raise ValueError(f"hflip_u8: images of shape {tuple(x.shape)} are not [n, C, H, W]")
+    out = torch.empty_like(x)
+    n, Cc, H, W = x.shape
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.mcvd_hflip_u8(_ctx_of(dev, scorenet), C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), n, Cc, H, W), "hflip_u8")
+    return out
+
+
+@torch.no_grad()
+def nn_collect(held, held_index, new_index, piece, index_base, scorenet=None):
+    """The images of the list slots after a knn_search over one piece (mcvd_nn_collect): [Nq, k, C, H, W], a slot whose index lies in
+    `piece` ([n, C, H, W], first row = index_base) copied from it, any other from the slot of `held` ([Nq, k, C, H, W], listed by
+    held_index) with the same index, zeros for -1.  held = held_index = None: nothing is held yet."""
+    dev = new_index.device
+    Nq, k = new_index.shape
+    n, Cc, H, W = piece.shape
+    out = torch.empty((Nq, k, Cc, H, W), dtype=torch.float32, device=dev)
+    P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib.mcvd_nn_collect(_ctx_of(dev, scorenet), P(held), P(held_index), P(new_index), P(piece), n, int(index_base), Nq, k, Cc, H, W,
+                                            P(out)), "nn_collect")
+    return out
+
+
+def detector_features(detector, images):
+    """get_activations of nearest_neighbor.py:45-55: `detector(images)[0]` on the whole batch in ONE call (not in batches of 50 as
+    fid_PR.py's), adaptive_avg_pool2d when the maps are not 1 x 1, reshape(n, -1); rows as fp32, as the reference's."""
+    pred = detector(images)
+    if isinstance(pred, (list, tuple)):
+        pred = pred[0]
+    pred = torch.as_tensor(pred).detach()
+    if pred.dim() == 4 and (pred.shape[2] != 1 or pred.shape[3] != 1):
+        pred = torch.nn.functional.adaptive_avg_pool2d(pred, output_size=(1, 1))
+    return pred.reshape(pred.shape[0], -1).float()
+
+
+class NearestNeighbors:
+    """get_nearest_neighbors (evaluation/nearest_neighbor.py:70-114) with the data set handed over in pieces: for each of the first
+    `n_samples` samples the `k` data images nearest in the detector's feature space, the distance being the smaller of the distances
+    from the sample and from its mirrored copy.  Neither the data images, nor their features, nor an n x N matrix are kept: after every
+    update() the state is k distances, k indices and k images per sample, all on the device.
+
+    samples: a tensor [n, C, H, W] in [0, 1] or the path of a .pt that holds one (fast_fid's samples_{ckpt}.pt); `[:n_samples]` is applied
+    as the reference does.  detector: the caller's (the reference's InceptionV3([block]); the package holds none), called on the whole
+    batch.  flip=False searches with the unmirrored view alone.  Ties in distance go to the lower data index (topk leaves them open)."""
+
+    def __init__(self, samples, detector, k=10, n_samples=10, flip=True, scorenet=None):
+        if isinstance(samples, str):
+            if not (samples.endswith(".pt") or samples.endswith(".pth")):
+                raise ValueError(f"NearestNeighbors: {samples!r} is not a .pt or .pth path")
+            samples = torch.load(samples, map_location="cpu", weights_only=True)
+        if not torch.is_tensor(samples) or samples.dim() != 4:
+            raise ValueError("NearestNeighbors: samples must be an image tensor [n, C, H, W] or the .pt path of one, got "
+                             + (str(tuple(samples.shape)) if torch.is_tensor(samples) else type(samples).__name__))
+        if detector is None:
+            raise ValueError("NearestNeighbors: a detector is needed (the package holds no Inception: the detector is the caller's)")
+        k, n_samples = int(k), int(n_samples)
+        if not 1 <= k <= 16:
+            raise ValueError(f"NearestNeighbors: k = {k} is outside 1..16")
+        if n_samples < 1 or len(samples) < 1:
+            raise ValueError(f"NearestNeighbors: no samples (n_samples = {n_samples}, {len(samples)} rows)")
+        self.k, self.detector, self.scorenet = k, detector, scorenet
+        self.device = _feature_device(scorenet, samples)
+        self.samples = samples[:n_samples].detach().to(device=self.device, dtype=torch.float32).contiguous()
+        self.flipped = hflip_u8(self.samples, scorenet=scorenet) if flip else None
+        self.feats = detector_features(detector, self.samples)
+        self.feats2 = detector_features(detector, self.flipped) if flip else None
+        self.seen = 0
+        self.state = None               # (dist2, index)
+        self.held = None                # [n, k, C, H, W]
+
+    @torch.no_grad()
+    def update(self, images, feats=None):
+        """One piece of the data set: images [m, C, H, W] in [0, 1], in data-set order; feats [m, d], or None for detector(images)."""
+        x = torch.as_tensor(images).detach().to(device=self.device, dtype=torch.float32).contiguous()
+        if x.dim() != 4 or tuple(x.shape[1:]) != tuple(self.samples.shape[1:]):
+            raise ValueError(f"NearestNeighbors.update: images of shape {tuple(x.shape)} beside samples of shape {tuple(self.samples.shape)}")
+        f = detector_features(self.detector, x) if feats is None else torch.as_tensor(feats)
+        if f.dim() != 2 or len(f) != len(x):
+            raise ValueError(f"NearestNeighbors.update: features of shape {tuple(f.shape)} for {len(x)} images")
+        if len(x) == 0:
+            return
+        old = self.state
+        self.state = knn_search(self.feats, f, self.k, query2=self.feats2, index_base=self.seen, state=old, scorenet=self.scorenet)
+        self.held = nn_collect(self.held, None if old is None else old[1], self.state[1], x, self.seen, scorenet=self.scorenet)
+        self.seen += len(x)
+
+    def result(self):
+        """indices [n, k] int64, distances [n, k] fp64 (Euclidean, ascending), neighbors [n, k, C, H, W] and plot_data [n (k + 1), C, H, W]
+        -- sample i followed by its k neighbours, what the reference hands to save_image(..., nrow=k + 1)."""
+        if self.seen < self.k:
+            raise RuntimeError(f"NearestNeighbors: k = {self.k} neighbours of {self.seen} data rows (the reference's topk raises there)")
+        dist2, index = self.state
+        plot = torch.cat([self.samples[:, None], self.held], 1).reshape(-1, *self.samples.shape[1:])
+        return {"indices": index, "distances": dist2.sqrt(), "neighbors": self.held, "plot_data": plot}

@@ -480,6 +480,24 @@ def fast_fid(config, scorenet, real, detector=None, cond_batches=None, ckpts=Non
     return out
 
 
+def nearest_neighbors(samples, data_batches, detector, k=10, n_samples=10, out_path=None, scorenet=None):
+    """The loop of get_nearest_neighbors (evaluation/nearest_neighbor.py:70-114): the `k` data images nearest, in the detector's feature
+    space, to each of the first `n_samples` rows of `samples` (a tensor, or the path of fast_fid's samples_{ckpt}.pt) or to its mirrored
+    copy -> metrics.NearestNeighbors.result(): indices, distances, neighbors and plot_data (sample | k neighbours per row of the
+    reference's grid).  data_batches: any iterable of `x` or `(x, _)`, as a DataLoader gives, x [B, C, H, W] in [0, 1]; every batch goes
+    through the detector and the search once and may then be freed -- the data set is never resident.  out_path: plot_data, indices and
+    distances (CPU tensors) as one .pt.  The PNG grid, the data-set table of the script's __main__ and an Inception stay with the caller
+    (DESIGN.md section 8)."""
+    from . import metrics
+    nn = metrics.NearestNeighbors(samples, detector, k=k, n_samples=n_samples, scorenet=scorenet)
+    for batch in data_batches:
+        nn.update(batch[0] if isinstance(batch, (list, tuple)) else batch)
+    out = nn.result()
+    if out_path is not None:
+        torch.save({key: out[key].detach().cpu() for key in ("plot_data", "indices", "distances")}, out_path)
+    return out
+
+
 def frames_to_uint8(scorenet, frames01, channels):
     """[B, T*C, H, W] frames in [0, 1] (after `inverse_data_transform`) -> uint8 [B, T, H, W, C] on the device: the packing the
     reference applies to every frame before it writes GIFs / PNGs (`(frame * 255).astype('uint8')` on the HWC view,
