@@ -15,6 +15,7 @@
 //   2^32 + k             the k-th conditioning-noise draw of a noise_in_cond forward (model.cpp OP_CONDNOISE)
 //   bit 39 set           the gamma stream of any of the above (philox_uniform4)
 //   bit 40 set           the denoising score-matching loss's z (dsm.cpp DSM_DRAW; with bit 39 as well under gamma)
+//   bit 41 set           the block init noise of a seeded evaluate_video_gen (runner.py INIT_NOISE_DRAW = 2^41, drawn through mcvd_randn)
 //
 // Uniforms: u = ((float)(c >> 8) + 0.5f) * 2^-24, in (0, 1]: for c >> 8 >= 2^23 the sum is rounded to fp32 (ties to even), and
 // c >> 8 = 2^24 - 1 gives u = 1.0 exactly (a Box-Muller radius of 0, a log u of 0); the smallest u is 2^-25.

@@ -415,6 +415,16 @@ def summarize_fvd(fake_embeddings, real_embeddings, preds_per_test=1, suffix="",
     return {k: avg, f"{k}_traj_mean": mean, f"{k}_traj_std": std, f"{k}_traj_conf95": c95}
 
 
+class _MergedOnly:
+    """Stands where VideoMetrics.merged has no LpipsNet / detector to put: the merged object summarises, it does not measure."""
+
+    def __call__(self, *a, **kw):
+        raise RuntimeError("a VideoMetrics built by merged() holds no detector: it takes no further update()")
+
+    def __getattr__(self, name):
+        raise RuntimeError("a VideoMetrics built by merged() holds no LpipsNet: it takes no further update()")
+
+
 class VideoMetrics:
     """Accumulates video_gen's metric lists over batches and summarises them as NCSNRunner.video_gen does in test mode.
 
@@ -434,7 +444,11 @@ class VideoMetrics:
 
     Rows are grouped in consecutive runs of `preds_per_test` (the reference's collate repeat_interleaves each clip).  When `real01` has
     fewer frames than `pred01` the phase appends 0 for every row instead (:1573-1578); after that in phase (1) the reference reports no
-    summary at all, and summary() returns None.  The MNIST rule follows config.data.dataset."""
+    summary at all, and summary() returns None.  The MNIST rule follows config.data.dataset.
+
+    A sharded evaluation (runner.evaluate_video_gen, shard=) keeps one VideoMetrics per rank: state() is what a rank hands over and
+    VideoMetrics.merged(config, states) the object of the whole run, its lists in global order.  Neither changes what update(),
+    update_gen(), summary() and embeddings() do without them; an update() of zero rows (an empty shard) adds nothing."""
 
     def __init__(self, config, preds_per_test=1, scorenet=None, lpips=None, fvd=None, fvd_batch=10):
         self.channels = int(config.data.channels)
@@ -445,6 +459,7 @@ class VideoMetrics:
         self.vid = {1: ([], []), 2: ([], [])}
         self.vid_lpips = {1: [], 2: []}
         self.cannot = {1: False, 2: False}      # the phase appended zeros ("cannot calculate")
+        self._calls = []                        # (phase, rows, cannot, embedded) per update / update_gen call: what state() cuts the lists by
         self.fvd = fvd
         self.fvd_batch = int(fvd_batch)
         if fvd is not None:
@@ -495,9 +510,15 @@ class VideoMetrics:
             if self.lpips is not None:
                 self.vid_lpips[phase].extend([0] * len(pred01))
             self.cannot[phase] = True
+            self._calls.append((phase, len(pred01), True, False))
             return
+        if len(pred01) == 0:                                    # an empty shard of a sharded evaluation: nothing to add
+            self._calls.append((phase, 0, False, False))
+            return
+        n_emb = len(self.emb[phase][0]) if self.fvd is not None else 0
         if self.fvd is not None:                                # the whole of `real`, before it is cut to the predicted frames (:1925-1972)
             self._update_fvd(pred01, real01, cond01, phase)
+        self._calls.append((phase, len(pred01), False, self.fvd is not None and len(self.emb[phase][0]) > n_emb))
         real01 = real01[:, :pred01.shape[1]]                    # frames jj < num_frames_pred only
         mse, ssim = frame_metrics(pred01, real01, self.channels, binary=self.binary, scorenet=self.scorenet)
         m, s = video_values(mse, ssim)
@@ -514,10 +535,71 @@ class VideoMetrics:
             raise ValueError("VideoMetrics.update_gen: no detector (fvd=) was given")
         if not self.gates[2]:
             return
+        if len(pred_uncond01) == 0:                             # an empty shard of a sharded evaluation
+            self._calls.append((3, 0, False, False))
+            return
         if self._last_real is None:
             raise ValueError("VideoMetrics.update_gen before this batch's update(): phase (3) reuses that call's real embeddings")
         self.emb[3][0].append(self._last_real)
         self.emb[3][1].append(self._detect(fvd_clips([pred_uncond01], self.channels, scorenet=self.scorenet)))
+        self._calls.append((3, len(pred_uncond01), False, True))
+
+    def state(self):
+        """What a rank of a sharded evaluation hands over (picklable, host-side): per update() / update_gen() call, in call order -- that is
+        per batch and phase --, {"phase", "rows", "cannot", "mse", "ssim", "lpips", "real", "fake"}: the per-video values of the call's rows
+        as the lists hold them (lpips None without an LpipsNet) and the call's real and fake embeddings as fp64 host arrays (None where
+        the call embedded nothing)."""
+        calls, at, at_emb = [], {1: 0, 2: 0}, {1: 0, 2: 0, 3: 0}
+        for phase, rows, cannot, embedded in self._calls:
+            c = {"phase": phase, "rows": rows, "cannot": cannot, "mse": None, "ssim": None, "lpips": None, "real": None, "fake": None}
+            if phase in (1, 2):
+                a = at[phase]
+                c["mse"], c["ssim"] = list(self.vid[phase][0][a:a + rows]), list(self.vid[phase][1][a:a + rows])
+                if self.lpips is not None:
+                    c["lpips"] = list(self.vid_lpips[phase][a:a + rows])
+                at[phase] = a + rows
+            if embedded:
+                j = at_emb[phase]
+                c["real"], c["fake"] = (self.emb[phase][w][j].detach().to("cpu", torch.float64).numpy() for w in (0, 1))
+                at_emb[phase] = j + 1
+            calls.append(c)
+        return {"preds_per_test": self.preds_per_test, "lpips": self.lpips is not None, "fvd": self.fvd is not None, "calls": calls}
+
+    @classmethod
+    def merged(cls, config, states, scorenet=None, device=None):
+        """The VideoMetrics of the whole evaluation from the state() of every rank, in rank order: the lists in global order -- batch-major,
+        the ranks in order inside a batch, which is the row order of dist.shard_rows' contiguous clip shards.  The result serves summary(),
+        embeddings() and state(); it holds no LpipsNet and no detector, so it takes no further update().  The embeddings go to
+        `scorenet`'s device (or `device`, default the current one), where summary() forms the FVD statistics."""
+        states = list(states)
+        if not states:
+            raise ValueError("VideoMetrics.merged: no states")
+        first = states[0]
+        for st in states:
+            if (st["preds_per_test"], st["lpips"], st["fvd"]) != (first["preds_per_test"], first["lpips"], first["fvd"]) \
+                    or [c["phase"] for c in st["calls"]] != [c["phase"] for c in first["calls"]]:
+                raise ValueError("VideoMetrics.merged: the states are not those of one evaluation (settings or call sequences differ)")
+        refuse = _MergedOnly()
+        vm = cls(config, preds_per_test=first["preds_per_test"], scorenet=scorenet, lpips=refuse if first["lpips"] else None,
+                 fvd=refuse if first["fvd"] else None)
+        if first["fvd"]:
+            dev = scorenet.device if scorenet is not None else (device if device is not None else torch.device("cuda", torch.cuda.current_device()))
+        for j, c0 in enumerate(first["calls"]):
+            phase = c0["phase"]
+            for st in states:
+                c = st["calls"][j]
+                if phase in (1, 2):
+                    vm.vid[phase][0].extend(c["mse"])
+                    vm.vid[phase][1].extend(c["ssim"])
+                    if first["lpips"]:
+                        vm.vid_lpips[phase].extend(c["lpips"])
+                    vm.cannot[phase] = vm.cannot[phase] or c["cannot"]
+                embedded = c["real"] is not None
+                if embedded:
+                    vm.emb[phase][0].append(torch.from_numpy(np.asarray(c["real"], dtype=np.float64)).to(dev))
+                    vm.emb[phase][1].append(torch.from_numpy(np.asarray(c["fake"], dtype=np.float64)).to(dev))
+                vm._calls.append((phase, c["rows"], c["cannot"], embedded))
+        return vm
 
     def _cat(self, k, which):
         return torch.cat(self.emb[k][which]) if self.emb[k][which] else None

@@ -269,6 +269,349 @@ def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, 
     return torch.cat(preds, dim=1)[:, :C * nfp]                                         # :1569
 
 
+# seed layout of evaluate_video_gen: (batch, phase) -> seed + ((3 * batch + phase - 1) << _SEED_SHIFT); video_gen adds the block index below it
+_SEED_SHIFT = 20
+# draw word of the block init noise (kernels/philox.h, "Draw words in use"): bit 41, which no other stream sets
+INIT_NOISE_DRAW = 1 << 41
+
+
+def _format_p(dd):
+    """The reference's format_p (:2284).  It formats ckpt as `{v:7d}`, which raises for the "latest" of :1367; a ckpt that is not an int
+    is printed as it is."""
+    parts = []
+    for k, v in dd.items():
+        if k == "ckpt":
+            parts.append(f"{k}:{v:7d}" if isinstance(v, int) else f"{k}:{v}")
+        elif k == "preds_per_test":
+            parts.append(f"{k}:{v:3d}")
+        elif k == "time":
+            parts.append(f"{k}:{v}")
+        else:
+            parts.append(f"{k}:{v:.4f}")
+    return ", ".join(parts)
+
+
+def _video_gen_branch(config):
+    """(name of phase (1), phase (2) aliased, phase (3) aliased) of the six branches that :2169-2190 and :2296-2365 switch on; None for a
+    mask combination none of them matches (prob_mask_cond > 0 with future frames and prob_mask_future == 0)."""
+    d = config.data
+    condp, futrf = float(getattr(d, "prob_mask_cond", 0.0)), int(getattr(d, "num_frames_future", 0))
+    futrp, sync = float(getattr(d, "prob_mask_future", 0.0)), bool(getattr(d, "prob_mask_sync", False))
+    if condp == 0.0 and futrf == 0:                                  # (1) Prediction
+        return "pred", False, False
+    if condp == 0.0 and futrf > 0 and futrp == 0.0:                  # (1) Interpolation
+        return "interp", False, False
+    if condp == 0.0 and futrf > 0 and futrp > 0.0:                   # (1) Interp + (2) Pred
+        return "interp", True, False
+    if condp > 0.0 and futrf == 0:                                   # (1) Pred + (3) Gen
+        return "pred", False, True
+    if condp > 0.0 and futrf > 0 and futrp > 0.0 and not sync:       # (1) Interp + (2) Pred + (3) Gen
+        return "interp", True, True
+    if condp > 0.0 and futrf > 0 and futrp > 0.0 and sync:           # (1) Interp + (3) Gen
+        return "interp", False, True
+    return None
+
+
+def video_gen_aliases(config, vid_metrics):
+    """The pred_ / interp_ / gen_ keys of vid_metrics.yml (:2296-2365), added to `vid_metrics` in the reference's order: phase (1)'s keys
+    under the name of its task, phase (2)'s mse2... as pred_..., phase (3)'s fvd3... as gen_fvd....  A key that is absent (no LPIPS net, an
+    FVD gate off, phase (2) not run) is skipped where the reference would raise KeyError."""
+    branch = _video_gen_branch(config)
+    if branch is None:
+        return vid_metrics
+    first, second, third = branch
+
+    def alias(prefix, suffix):
+        for tail in ("", "_std", "_conf95"):
+            for m in ("mse", "psnr", "ssim", "lpips"):
+                if f"{m}{suffix}{tail}" in vid_metrics:
+                    vid_metrics[f"{prefix}_{m}{tail}"] = vid_metrics[f"{m}{suffix}{tail}"]
+        alias_fvd(prefix, suffix)
+
+    def alias_fvd(prefix, suffix):
+        for tail in ("", "_traj_mean", "_traj_std", "_traj_conf95"):
+            if f"fvd{suffix}{tail}" in vid_metrics:
+                vid_metrics[f"{prefix}_fvd{tail}"] = vid_metrics[f"fvd{suffix}{tail}"]
+    alias(first, "")
+    if second:
+        alias("pred", "2")
+    if third:
+        alias_fvd("gen", "3")
+    return vid_metrics
+
+
+def write_to_yaml(yaml_file, my_dict):
+    """NCSNRunner.write_to_yaml (:2867-2877): merged into the file's dict when it exists and written with sorted keys."""
+    import os
+    import yaml
+    if os.path.exists(yaml_file):
+        with open(yaml_file, "r") as f:
+            old_dict = yaml.load(f, Loader=yaml.FullLoader)
+        for key in my_dict.keys():
+            old_dict[key] = my_dict[key]
+        my_dict = {}
+        for key in sorted(old_dict.keys()):
+            my_dict[key] = old_dict[key]
+    with open(yaml_file, "w") as f:
+        yaml.dump(my_dict, f, default_flow_style=False)
+
+
+def _saved_dicts(config, pred, real, cond_original, pred2, real2, pred_uncond):
+    """The dicts the reference saves for one batch (:1985-1993, :2106-2112, :2131-2135, :2157-2159, branches :2169-2190) as
+    {file stem: {key: CPU tensor}}: videos_pred {cond, pred, real}, videos_interp {cond, pred, real, futr}, videos_gen {gen}.  `real` is
+    padded with zero frames when it is shorter than `pred` (:1988-1990); with future frames `cond` is split into cond and futr (:1992-1993),
+    and phase (2)'s dict keeps phase (1)'s cond frames, as the reference's closure does."""
+    C, nc, future = config.data.channels, config.data.num_frames_cond, getattr(config.data, "num_frames_future", 0)
+    cpu = lambda t: t.detach().to("cpu")                 # noqa: E731
+    cond, futr = cond_original, None
+    if real.shape[1] < pred.shape[1]:
+        real = torch.cat([real, torch.zeros(real.shape[0], pred.shape[1] - real.shape[1], real.shape[2], real.shape[3], device=real.device)], dim=1)
+    if future > 0:
+        cond, futr = torch.tensor_split(cond, (nc * C,), dim=1)
+    branch = _video_gen_branch(config)
+    out = {}
+    if branch is None:
+        return out
+    first, second, third = branch
+    if first == "pred":
+        out["videos_pred"] = {"cond": cpu(cond), "pred": cpu(pred), "real": cpu(real)}
+    else:
+        out["videos_interp"] = {"cond": cpu(cond), "pred": cpu(pred), "real": cpu(real), "futr": cpu(futr)}
+    if second and pred2 is not None:
+        out["videos_pred"] = {"cond": cpu(cond), "pred": cpu(pred2), "real": cpu(real2)}
+    if third and pred_uncond is not None:
+        out["videos_gen"] = {"gen": cpu(pred_uncond)}
+    return out
+
+
+def _finish_video_gen(config, metrics, ckpt, train, out_dir, start_time, log, write):
+    """The part of NCSNRunner.video_gen after its loop (:2192-2368) on a complete `metrics`: summary, embeddings file, log lines, aliases, YAML."""
+    import datetime
+    import os
+    import time
+    import numpy as np
+    from .metrics import fvd_gates
+    summary = metrics.summary()
+    if summary is None:                                               # :2192
+        return None
+    vid_metrics = {"ckpt": ckpt, **summary}
+    if not train and write and out_dir is not None and any(fvd_gates(config)):         # :2271-2278
+        np.savez(os.path.join(out_dir, f"video_embeddings_{ckpt}.npz"), **metrics.embeddings())
+    elapsed = str(datetime.timedelta(seconds=(time.time() - start_time)))[:-3]          # :2283
+    log(f"elapsed: {elapsed}, {_format_p(vid_metrics)}")                               # :2285
+    if train:                                                         # :2288-2289
+        return vid_metrics
+    vid_metrics["time"] = elapsed                                     # :2294
+    video_gen_aliases(config, vid_metrics)                            # :2296-2365
+    log(f"elapsed: {elapsed}, {_format_p(vid_metrics)}")                               # :2367
+    if write and out_dir is not None:                                 # :2368
+        write_to_yaml(os.path.join(out_dir, "vid_metrics.yml"), vid_metrics)
+    return vid_metrics
+
+
+@torch.no_grad()
+def evaluate_video_gen(config, scorenet, batches, *, ckpt="latest", train=False, max_data_iter=None, preds_per_test=None,
+                       lpips=None, fvd=None, fvd_batch=10, data_init_batches=None, out_dir=None, sampler=None,
+                       init_noise_fn=None, seed=None, shard=None, metrics=None, log=None):
+    """NCSNRunner.video_gen (runners/ncsn_runner.py:1304-2368), the mode `main.py --video_gen` runs, as one call: every batch of `batches`
+    through the phases of `video_tasks(config)`, the frames of each phase into a `VideoMetrics`, and the reference's vid_metrics dict back.
+    Frames stay on the device from the sampler to the metrics (the reference's per-block `.to('cpu')`, :1523, is not reproduced).
+
+      * returns {} when neither sampling.ssim nor sampling.fvd is set (:1340-1343); asserts data.num_frames_cond > 0 (:1356);
+      * train=True (the call of the training loop, :497): one batch and preds_per_test = 1 (:1345-1348); else sampling.max_data_iter and
+        sampling.preds_per_test (:1351-1352) unless `max_data_iter=` / `preds_per_test=` say otherwise;
+      * batches: any iterable of clip batches `x` or `(x, _)`, x [b, T, C, S, S] in [0, 1] as a dataset yields them before data_transform:
+        the caller's loader, with batch_size = sampling.batch_size // preds_per_test as :1413 sizes it.  Each batch is moved to the device
+        once, repeat_interleave(preds_per_test, dim=0) (:1392-1395) and data_transform (:1442); the loop stops at max_data_iter (:1437-1440);
+      * phase (1) (:1444-1609): task_conditioning "pred" (num_frames_future == 0) or "interp", video_gen(task=...), inverse_data_transform,
+        metrics.update(pred01, real01, phase=1, cond01=cond_original);
+        phase (2) under future > 0 and prob_mask_future > 0 and not prob_mask_sync (:1615-1616): "pred_future_masked",
+        metrics.update(..., phase=2, cond01=cond_original2);
+        phase (3) only under calc_fvd3 of metrics.fvd_gates (:1787): "gen" with num_frames_cond + sampling.num_frames_pred frames (:1793),
+        metrics.update_gen(pred_uncond01);
+      * the sampler calls get verbose = log = not train, as :1516 and :1519 pass them;
+      * sampling.data_init (:1479-1489, :1646-1656, :1818-1828): every phase that runs takes the next batch of `data_init_batches` (an
+        iterable of `x` or `(x, _)`, sampling.batch_size clips as :1418 sizes it) and starts it over when it runs out, so it must be
+        re-iterable.  With model.gamma the reference fails on an undefined name (:1496); refused as in video_gen;
+      * metrics: a ready VideoMetrics or a stand-in with update, update_gen, summary and embeddings (and state / merged under
+        torch.distributed).  Default: VideoMetrics(config, preds_per_test, scorenet, lpips=lpips, fvd=fvd, fvd_batch=fvd_batch).
+        sampling.fvd without `fvd=` (and without `metrics=`) is a ValueError: the package loads no detector;
+      * after the loop (:2192-2368): None where phase (1) could not calculate (:2192), else {'ckpt': ckpt, **metrics.summary()}; unless
+        `train` also 'time' and the pred_ / interp_ / gen_ aliases of :2296-2365 (`video_gen_aliases`; absent keys are skipped).  `log`
+        (default logging.info) receives the reference's "elapsed: ..., {format_p}" lines (:2285, :2367);
+      * out_dir: videos_pred_{ckpt}.pt / videos_interp_{ckpt}.pt / videos_gen_{ckpt}.pt (:2106-2112, :2131-2135, :2157-2159) for the batches
+        `i == 0 or preds_per_test == 1` (:1984), each overwriting the last as in the reference; video_embeddings_{ckpt}.npz under :2271 and
+        vid_metrics.yml through `write_to_yaml`.  GIFs, PNGs, captions and plots are not written.
+
+    Noise.  Without `seed=` the block init z is video_gen's default (torch.randn on the device, the centred gamma variate under model.gamma)
+    and the step noise the samplers' own.  With `seed=` both are Philox streams keyed by the GLOBAL row: (batch i, phase p) samples under
+    seed + ((3 i + p - 1) << 20), video_gen adds the block index, the step noise is the samplers' `seed` / `sample_offset` stream and the
+    block init z is mcvd_randn's layout at the draw word INIT_NOISE_DRAW (2^41, registered in kernels/philox.h).  `init_noise_fn(block,
+    shape, device)` replaces the init z in either case; `sampler=` replaces get_sampler(config).
+
+    Sharding.  shard=(rank, world), or with shard=None the rank and world of an initialised torch.distributed.  A rank takes the CLIPS
+    dist.shard_rows(n_clips, rank, world) of every batch, so a clip's preds_per_test rows stay together; global row = begin * preds_per_test
+    + local row goes to the samplers as sample_offset.  A shard needs `seed=` (ValueError: torch's generator is not row-keyed), and with
+    model.gamma an `init_noise_fn`.  Under torch.distributed the ranks exchange metrics.state() (and the tensors of the saved dicts) with ONE
+    all_gather_object after the loop, VideoMetrics.merged reassembles the global order, every rank returns the same dict -- the single-rank
+    one, bit for bit -- and rank 0 writes the files.  A shard without a process group returns {'shard': (rank, world), 'state':
+    metrics.state(), 'saved': {file stem: tensors}} for the caller to merge (VideoMetrics.merged(config, states).summary()).
+    data_transform's dequantisation noise is torch's and not row-keyed: a sharded run of such a config is not the single-rank one."""
+    import logging
+    import os
+    import time
+    import torch.distributed as tdist
+    from . import metrics as M
+    from .dist import shard_rows
+    log = log or logging.info
+    d, s = config.data, config.sampling
+    calc_ssim = getattr(s, "ssim", False)
+    calc_fvd = getattr(s, "fvd", False)
+    if not calc_fvd and calc_ssim is False:                           # :1340-1343
+        return {}
+    calc_fvd3 = M.fvd_gates(config)[2]                                # :1311-1337
+    if train:                                                         # :1345-1348
+        assert scorenet is not None and ckpt is not None
+        max_data_iter, preds_per_test = 1, 1
+    else:                                                             # :1350-1352
+        max_data_iter = s.max_data_iter if max_data_iter is None else max_data_iter
+        preds_per_test = getattr(s, "preds_per_test", 1) if preds_per_test is None else preds_per_test
+    start_time = time.time()
+    ppt = int(preds_per_test)
+    conditional = d.num_frames_cond > 0                               # :1355-1356
+    assert conditional, f"Video generating model has to be conditional! num_frames_cond has to be > 0! Given {d.num_frames_cond}"
+    future = getattr(d, "num_frames_future", 0)
+    prob_mask_future = getattr(d, "prob_mask_future", 0.0)
+    second_calc = future > 0 and prob_mask_future > 0.0 and not getattr(d, "prob_mask_sync", False)      # :1615-1616
+    gamma = bool(getattr(config.model, "gamma", False))
+    use_data_init = bool(getattr(s, "data_init", False))
+    if use_data_init:
+        if gamma:
+            raise NameError("name 'used_alphas' is not defined (runners/ncsn_runner.py:1496: the reference cannot run model.gamma with "
+                            "sampling.data_init; refused here as well)")
+        if data_init_batches is None:
+            raise ValueError("evaluate_video_gen: sampling.data_init is set: data_init_batches is needed")
+    if calc_fvd and fvd is None and metrics is None:
+        raise ValueError("evaluate_video_gen: sampling.fvd is set: a detector is needed (fvd=); the package loads none")
+
+    in_group = tdist.is_available() and tdist.is_initialized()
+    if shard is None:
+        shard = (tdist.get_rank(), tdist.get_world_size()) if in_group else (0, 1)
+    rank, world = int(shard[0]), int(shard[1])
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"evaluate_video_gen: shard = {shard!r} is not (rank, world) with 0 <= rank < world")
+    exchange = world > 1 and in_group and (rank, world) == (tdist.get_rank(), tdist.get_world_size())
+    if world > 1 and seed is None:
+        raise ValueError("evaluate_video_gen: a sharded evaluation needs seed= (the Philox streams are keyed by the global row; torch's "
+                         "generator is not)")
+    if world > 1 and gamma and init_noise_fn is None:
+        raise ValueError("evaluate_video_gen: a sharded evaluation of a model.gamma config needs init_noise_fn (the default gamma init "
+                         "is drawn from torch's CPU generator, which is not row-keyed)")
+
+    net = scorenet.module if hasattr(scorenet, "module") else scorenet                 # :1389
+    dev = net.device
+    if metrics is None:
+        metrics = M.VideoMetrics(config, preds_per_test=ppt, scorenet=None if getattr(net, "plan_only", False) else net,
+                                 lpips=lpips, fvd=fvd, fvd_batch=fvd_batch)
+    C, S = d.channels, d.image_size
+    init_iter = [None]
+
+    def next_data_init():                                             # :1480-1486: a loader that has run out is started over
+        for attempt in range(2):
+            if init_iter[0] is None:
+                init_iter[0] = iter(data_init_batches)
+            try:
+                b = next(init_iter[0])
+                return b[0] if isinstance(b, (list, tuple)) else b
+            except StopIteration:
+                init_iter[0] = None
+        raise ValueError("evaluate_video_gen: data_init_batches is empty")
+
+    def run_phase(i, phase, task, cond, cond_mask, begin, rows, nfp):
+        """One phase's block loop on this rank's rows -> frames in [0, 1]."""
+        data_init = None
+        if use_data_init:                                             # :1487-1489
+            data_init = data_transform(config, next_data_init().to(dev))[begin * ppt:begin * ppt + rows]
+        if rows == 0:                                                 # an empty shard samples nothing
+            return torch.zeros((0, C * nfp, S, S), device=dev)
+        kw, noise_fn = {}, init_noise_fn
+        if seed is not None:
+            phase_seed = int(seed) + ((3 * i + phase - 1) << _SEED_SHIFT)
+            kw = dict(seed=phase_seed, sample_offset=begin * ppt)
+            if noise_fn is None and not gamma:
+                noise_fn = lambda blk, shp, dv: _philox_init(net, phase_seed + blk, begin * ppt, shp, dv)      # noqa: E731
+        pred = video_gen(config, scorenet, cond, task=task, cond_mask=cond_mask, data_init=data_init, sampler=sampler,
+                         init_noise_fn=noise_fn, verbose=not train, log=not train, **kw)
+        return inverse_data_transform(config, pred)
+
+    saved = {}
+    for i, batch in enumerate(batches):
+        if i >= max_data_iter:                                        # :1439-1440
+            break
+        x = (batch[0] if isinstance(batch, (list, tuple)) else batch).to(dev)
+        begin, end = shard_rows(len(x), rank, world)
+        real_ = x[begin:end].repeat_interleave(ppt, dim=0)            # :1392-1395, this rank's clips
+        rows = len(real_)
+        real_ = data_transform(config, real_)                         # :1442
+
+        # (1) prediction, or interpolation with future frames (:1444-1609)
+        task1 = "pred" if future == 0 else "interp"
+        real, cond, cond_mask, nfp = task_conditioning(config, real_, task1)            # :1458-1459
+        real = inverse_data_transform(config, real)
+        cond_original = inverse_data_transform(config, cond.clone())
+        pred = run_phase(i, 1, task1, cond, cond_mask, begin, rows, nfp)
+        metrics.update(pred, real, phase=1, cond01=cond_original)
+
+        # (2) prediction with the future block masked (:1612-1778)
+        pred2 = real2 = None
+        if second_calc:
+            real2, cond2, cond_mask2, nfp2 = task_conditioning(config, real_, "pred_future_masked")      # :1625-1626
+            real2 = inverse_data_transform(config, real2)
+            cond_original2 = inverse_data_transform(config, cond2.clone())
+            pred2 = run_phase(i, 2, "pred_future_masked", cond2, cond_mask2, begin, rows, nfp2)
+            metrics.update(pred2, real2, phase=2, cond01=cond_original2)
+
+        # (3) unconditional generation, for its FVD alone (:1783-1916, :1974-1982)
+        pred_uncond = None
+        if calc_fvd3:
+            _, cond_fvd, cond_mask_fvd, nfp3 = task_conditioning(config, real_, "gen")  # :1798-1799
+            pred_uncond = run_phase(i, 3, "gen", cond_fvd, cond_mask_fvd, begin, rows, nfp3)
+            metrics.update_gen(pred_uncond)
+
+        if out_dir is not None and (i == 0 or ppt == 1):              # :1984
+            saved.update(_saved_dicts(config, pred, real, cond_original, pred2, real2, pred_uncond))
+            if world == 1:
+                for stem, dd in saved.items():
+                    torch.save(dd, os.path.join(out_dir, f"{stem}_{ckpt}.pt"))
+
+    if world > 1 and not exchange:
+        return {"shard": (rank, world), "state": metrics.state(), "saved": saved}
+    write = True
+    if exchange:
+        got = [None] * world
+        tdist.all_gather_object(got, (metrics.state(), saved))        # the one collective of a sharded evaluation
+        metrics = type(metrics).merged(config, [g[0] for g in got], scorenet=getattr(metrics, "scorenet", None))
+        write = rank == 0
+        if write and out_dir is not None:
+            for stem in got[0][1]:
+                dd = {k: torch.cat([g[1][stem][k] for g in got], dim=0) for k in got[0][1][stem]}
+                torch.save(dd, os.path.join(out_dir, f"{stem}_{ckpt}.pt"))
+    return _finish_video_gen(config, metrics, ckpt, train, out_dir, start_time, log, write)
+
+
+def _philox_init(net, seed, sample_offset, shape, dev):
+    """Standard normals of `shape` = [B, ...] on the device from the library's Philox stream (mcvd_randn): row b is the stream of
+    (seed, sample_offset + b, INIT_NOISE_DRAW), whatever the batch it is drawn in."""
+    import ctypes as C
+    from . import _lib
+    z = torch.empty(shape, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        net._bind_stream()
+        _lib.check(_lib.lib.mcvd_randn(net._ctx, C.c_void_p(z.data_ptr()), C.c_uint64(seed), C.c_uint64(sample_offset),
+                                       C.c_uint64(INIT_NOISE_DRAW), shape[0], z[0].numel()), "randn")
+    return z
+
+
 def _apply_ema_shadow(net, shadow):
     """EMAHelper.register / load_state_dict(shadow) / ema(net) of NCSNRunner.test (:2388-2392, models/ema.py:9-29): every parameter that
     requires grad takes shadow[name] (bare names: the helper unwraps DataParallel); states[0] is not read."""
