@@ -31,6 +31,8 @@
  *   mcvd_frame_metrics                    <- the per-frame MSE / SSIM loop of video_gen's test mode, runners/ncsn_runner.py:1580-1609
  *   mcvd_lpips_create / _set_param / _finalize / _frames
  *                                         <- eval_models.PerceptualLoss + the per-frame T2 / model_lpips.forward calls, ncsn_runner.py:1431, :1602-1605
+ *   mcvd_inception_create / _set_param / _finalize / _forward
+ *                                         <- evaluation/inception.py: InceptionV3 (the detector of fast_fid and nearest_neighbor)
  *   mcvd_fvd_clips                        <- the torch.cat / [::preds_per_test] / to_i3d of the FVD clips, ncsn_runner.py:1918-1982, and
  *                                            preprocess_single, models/fvd/fvd.py:160-186 (the detector call between is the caller's)
  *   mcvd_feature_stats                    <- compute_stats (np.mean / np.cov), models/fvd/fvd.py:275-278, and the
@@ -461,6 +463,30 @@ int mcvd_lpips_set_param(mcvd_lpips* net, const char* name, const void* ptr, con
 int mcvd_lpips_finalize(mcvd_lpips* net);
 int mcvd_lpips_frames(mcvd_lpips* net, const float* pred01, const float* real01, int B, int T, int C, int H, int W, float* lpips_out,
                       uint8_t* resized_out, float* per_tap_out);
+/* The FID InceptionV3 of fast_fid, fid_pr and nearest_neighbor (evaluation/inception.py: InceptionV3 over fid_inception_v3, eval mode),
+ * on the device.  The package holds no weights and downloads none: the caller hands over pt_inception-2015-12-05-6726825d.pth.
+ *   create / destroy    <- InceptionV3(...).  The net runs on ctx's device and stream.
+ *   set_param           one tensor of that file by its own key: "<layer>.conv.weight" [Cout, Cin, kh, kw] and
+ *                          "<layer>.bn.weight|bias|running_mean|running_var" [Cout] for the 94 BasicConv2d layers (Conv2d_1a_3x3 ...
+ *                          Mixed_7c.branch_pool); fp32, host pointer (on_device 0) or device pointer (1).  MCVD_EINVAL for an unknown
+ *                          name (fc.*, AuxLogits.* and *.num_batches_tracked are the caller's to drop) or a wrong element count.
+ *   finalize            folds every BatchNorm(eps 0.001) into alpha = w / sqrt(var + 0.001), beta = b - mean alpha (fp64, rounded once),
+ *                          packs the weights; MCVD_ESTATE names the first missing tensor.
+ *   forward             images01: [n, 3, H, W] fp32 in [0, 1] on the device.  resize_input: F.interpolate(size=(299, 299), bilinear,
+ *                          align_corners=False) (else H = W = 299 is required: MCVD_EINVAL); normalize_input: 2 x - 1.  block_mask: bit k
+ *                          asks for block k, written to out<k> (NCHW, device): [n, 64, 73, 73], [n, 192, 35, 35], [n, 768, 17, 17],
+ *                          [n, 2048, 1, 1]; the net runs up to the highest block asked for, the other outputs may be NULL.
+ *                          MCVD_ESTATE before finalize.  Every output element is one fp32 fma chain in a fixed order: bit-identical
+ *                          run to run, for any batch size and any split of the images into calls.  Images are processed in chunks of
+ *                          mcvd_inception_chunk() = 32, so the workspace stays below 508 MB whatever n, H and W are. */
+typedef struct mcvd_inception mcvd_inception;
+int mcvd_inception_create(mcvd_ctx* ctx, mcvd_inception** out);
+void mcvd_inception_destroy(mcvd_inception* net);
+int mcvd_inception_set_param(mcvd_inception* net, const char* name, const void* ptr, const int64_t* shape, int ndim, int on_device);
+int mcvd_inception_finalize(mcvd_inception* net);
+int mcvd_inception_chunk(void);
+int mcvd_inception_forward(mcvd_inception* net, const float* images01, int64_t n, int H, int W, int resize_input, int normalize_input,
+                           int block_mask, float* out0, float* out1, float* out2, float* out3);
 /* Denoising score-matching loss of a checkpoint on a batch, forward only (anneal_dsm_score_estimation, losses/dsm.py:7-52, for versions
  * DDPM / DDIM / FPNDM).  Three steps on the context's stream, with a = alphas[labels[b]] per row:
  *   z           = the caller's z, or drawn on the device: Philox normals keyed by (seed, sample_offset + row, draw word 2^40, element) --
@@ -512,6 +538,18 @@ int mcvd_op_conv2d(mcvd_ctx* ctx, const float* x0, int C0, const float* x1, int 
  * (device; repacked into the context's scratch per call), bias:[Cout] or NULL, y:[B,Cout,OH,OW], OH = (H + 2 pad - ks) / stride + 1. */
 int mcvd_op_conv2d_strided(mcvd_ctx* ctx, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, int ks,
                            int stride, int pad, int relu, float* y);
+/* y[:, c0 : c0 + Cout] = relu?( fma(conv2d(x, w, stride, (pad_h, pad_w)), alpha, beta) ) into a y of Ctot channels: the rectangular conv
+ * the FID InceptionV3 runs on (implicit GEMM on the fp32 MFMA, exact fp32 products, one fma chain per output in the order of w's
+ * flattened (ci, ky, kx); kh, kw in 1..15).  x:[B,Cin,H,W], w:[Cout,Cin,kh,kw] reference layout (device; repacked into the context's
+ * scratch per call), alpha / beta:[Cout] or NULL (1 / 0), y:[B,Ctot,OH,OW]; channels outside the slice are not touched. */
+int mcvd_op_conv2d_rect(mcvd_ctx* ctx, const float* x, const float* w, const float* alpha, const float* beta, int B, int Cin, int H, int W,
+                        int Cout, int kh, int kw, int stride, int pad_h, int pad_w, int relu, float* y, int c0, int Ctot);
+/* 3 x 3 pool, stride 1, padding 1, on [NC, H, W] planes: mode 0 = F.avg_pool2d(count_include_pad=False), mode 1 = F.max_pool2d. */
+int mcvd_op_pool3(mcvd_ctx* ctx, const float* x, float* y, int64_t NC, int H, int W, int mode);
+/* y[i] = mean of x[i, 0 : HW], summed in fp64 in index order and rounded once (AdaptiveAvgPool2d((1, 1))). */
+int mcvd_op_global_avg(mcvd_ctx* ctx, const float* x, float* y, int64_t NC, int HW);
+/* y [n, 3, 299, 299] = F.interpolate(x [n, 3, H, W], (299, 299), bilinear, align_corners=False), then 2 y - 1 when normalize. */
+int mcvd_op_resize299(mcvd_ctx* ctx, const float* x, int64_t n, int H, int W, int normalize, float* y);
 /* Which kernel family the calling thread's last conv launch (mcvd_op_conv2d or a model forward) was dispatched to: the ids of the
  * "conv_shape" option (0..3 direct implicit-GEMM tile shapes, 4 / 8 fp32 Winograd, 5 / 6 / 9 fp32 1x1 GEMM, 10 / 11 three-piece bf16
  * Winograd, 12 / 13 two-piece fp16 Winograd, 14 / 15 split-operand 1x1 GEMM); -1 none yet.  A forced "conv_shape" that does not apply to a

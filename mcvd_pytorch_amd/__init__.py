@@ -11,7 +11,7 @@ from .scorenet import HipScoreNet, get_model  # noqa: F401
 from .checkpoint import load_model, load_states_into  # noqa: F401
 from .runner import (conditioning_fn, data_transform, evaluate_video_gen, fast_fid, frames_to_uint8, inverse_data_transform,  # noqa: F401
                      nearest_neighbors, save_video_pred, task_conditioning, test_checkpoints, video_gen, video_gen_aliases, video_tasks)
-from .metrics import (LpipsNet, NearestNeighbors, VideoMetrics, feature_stats, fid_from_features, fid_from_stats, fid_pr, frame_lpips,  # noqa: F401
+from .metrics import (FidInception, LpipsNet, NearestNeighbors, VideoMetrics, feature_stats, fid_from_features, fid_from_stats, fid_pr, frame_lpips,  # noqa: F401
                       frame_metrics, frechet_distance, fvd_clips, fvd_gates, knn_radii, knn_search, manifold_hits, precision_recall, video_lpips)
 from .losses import anneal_dsm_score_estimation  # noqa: F401
 
@@ -20,5 +20,5 @@ __all__ = ["HipScoreNet", "get_model", "ddpm_sampler", "ddim_sampler", "fpndm_sa
            "inverse_data_transform", "video_gen", "video_tasks", "task_conditioning", "save_video_pred", "frames_to_uint8",
            "frame_metrics", "VideoMetrics", "LpipsNet", "frame_lpips", "video_lpips", "anneal_dsm_score_estimation", "test_checkpoints",
            "fvd_gates", "fvd_clips", "feature_stats", "frechet_distance", "knn_radii", "manifold_hits", "precision_recall",
-           "fid_from_features", "fid_from_stats", "fid_pr", "fast_fid", "knn_search",
+           "fid_from_features", "fid_from_stats", "fid_pr", "fast_fid", "knn_search", "FidInception",
            "NearestNeighbors", "nearest_neighbors", "evaluate_video_gen", "video_gen_aliases"]

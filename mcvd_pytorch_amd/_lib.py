@@ -90,6 +90,16 @@ _PROTOS = {
     "mcvd_lpips_set_param": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i, _i]),
     "mcvd_lpips_finalize": (_i, [_vp]),
     "mcvd_lpips_frames": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "mcvd_inception_create": (_i, [_vp, C.POINTER(_vp)]),
+    "mcvd_inception_destroy": (None, [_vp]),
+    "mcvd_inception_set_param": (_i, [_vp, C.c_char_p, _vp, C.POINTER(_i64), _i, _i]),
+    "mcvd_inception_finalize": (_i, [_vp]),
+    "mcvd_inception_chunk": (_i, []),
+    "mcvd_inception_forward": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "mcvd_op_conv2d_rect": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i]),
+    "mcvd_op_pool3": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i]),
+    "mcvd_op_global_avg": (_i, [_vp, _vp, _vp, _i64, _i]),
+    "mcvd_op_resize299": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp]),
     "mcvd_fvd_clips": (_i, [_vp, C.POINTER(_vp), C.POINTER(_i), C.POINTER(_i64), _i, _i, _i, _i, _i, _i, _i, _vp]),
     "mcvd_feature_stats": (_i, [_vp, _vp, _i, _i64, _i, _i64, _i64, _i64, _vp, _vp]),
     "mcvd_knn_radii": (_i, [_vp, _vp, _i, _i64, _i, _i64, _i, _vp]),

@@ -19,6 +19,7 @@
 
 #include "model.h"
 #include "conv_kernels.h"
+#include "inception.h"
 #include "lpips.h"
 
 using namespace mcvd;
@@ -1268,6 +1269,109 @@ int mcvd_op_conv2d_strided(mcvd_ctx* ctx, const float* x, const float* w, const 
     if (int rc = ctx->ensure_scratch(wfloats * sizeof(float))) return rc;
     if (int rc = launch_pack_conv_gemm(w, ctx->scratch, Cout, Cin, ks, ctx->stream)) return rc;
     return launch_conv_gemm(x, ctx->scratch, bias, y, B, Cin, H, W, Cout, ks, stride, pad, relu, ctx->stream);
+    API_CATCH
+}
+
+// The FID InceptionV3 (kernels/inception.cpp)
+int mcvd_inception_create(mcvd_ctx* ctx, mcvd_inception** out) {
+    API_TRY
+    MCVD_REQUIRE(ctx && out, "inception_create: NULL argument");
+    mcvd_inception* n = new mcvd_inception();
+    n->ctx = ctx;
+    *out = n;
+    return 0;
+    API_CATCH
+}
+
+void mcvd_inception_destroy(mcvd_inception* net) { delete net; }
+
+int mcvd_inception_set_param(mcvd_inception* net, const char* name, const void* ptr, const int64_t* shape, int ndim, int on_device) {
+    API_TRY
+    MCVD_REQUIRE(net && name && ptr && shape && ndim >= 1 && ndim <= 8, "inception_set_param: bad arguments");
+    int64_t numel = 1;
+    for (int i = 0; i < ndim; ++i) {
+        MCVD_REQUIRE(shape[i] > 0 && shape[i] < (1 << 24), "inception_set_param: bad shape");
+        numel *= shape[i];
+    }
+    MCVD_REQUIRE(numel < (1LL << 28), "inception_set_param: '%s' is too large", name);
+    if (!on_device) return inception_set_param(net, name, (const float*)ptr, numel);
+    std::vector<float> host((size_t)numel);
+    MCVD_HIP_CHECK(hipMemcpyAsync(host.data(), ptr, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost, net->ctx->stream));
+    MCVD_HIP_CHECK(hipStreamSynchronize(net->ctx->stream));
+    return inception_set_param(net, name, host.data(), numel);
+    API_CATCH
+}
+
+int mcvd_inception_finalize(mcvd_inception* net) {
+    API_TRY
+    MCVD_REQUIRE(net && net->ctx, "inception_finalize: NULL net");
+    return inception_finalize(net);
+    API_CATCH
+}
+
+int mcvd_inception_chunk(void) { return INCEPTION_CHUNK; }
+
+int mcvd_inception_forward(mcvd_inception* net, const float* images01, int64_t n, int H, int W, int resize_input, int normalize_input,
+                           int block_mask, float* out0, float* out1, float* out2, float* out3) {
+    API_TRY
+    MCVD_REQUIRE(net && net->ctx && images01, "inception_forward: NULL argument");
+    MCVD_REQUIRE(n > 0 && n < (1LL << 24), "inception_forward: bad image count %lld", (long long)n);
+    MCVD_REQUIRE(H > 0 && W > 0 && H <= 16384 && W <= 16384, "inception_forward: bad image size %d x %d", H, W);
+    if (!net->finalized) {
+        set_error("inception_forward before mcvd_inception_finalize");
+        return MCVD_ESTATE;
+    }
+    float* const out[4] = {out0, out1, out2, out3};
+    return inception_forward(net, images01, n, H, W, resize_input, normalize_input, block_mask, out);
+    API_CATCH
+}
+
+int mcvd_op_conv2d_rect(mcvd_ctx* ctx, const float* x, const float* w, const float* alpha, const float* beta, int B, int Cin, int H, int W,
+                        int Cout, int kh, int kw, int stride, int pad_h, int pad_w, int relu, float* y, int c0, int Ctot) {
+    API_TRY
+    MCVD_REQUIRE(ctx && x && w && y, "op_conv2d_rect: NULL argument");
+    MCVD_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && kh >= 1 && kh <= 15 && kw >= 1 && kw <= 15 && Cin <= 65536 && Cout <= 65536, "op_conv2d_rect: bad shape");
+    const int KP = conv_rect_kp(Cin, kh, kw);
+    const size_t wfloats = (size_t)KP * conv_rect_coutp(Cout);
+    if (int rc = ctx->ensure_scratch((wfloats + KP) * sizeof(float))) return rc;
+    int* tab = reinterpret_cast<int*>(ctx->scratch + wfloats);
+    std::vector<int> host;
+    conv_rect_table(Cin, kh, kw, host);
+    MCVD_HIP_CHECK(hipMemcpyAsync(tab, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    MCVD_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // `host` goes out of scope
+    if (int rc = launch_pack_conv_rect(w, ctx->scratch, Cout, Cin * kh * kw, ctx->stream)) return rc;
+    return launch_conv_rect(x, ctx->scratch, tab, alpha, beta, y, B, Cin, H, W, Cout, kh, kw, stride, pad_h, pad_w, relu, c0, Ctot, ctx->stream);
+    API_CATCH
+}
+
+int mcvd_op_pool3(mcvd_ctx* ctx, const float* x, float* y, int64_t NC, int H, int W, int mode) {
+    API_TRY
+    MCVD_REQUIRE(ctx, "op_pool3: NULL context");
+    return launch_pool3(x, y, NC, H, W, mode, ctx->stream);
+    API_CATCH
+}
+
+int mcvd_op_global_avg(mcvd_ctx* ctx, const float* x, float* y, int64_t NC, int HW) {
+    API_TRY
+    MCVD_REQUIRE(ctx, "op_global_avg: NULL context");
+    return launch_global_avg(x, y, NC, HW, ctx->stream);
+    API_CATCH
+}
+
+int mcvd_op_resize299(mcvd_ctx* ctx, const float* x, int64_t n, int H, int W, int normalize, float* y) {
+    API_TRY
+    MCVD_REQUIRE(ctx && x && y, "op_resize299: NULL argument");
+    MCVD_REQUIRE(n > 0 && n < (1LL << 24) && H > 0 && W > 0 && H <= 16384 && W <= 16384, "op_resize299: bad shape");
+    std::vector<int> th, tw;
+    inception_axis_table(H, th);
+    inception_axis_table(W, tw);
+    if (int rc = ctx->ensure_scratch((th.size() + tw.size()) * sizeof(int))) return rc;
+    int* dh = reinterpret_cast<int*>(ctx->scratch);
+    int* dw = dh + th.size();
+    MCVD_HIP_CHECK(hipMemcpyAsync(dh, th.data(), th.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    MCVD_HIP_CHECK(hipMemcpyAsync(dw, tw.data(), tw.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    MCVD_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // the host tables go out of scope
+    return launch_inception_prep(x, y, n, H, W, normalize, dh, dw, ctx->stream);
     API_CATCH
 }
 

@@ -23,7 +23,8 @@ HOST_ONLY_FLAGS = {"model.cpp": ["-ffp-contract=off"], "api.cpp": ["-ffp-contrac
                    "sampler.cpp": ["-ffp-contract=off"],      # sampler update kernels: one rounding per operation
                    "dsm.cpp": ["-ffp-contract=off"],          # the loss's perturbation: the reference's separate roundings, same Philox bits
                    "lpips.cpp": ["-ffp-contract=off"],        # Pillow's resize tables: the same double expressions, one rounding each
-                   "fvd.cpp": ["-ffp-contract=off"]}          # torch's bilinear coordinates and lerp: one rounding per operation
+                   "fvd.cpp": ["-ffp-contract=off"],          # torch's bilinear coordinates and lerp: one rounding per operation
+                   "inception.cpp": ["-ffp-contract=off"]}    # the same coordinate rule for 299 x 299, and alpha / beta rounded once
 
 
 def sources():

@@ -16,8 +16,10 @@ statistics on the device (feature_stats), the Frechet distance (frechet_distance
 
 fast_fid's scores (evaluation/fid_PR.py, NCSNRunner.fast_fid) are at the end of the module: FID from the same feature_stats /
 frechet_from_stats, and the improved precision and recall (k-nearest-neighbour manifolds) in fp64 on the device without the pairwise
-distance matrices (mcvd_knn_radii, mcvd_manifold_hits, kernels/prdc.cpp).  The detector (the reference's InceptionV3) is the caller's, as
-with FVD.
+distance matrices (mcvd_knn_radii, mcvd_manifold_hits, kernels/prdc.cpp).  `detector=` takes any callable; the reference's own detector,
+the FID InceptionV3 of evaluation/inception.py, is FidInception below (mcvd_inception_*, kernels/inception.cpp): the architecture runs on
+the device and the caller hands over the weights (pt_inception-2015-12-05-6726825d.pth) as a state dict or a path -- the package holds
+none and downloads none, as with LPIPS.
 
 Deliberate divergences from the reference:
   * frames of 2 or 4 channels (torchvision's LA / RGBA images) are refused with ValueError: no MCVD dataset has them;
@@ -763,7 +765,8 @@ def get_activations(x, detector=None, batch_size=50):
     if x.dim() != 4:
         raise ValueError(f"fid_pr: a tensor of shape {tuple(x.shape)} is neither features [n, dims] nor images [n, C, H, W]")
     if detector is None:
-        raise ValueError("fid_pr: an image tensor needs a detector (the package holds no Inception: the detector is the caller's)")
+        raise ValueError("fid_pr: an image tensor needs a detector, e.g. FidInception(...).load_state_dict(weights) (the package holds no "
+                         "Inception weights: they are the caller's)")
     n = len(x)
     batch_size = int(batch_size)
     if batch_size < 1:
@@ -783,7 +786,7 @@ def get_activations(x, detector=None, batch_size=50):
 
 def fid_pr(real, fake, detector=None, k=3, batch_size=50, save_feats_path=None, scorenet=None):
     """(fid, precision, recall) of get_fid_PR (fid_PR.py:282-299).  `real` and `fake` are each a feature tensor, a `.pt` / `.pth` path of
-    features or an image tensor (see get_activations; images need `detector`, which is the caller's as with VideoMetrics' `fvd=`).
+    features or an image tensor (see get_activations; images need `detector`: FidInception with the caller's weights, or any callable).
     save_feats_path: the generated features are torch.save()d there (on the CPU), as the reference does for its feats_{ckpt}.pt."""
     feat_r = get_activations(real, detector, batch_size)
     feat_g = get_activations(fake, detector, batch_size)
@@ -791,6 +794,154 @@ def fid_pr(real, fake, detector=None, k=3, batch_size=50, save_feats_path=None, 
         torch.save(feat_g.detach().cpu(), save_feats_path)
     precision, recall = precision_recall(feat_r, feat_g, k, scorenet=scorenet)
     return fid_from_features(feat_r, feat_g, scorenet=scorenet), precision, recall
+
+
+def _inception_a(p, cin, pf):
+    return [(p + ".branch1x1", 64, cin, 1, 1), (p + ".branch5x5_1", 48, cin, 1, 1), (p + ".branch5x5_2", 64, 48, 5, 5),
+            (p + ".branch3x3dbl_1", 64, cin, 1, 1), (p + ".branch3x3dbl_2", 96, 64, 3, 3), (p + ".branch3x3dbl_3", 96, 96, 3, 3),
+            (p + ".branch_pool", pf, cin, 1, 1)]
+
+
+def _inception_c(p, cin, c7):
+    return [(p + ".branch1x1", 192, cin, 1, 1), (p + ".branch7x7_1", c7, cin, 1, 1), (p + ".branch7x7_2", c7, c7, 1, 7),
+            (p + ".branch7x7_3", 192, c7, 7, 1), (p + ".branch7x7dbl_1", c7, cin, 1, 1), (p + ".branch7x7dbl_2", c7, c7, 7, 1),
+            (p + ".branch7x7dbl_3", c7, c7, 1, 7), (p + ".branch7x7dbl_4", c7, c7, 7, 1), (p + ".branch7x7dbl_5", 192, c7, 1, 7),
+            (p + ".branch_pool", 192, cin, 1, 1)]
+
+
+def _inception_e(p, cin):
+    return [(p + ".branch1x1", 320, cin, 1, 1), (p + ".branch3x3_1", 384, cin, 1, 1), (p + ".branch3x3_2a", 384, 384, 1, 3),
+            (p + ".branch3x3_2b", 384, 384, 3, 1), (p + ".branch3x3dbl_1", 448, cin, 1, 1), (p + ".branch3x3dbl_2", 384, 448, 3, 3),
+            (p + ".branch3x3dbl_3a", 384, 384, 1, 3), (p + ".branch3x3dbl_3b", 384, 384, 3, 1), (p + ".branch_pool", 192, cin, 1, 1)]
+
+
+# The 94 BasicConv2d layers of the FID InceptionV3 in torchvision's module order: (name, Cout, Cin, kh, kw) = the shape of
+# `<name>.conv.weight`; `<name>.bn.weight|bias|running_mean|running_var` are [Cout].  Strides and paddings live in kernels/inception.cpp.
+FID_INCEPTION_CONVS = tuple(
+    [("Conv2d_1a_3x3", 32, 3, 3, 3), ("Conv2d_2a_3x3", 32, 32, 3, 3), ("Conv2d_2b_3x3", 64, 32, 3, 3), ("Conv2d_3b_1x1", 80, 64, 1, 1),
+     ("Conv2d_4a_3x3", 192, 80, 3, 3)]
+    + _inception_a("Mixed_5b", 192, 32) + _inception_a("Mixed_5c", 256, 64) + _inception_a("Mixed_5d", 288, 64)
+    + [("Mixed_6a.branch3x3", 384, 288, 3, 3), ("Mixed_6a.branch3x3dbl_1", 64, 288, 1, 1), ("Mixed_6a.branch3x3dbl_2", 96, 64, 3, 3),
+       ("Mixed_6a.branch3x3dbl_3", 96, 96, 3, 3)]
+    + _inception_c("Mixed_6b", 768, 128) + _inception_c("Mixed_6c", 768, 160) + _inception_c("Mixed_6d", 768, 160)
+    + _inception_c("Mixed_6e", 768, 192)
+    + [("Mixed_7a.branch3x3_1", 192, 768, 1, 1), ("Mixed_7a.branch3x3_2", 320, 192, 3, 3), ("Mixed_7a.branch7x7x3_1", 192, 768, 1, 1),
+       ("Mixed_7a.branch7x7x3_2", 192, 192, 1, 7), ("Mixed_7a.branch7x7x3_3", 192, 192, 7, 1), ("Mixed_7a.branch7x7x3_4", 192, 192, 3, 3)]
+    + _inception_e("Mixed_7b", 1280) + _inception_e("Mixed_7c", 2048))
+_FID_BN = ("weight", "bias", "running_mean", "running_var")
+# every tensor FidInception.load_state_dict requires -> its shape, in the state dict's own order
+FID_INCEPTION_PARAMS = {}
+for _n, _co, _ci, _kh, _kw in FID_INCEPTION_CONVS:
+    FID_INCEPTION_PARAMS[f"{_n}.conv.weight"] = (_co, _ci, _kh, _kw)
+    for _k in _FID_BN:
+        FID_INCEPTION_PARAMS[f"{_n}.bn.{_k}"] = (_co,)
+del _n, _co, _ci, _kh, _kw, _k
+_FID_BLOCK_SHAPES = ((64, 73, 73), (192, 35, 35), (768, 17, 17), (2048, 1, 1))
+
+
+class FidInception:
+    """The reference's evaluation.inception.InceptionV3(output_blocks, resize_input, normalize_input) -- the FID variant
+    (use_fid_inception=True), eval mode, no gradients -- on the device, as a `detector=` for fid_pr, fast_fid and NearestNeighbors:
+
+        det = FidInception(scorenet=hipnet).load_state_dict("pt_inception-2015-12-05-6726825d.pth")      # or FidInception(device="cuda:0")
+        feats = det(images01)[0]                                # [n, 2048, 1, 1]; a list in ascending block order, as InceptionV3.forward
+
+    output_blocks: any of 0 (first max pool, 64 x 73 x 73), 1 (second max pool, 192 x 35 x 35), 2 (Mixed_6e, 768 x 17 x 17), 3 (the final
+    average pool, 2048 x 1 x 1); the net runs up to the highest one.  The weights are the caller's: load_state_dict takes the reference's
+    file (a path or its dict) by its own key names and the package holds and downloads none.  Runs on the scorenet's context and stream
+    when given one, else on this module's own context (as LpipsNet).  Missing weights are an error at the first use (MCVD_ESTATE names
+    the tensor).  There is no CPU fallback."""
+
+    def __init__(self, output_blocks=(3,), resize_input=True, normalize_input=True, device=None, scorenet=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("FidInception needs a ROCm GPU (MI355X); there is no CPU fallback")
+        blocks = sorted(set(int(b) for b in output_blocks))
+        if not blocks or blocks[0] < 0 or blocks[-1] > 3:
+            raise ValueError(f"FidInception: output_blocks {tuple(output_blocks)} must be a non-empty subset of 0..3")
+        self.output_blocks, self.resize_input, self.normalize_input = blocks, bool(resize_input), bool(normalize_input)
+        self.scorenet = scorenet
+        if scorenet is not None:
+            self.device = scorenet.device
+        else:
+            dev = torch.device(device if device is not None else "cuda")
+            self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+        self._net = C.c_void_p()
+        self._final = False
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib.mcvd_inception_create(self._ctx(), C.byref(self._net)), "inception_create")
+
+    def _ctx(self):
+        if self.scorenet is not None:
+            self.scorenet._bind_stream()
+            return self.scorenet._ctx
+        return _package_ctx(self.device)
+
+    def _set(self, name, t):
+        t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        shape = (C.c_int64 * t.dim())(*t.shape)
+        _lib.check(_lib.lib.mcvd_inception_set_param(self._net, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), 0),
+                   f"inception_set_param({name})")
+        self._final = False
+
+    def load_state_dict(self, sd_or_path):
+        """The reference's pt_inception-2015-12-05-6726825d.pth (path or dict): `X.conv.weight`, `X.bn.weight|bias|running_mean|running_var`.
+        `fc.*`, `AuxLogits.*` and `*.num_batches_tracked` are ignored; any other unknown key and any wrong shape is a ValueError.  A
+        partial dict is accepted (what is still missing is named at the first use)."""
+        sd = sd_or_path
+        if not isinstance(sd, dict):
+            sd = torch.load(sd, map_location="cpu", weights_only=True)
+        for name, t in sd.items():
+            if name.startswith("fc.") or name.startswith("AuxLogits.") or name.endswith(".num_batches_tracked"):
+                continue
+            want = FID_INCEPTION_PARAMS.get(name)
+            if want is None:
+                raise ValueError(f"FidInception.load_state_dict: unknown key {name!r}")
+            if tuple(t.shape) != want:
+                raise ValueError(f"FidInception.load_state_dict: {name} has shape {tuple(t.shape)}, expected {want}")
+            self._set(name, t)
+        return self
+
+    def finalize(self):
+        if not self._final:
+            with torch.cuda.device(self.device):
+                self._ctx()
+                _lib.check(_lib.lib.mcvd_inception_finalize(self._net), "inception_finalize")
+            self._final = True
+        return self
+
+    @torch.no_grad()
+    def __call__(self, images):
+        """images [n, 3, H, W] in [0, 1] -> the requested blocks' outputs, a list of fp32 device tensors in ascending block order."""
+        if not torch.is_tensor(images) or images.dim() != 4:
+            raise ValueError("FidInception: images must be a tensor [n, 3, H, W]")
+        n, ch, H, W = images.shape
+        if ch != 3:
+            raise ValueError(f"FidInception: {ch}-channel images (Conv2d_1a_3x3 takes 3 channels)")
+        if n < 1:
+            raise ValueError("FidInception: no images")
+        if not self.resize_input and (H, W) != (299, 299):
+            raise ValueError(f"FidInception: resize_input=False needs 299 x 299 images, got {H} x {W}")
+        x = images.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        self.finalize()
+        outs = [None] * 4
+        mask = 0
+        for b in self.output_blocks:
+            outs[b] = torch.empty((n,) + _FID_BLOCK_SHAPES[b], dtype=torch.float32, device=self.device)
+            mask |= 1 << b
+        with torch.cuda.device(self.device):
+            self._ctx()
+            ptrs = [C.c_void_p(o.data_ptr()) if o is not None else None for o in outs]
+            _lib.check(_lib.lib.mcvd_inception_forward(self._net, C.c_void_p(x.data_ptr()), n, H, W, int(self.resize_input),
+                                                       int(self.normalize_input), mask, *ptrs), "inception_forward")
+        return [outs[b] for b in self.output_blocks]
+
+    def __del__(self):
+        try:
+            if getattr(self, "_net", None):
+                _lib.lib.mcvd_inception_destroy(self._net)
+                self._net = None
+        except Exception:
+            pass
 
 
 # ---- nearest neighbours of samples in a data set (evaluation/nearest_neighbor.py) -----------------------------------------------------------
@@ -878,8 +1029,8 @@ class NearestNeighbors:
     update() the state is k distances, k indices and k images per sample, all on the device.
 
     samples: a tensor [n, C, H, W] in [0, 1] or the path of a .pt that holds one (fast_fid's samples_{ckpt}.pt); `[:n_samples]` is applied
-    as the reference does.  detector: the caller's (the reference's InceptionV3([block]); the package holds none), called on the whole
-    batch.  flip=False searches with the unmirrored view alone.  Ties in distance go to the lower data index (topk leaves them open)."""
+    as the reference does.  detector: the reference's InceptionV3([block]) is FidInception((block,)) with the caller's weights; any
+    callable will do.  It is called on the whole batch.  flip=False searches with the unmirrored view alone.  Ties in distance go to the lower data index (topk leaves them open)."""
 
     def __init__(self, samples, detector, k=10, n_samples=10, flip=True, scorenet=None):
         if isinstance(samples, str):
@@ -890,7 +1041,8 @@ class NearestNeighbors:
             raise ValueError("NearestNeighbors: samples must be an image tensor [n, C, H, W] or the .pt path of one, got "
                              + (str(tuple(samples.shape)) if torch.is_tensor(samples) else type(samples).__name__))
         if detector is None:
-            raise ValueError("NearestNeighbors: a detector is needed (the package holds no Inception: the detector is the caller's)")
+            raise ValueError("NearestNeighbors: a detector is needed, e.g. FidInception(...).load_state_dict(weights) (the package holds no "
+                             "Inception weights: they are the caller's)")
         k, n_samples = int(k), int(n_samples)
         if not 1 <= k <= 16:
             raise ValueError(f"NearestNeighbors: k = {k} is outside 1..16")

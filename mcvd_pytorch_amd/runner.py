@@ -687,7 +687,8 @@ def fast_fid(config, scorenet, real, detector=None, cond_batches=None, ckpts=Non
         model.gamma; inverse_data_transform; at the end everything reshaped to (-1, C, S, S).  The samples stay on the device;
       * scoring: metrics.fid_pr(real, samples, detector, k=fast_fid.pr_nn_k) -- `real` is the dataset's features (a tensor or a .pt / .pth
         path) or images --, or with `no_pr` metrics.fid_from_stats(real, features of the samples) with `real` = (mu, sigma) or an .npz path.
-        The detector is the caller's (see metrics.fid_pr); the dataset feature files and the stats download of get_feats_path /
+        The detector is any callable -- the reference's is metrics.FidInception with the caller's weights (see metrics.fid_pr); the
+        dataset feature files and the stats download of get_feats_path /
         get_stats_path stay with the caller;
       * files, only with `out_dir`: samples_{ckpt}.pt (CPU tensor) and, without `no_pr`, feats_{ckpt}.pt are written, and reused when present,
         features first, then samples (:2477-2484) -- a checkpoint whose features are there is neither loaded nor sampled.  The image grid,
@@ -728,7 +729,7 @@ def fast_fid(config, scorenet, real, detector=None, cond_batches=None, ckpts=Non
     elif not torch.is_tensor(real) or real.dim() not in (2, 4):
         raise ValueError("fast_fid: `real` must be features [n, dims], images [n, C, H, W] or a .pt / .pth path of features")
     elif real.dim() == 4 and detector is None:
-        raise ValueError("fast_fid: `real` holds images: a detector is needed")
+        raise ValueError("fast_fid: `real` holds images: a detector is needed (e.g. FidInception(...).load_state_dict(weights))")
 
     def cached(kind, ckpt):
         path = None if out_dir is None else os.path.join(out_dir, f"{kind}_{ckpt}.pt")
@@ -737,7 +738,7 @@ def fast_fid(config, scorenet, real, detector=None, cond_batches=None, ckpts=Non
         if cached("feats", ckpt)[1]:
             continue
         if detector is None:
-            raise ValueError(f"fast_fid: ckpt {ckpt} has no cached features: a detector is needed to score its samples")
+            raise ValueError(f"fast_fid: ckpt {ckpt} has no cached features: a detector is needed to score its samples (e.g. FidInception(...).load_state_dict(weights))")
         if cached("samples", ckpt)[1]:
             continue
         if ckpt_dir is None:
