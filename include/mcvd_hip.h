@@ -533,14 +533,16 @@ int mcvd_upfirdn2d(mcvd_ctx* ctx, const float* in, const float* kernel_host, int
 int mcvd_op_conv2d(mcvd_ctx* ctx, const float* x0, int C0, const float* x1, int C1, const float* w, const float* bias,
                    int Cout, int ks, const float* coef, int act, const float* res, float out_scale, float* y, int B, int H,
                    int W);
-/* y = relu?( conv2d(x, w, bias, stride, padding) ): the general conv LPIPS's AlexNet runs on (implicit GEMM on the fp32 MFMA, exact fp32
- * products; any odd ks, any stride, zero padding, any map size; torch's F.conv2d).  x:[B,Cin,H,W], w:[Cout,Cin,ks,ks] reference layout
- * (device; repacked into the context's scratch per call), bias:[Cout] or NULL, y:[B,Cout,OH,OW], OH = (H + 2 pad - ks) / stride + 1. */
+/* y = relu?( conv2d(x, w, bias, stride, padding) ): the conv LPIPS's AlexNet runs on -- mcvd_op_conv2d_rect's kernel with kh = kw = ks,
+ * pad_h = pad_w = pad, alpha NULL, beta = bias, c0 = 0, Ctot = Cout, and the same values bit for bit (implicit GEMM on the fp32 MFMA, exact
+ * fp32 products; any odd ks up to 31, any stride, zero padding, any map size; torch's F.conv2d).  x:[B,Cin,H,W], w:[Cout,Cin,ks,ks]
+ * reference layout (device; repacked into the context's scratch per call), bias:[Cout] or NULL, y:[B,Cout,OH,OW],
+ * OH = (H + 2 pad - ks) / stride + 1. */
 int mcvd_op_conv2d_strided(mcvd_ctx* ctx, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, int ks,
                            int stride, int pad, int relu, float* y);
-/* y[:, c0 : c0 + Cout] = relu?( fma(conv2d(x, w, stride, (pad_h, pad_w)), alpha, beta) ) into a y of Ctot channels: the rectangular conv
- * the FID InceptionV3 runs on (implicit GEMM on the fp32 MFMA, exact fp32 products, one fma chain per output in the order of w's
- * flattened (ci, ky, kx); kh, kw in 1..15).  x:[B,Cin,H,W], w:[Cout,Cin,kh,kw] reference layout (device; repacked into the context's
+/* y[:, c0 : c0 + Cout] = relu?( fma(conv2d(x, w, stride, (pad_h, pad_w)), alpha, beta) ) into a y of Ctot channels: the conv the
+ * FID InceptionV3 runs on, and LPIPS's (implicit GEMM on the fp32 MFMA, exact fp32 products, one fma chain per output in the order of w's
+ * flattened (ci, ky, kx); kh, kw in 1..31).  x:[B,Cin,H,W], w:[Cout,Cin,kh,kw] reference layout (device; repacked into the context's
  * scratch per call), alpha / beta:[Cout] or NULL (1 / 0), y:[B,Ctot,OH,OW]; channels outside the slice are not touched. */
 int mcvd_op_conv2d_rect(mcvd_ctx* ctx, const float* x, const float* w, const float* alpha, const float* beta, int B, int Cin, int H, int W,
                         int Cout, int kh, int kw, int stride, int pad_h, int pad_w, int relu, float* y, int c0, int Ctot);

@@ -121,6 +121,41 @@ void ctx_unregister(mcvd_ctx* c) {
     auto& v = g_live_ctx[c->device];
     v.erase(std::remove(v.begin(), v.end(), c), v.end());
 }
+
+// The set_param front end of the detector nets: the shape's element count, and a device tensor through the host; `set` is the net's own
+template <class Net>
+int net_set_param(const char* who, int (*set)(Net*, const char*, const float*, int64_t), Net* net, const char* name, const void* ptr,
+                  const int64_t* shape, int ndim, int on_device) {
+    MCVD_REQUIRE(net && name && ptr && shape && ndim >= 1 && ndim <= 8, "%s: bad arguments", who);
+    int64_t numel = 1;
+    for (int i = 0; i < ndim; ++i) {
+        MCVD_REQUIRE(shape[i] > 0 && shape[i] < (1 << 24), "%s: bad shape", who);
+        numel *= shape[i];
+    }
+    MCVD_REQUIRE(numel < (1LL << 28), "%s: '%s' is too large", who, name);
+    if (!on_device) return set(net, name, (const float*)ptr, numel);
+    std::vector<float> host((size_t)numel);
+    MCVD_HIP_CHECK(hipMemcpyAsync(host.data(), ptr, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost, net->ctx->stream));
+    MCVD_HIP_CHECK(hipStreamSynchronize(net->ctx->stream));
+    return set(net, name, host.data(), numel);
+}
+
+// One conv of the detector nets on unpacked weights (mcvd_op_conv2d_strided / _rect, named by `who`): the tap table and the packed
+// weights go to the context's scratch
+int detector_conv_op(const char* who, mcvd_ctx* ctx, const float* x, const float* w, const float* alpha, const float* beta, int B, int Cin,
+                     int H, int W, int Cout, int kh, int kw, int stride, int pad_h, int pad_w, int relu, float* y, int c0, int Ctot) {
+    const int KP = conv_kp(Cin, kh, kw);
+    const size_t wfloats = (size_t)KP * conv_coutp(Cout);
+    if (int rc = ctx->ensure_scratch((wfloats + KP) * sizeof(float))) return rc;
+    int* tab = reinterpret_cast<int*>(ctx->scratch + wfloats);
+    std::vector<int> host;
+    conv_table(Cin, kh, kw, host);
+    MCVD_HIP_CHECK(hipMemcpyAsync(tab, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    MCVD_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // `host` goes out of scope
+    if (int rc = launch_pack_conv(w, ctx->scratch, Cout, Cin * kh * kw, ctx->stream)) return rc;
+    return launch_conv(x, ctx->scratch, tab, alpha, beta, y, B, Cin, H, W, Cout, kh, kw, stride, pad_h, pad_w, relu, c0, Ctot, who,
+                       ctx->stream);
+}
 }  // namespace
 
 // Does anything else run kernels on this context's device CONCURRENTLY with it?  Another process (the context was let in by
@@ -1223,18 +1258,7 @@ void mcvd_lpips_destroy(mcvd_lpips* net) { delete net; }
 
 int mcvd_lpips_set_param(mcvd_lpips* net, const char* name, const void* ptr, const int64_t* shape, int ndim, int on_device) {
     API_TRY
-    MCVD_REQUIRE(net && name && ptr && shape && ndim >= 1 && ndim <= 8, "lpips_set_param: bad arguments");
-    int64_t numel = 1;
-    for (int i = 0; i < ndim; ++i) {
-        MCVD_REQUIRE(shape[i] > 0 && shape[i] < (1 << 24), "lpips_set_param: bad shape");
-        numel *= shape[i];
-    }
-    MCVD_REQUIRE(numel < (1LL << 28), "lpips_set_param: '%s' is too large", name);
-    if (!on_device) return lpips_set_param(net, name, (const float*)ptr, numel);
-    std::vector<float> host((size_t)numel);
-    MCVD_HIP_CHECK(hipMemcpyAsync(host.data(), ptr, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost, net->ctx->stream));
-    MCVD_HIP_CHECK(hipStreamSynchronize(net->ctx->stream));
-    return lpips_set_param(net, name, host.data(), numel);
+    return net_set_param("lpips_set_param", lpips_set_param, net, name, ptr, shape, ndim, on_device);
     API_CATCH
 }
 
@@ -1265,10 +1289,7 @@ int mcvd_op_conv2d_strided(mcvd_ctx* ctx, const float* x, const float* w, const 
     API_TRY
     MCVD_REQUIRE(ctx && x && w && y, "op_conv2d_strided: NULL argument");
     MCVD_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && ks >= 1 && ks <= 31 && (ks & 1) && Cin <= 65536 && Cout <= 65536, "op_conv2d_strided: bad shape");
-    const size_t wfloats = (size_t)conv_gemm_kp(Cin, ks) * conv_gemm_coutp(Cout);
-    if (int rc = ctx->ensure_scratch(wfloats * sizeof(float))) return rc;
-    if (int rc = launch_pack_conv_gemm(w, ctx->scratch, Cout, Cin, ks, ctx->stream)) return rc;
-    return launch_conv_gemm(x, ctx->scratch, bias, y, B, Cin, H, W, Cout, ks, stride, pad, relu, ctx->stream);
+    return detector_conv_op("op_conv2d_strided", ctx, x, w, nullptr, bias, B, Cin, H, W, Cout, ks, ks, stride, pad, pad, relu, y, 0, Cout);
     API_CATCH
 }
 
@@ -1287,18 +1308,7 @@ void mcvd_inception_destroy(mcvd_inception* net) { delete net; }
 
 int mcvd_inception_set_param(mcvd_inception* net, const char* name, const void* ptr, const int64_t* shape, int ndim, int on_device) {
     API_TRY
-    MCVD_REQUIRE(net && name && ptr && shape && ndim >= 1 && ndim <= 8, "inception_set_param: bad arguments");
-    int64_t numel = 1;
-    for (int i = 0; i < ndim; ++i) {
-        MCVD_REQUIRE(shape[i] > 0 && shape[i] < (1 << 24), "inception_set_param: bad shape");
-        numel *= shape[i];
-    }
-    MCVD_REQUIRE(numel < (1LL << 28), "inception_set_param: '%s' is too large", name);
-    if (!on_device) return inception_set_param(net, name, (const float*)ptr, numel);
-    std::vector<float> host((size_t)numel);
-    MCVD_HIP_CHECK(hipMemcpyAsync(host.data(), ptr, (size_t)numel * sizeof(float), hipMemcpyDeviceToHost, net->ctx->stream));
-    MCVD_HIP_CHECK(hipStreamSynchronize(net->ctx->stream));
-    return inception_set_param(net, name, host.data(), numel);
+    return net_set_param("inception_set_param", inception_set_param, net, name, ptr, shape, ndim, on_device);
     API_CATCH
 }
 
@@ -1330,17 +1340,8 @@ int mcvd_op_conv2d_rect(mcvd_ctx* ctx, const float* x, const float* w, const flo
                         int Cout, int kh, int kw, int stride, int pad_h, int pad_w, int relu, float* y, int c0, int Ctot) {
     API_TRY
     MCVD_REQUIRE(ctx && x && w && y, "op_conv2d_rect: NULL argument");
-    MCVD_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && kh >= 1 && kh <= 15 && kw >= 1 && kw <= 15 && Cin <= 65536 && Cout <= 65536, "op_conv2d_rect: bad shape");
-    const int KP = conv_rect_kp(Cin, kh, kw);
-    const size_t wfloats = (size_t)KP * conv_rect_coutp(Cout);
-    if (int rc = ctx->ensure_scratch((wfloats + KP) * sizeof(float))) return rc;
-    int* tab = reinterpret_cast<int*>(ctx->scratch + wfloats);
-    std::vector<int> host;
-    conv_rect_table(Cin, kh, kw, host);
-    MCVD_HIP_CHECK(hipMemcpyAsync(tab, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
-    MCVD_HIP_CHECK(hipStreamSynchronize(ctx->stream));      // `host` goes out of scope
-    if (int rc = launch_pack_conv_rect(w, ctx->scratch, Cout, Cin * kh * kw, ctx->stream)) return rc;
-    return launch_conv_rect(x, ctx->scratch, tab, alpha, beta, y, B, Cin, H, W, Cout, kh, kw, stride, pad_h, pad_w, relu, c0, Ctot, ctx->stream);
+    MCVD_REQUIRE(B > 0 && Cin > 0 && Cout > 0 && kh >= 1 && kh <= 31 && kw >= 1 && kw <= 31 && Cin <= 65536 && Cout <= 65536, "op_conv2d_rect: bad shape");
+    return detector_conv_op("op_conv2d_rect", ctx, x, w, alpha, beta, B, Cin, H, W, Cout, kh, kw, stride, pad_h, pad_w, relu, y, c0, Ctot);
     API_CATCH
 }
 

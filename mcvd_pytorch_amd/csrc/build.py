@@ -23,8 +23,9 @@ HOST_ONLY_FLAGS = {"model.cpp": ["-ffp-contract=off"], "api.cpp": ["-ffp-contrac
                    "sampler.cpp": ["-ffp-contract=off"],      # sampler update kernels: one rounding per operation
                    "dsm.cpp": ["-ffp-contract=off"],          # the loss's perturbation: the reference's separate roundings, same Philox bits
                    "lpips.cpp": ["-ffp-contract=off"],        # Pillow's resize tables: the same double expressions, one rounding each
-                   "fvd.cpp": ["-ffp-contract=off"],          # torch's bilinear coordinates and lerp: one rounding per operation
-                   "inception.cpp": ["-ffp-contract=off"]}    # the same coordinate rule for 299 x 299, and alpha / beta rounded once
+                   "fvd.cpp": ["-ffp-contract=off"],          # torch's bilinear lerp: one rounding per operation
+                   "inception.cpp": ["-ffp-contract=off"],    # alpha / beta of a folded BatchNorm: fp64, rounded once
+                   "detector_ops.cpp": ["-ffp-contract=off"]} # torch's bilinear coordinate rule, and the kernels moved out of the two files above
 
 
 def sources():

@@ -1,5 +1,5 @@
-// The FID InceptionV3 (kernels/inception.cpp): the net object behind mcvd_inception_* and the rectangular conv, the stride-1 3 x 3 pools,
-// the global average and the 299 x 299 bilinear resize it is made of.
+// The FID InceptionV3 (kernels/inception.cpp): the net object behind mcvd_inception_* and its 299 x 299 bilinear resize.  Its convs and
+// pools are the detector nets' shared ones (detector_ops.h).
 //
 // Workspace bound: images are processed in chunks of at most INCEPTION_CHUNK images.  The net always runs at 299 x 299 (resize_input, or
 // a 299 x 299 input), so a chunk of n images holds fixed-size maps: the 3 x 299 x 299 input (268 203 floats), two ping-pong maps for the
@@ -9,11 +9,10 @@
 // and grows only when a later call brings a larger chunk; the frame size only adds one 4.8 KB coordinate table per distinct H or W,
 // built on first sight.  A requested block output is written straight into the caller's buffer.
 #pragma once
-#include <map>
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "detector_ops.h"
 
 struct mcvd_ctx;
 
@@ -26,21 +25,7 @@ constexpr int INCEPTION_BLOCKS = 4;
 struct IncLayer { std::string name; int Cin, Cout, kh, kw, stride, ph, pw; };      // one BasicConv2d: conv (no bias) + BN(eps 0.001) + ReLU
 struct IncOp { int kind, layer, src, dst, c0, Csrc, Cdst, H, W, block; };         // H, W: the op's input map; c0: first channel of dst written
 
-// Rectangular conv as an implicit GEMM on v_mfma_f32_32x32x2_f32, pixels of all images flattened into the GEMM's N; the epilogue is
-// y[:, c0 + co] = relu?(fma(acc, alpha[co], beta[co])) into a tensor of Ctot channels.  Packed weights: wp[k * CoutP + co],
-// k = (ci * kh + ky) * kw + kx, K padded to a multiple of 32 and Cout to one of 64, zeros.  tab[k] = ci << 8 | ky << 4 | kx, -1 for k >= K.
-int conv_rect_kp(int Cin, int kh, int kw);
-int conv_rect_coutp(int Cout);
-void conv_rect_table(int Cin, int kh, int kw, std::vector<int>& tab);      // conv_rect_kp entries
-int launch_pack_conv_rect(const float* w, float* wp, int Cout, int K, hipStream_t s);      // wp: conv_rect_kp * conv_rect_coutp floats
-int launch_conv_rect(const float* x, const float* wp, const int* tab, const float* alpha, const float* beta, float* y, int N, int Cin, int H,
-                     int W, int Cout, int kh, int kw, int stride, int ph, int pw, int relu, int c0, int Ctot, hipStream_t s);
-// 3 x 3, stride 1, padding 1 over [NC, H, W] planes.  mode 0: F.avg_pool2d(count_include_pad=False) (fp64 sum in window order, divided by
-// the 4 / 6 / 9 values inside the map, rounded once); mode 1: F.max_pool2d.
-int launch_pool3(const float* x, float* y, long long NC, int H, int W, int mode, hipStream_t s);
-// y[i] = (float)(sum of x[i][0 .. HW) in fp64, in index order, / HW)
-int launch_global_avg(const float* x, float* y, long long NC, int HW, hipStream_t s);
-// One axis of F.interpolate(mode='bilinear', align_corners=False) from S to 299 with torch's coordinate rule (fvd_axis_table's):
+// One axis of F.interpolate(mode='bilinear', align_corners=False) from S to 299 (bilinear_axis_table, detector_ops.h):
 // tab = i0 [299] | i1 [299] | l0 [299] | l1 [299] (the weights as fp32 bit patterns)
 void inception_axis_table(int S, std::vector<int>& tab);
 // y [n, 3, 299, 299] = (normalize ? 2 v - 1 : v), v = the bilinear resize of x [n, 3, H, W]; tab_h / tab_w: device tables of H and W
@@ -55,11 +40,10 @@ struct mcvd_inception {
     bool finalized = false;
     std::vector<std::vector<float>> w, bn_w, bn_b, bn_m, bn_v;      // host copies until finalize, one per layer
     float* params = nullptr;                                        // device: packed weights, alpha, beta, tap tables
-    std::vector<float*> wp, alpha, beta;
-    std::vector<int*> tab;
+    std::vector<mcvd::ConvParams> conv;
     float* ws = nullptr;                                            // chunk workspace (see the bound above)
-    int ws_images = 0;
-    std::map<int, int*> axis;                                       // input length -> device coordinate table
+    size_t ws_bytes = 0;
+    mcvd::TableCache axis;                                          // input length -> device coordinate table
     mcvd_inception();
     ~mcvd_inception();
 };

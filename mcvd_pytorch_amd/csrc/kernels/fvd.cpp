@@ -4,8 +4,7 @@
 //   selection, to_i3d (grey repeated to RGB, BTCHW -> BCTHW; runners/ncsn_runner.py:1918-1982) and preprocess_single (models/fvd/fvd.py:160-186)
 //   for square frames: F.interpolate(mode='bilinear', align_corners=False) to 224 x 224 (the centre crop is then the identity) and
 //   (v - 0.5) * 2.  Per-axis tables (two source indices and two fp32 weights per output position) come from the host with torch's
-//   coordinate rule: src = fl32(scale32 * (d + 0.5) - 0.5) with ONE rounding, scale32 = fl32(S / 224); max(src, 0); i0 = floor(src);
-//   i1 = min(i0 + 1, S - 1); l1 = src - i0 in fp32; l0 = 1 - l1.  The lerp has torch's order, every operation rounded separately:
+//   coordinate rule (bilinear_axis_table, detector_ops.h).  The lerp has torch's order, every operation rounded separately:
 //   h0 * (w0 * p00 + w1 * p01) + h1 * (w0 * p10 + w1 * p11).  One thread per four consecutive output pixels (224 = 56 * 4), float4 stores;
 //   a grey value is computed once and stored to the three channel planes.
 //
@@ -14,7 +13,7 @@
 //   sum has a fixed order and the chunk partials are added in index order: bit-identical run to run.  The centred product runs on
 //   v_mfma_f64_16x16x4_f64, one wave per (16 x 16 tile of the lower triangle, chunk); the upper triangle is the mirror of the lower, so
 //   sigma is exactly symmetric.
-#include "../common.h"
+#include "../detector_ops.h"
 
 namespace mcvd {
 namespace {
@@ -180,23 +179,6 @@ int fs_chunks(int n, int d) {
 
 }  // namespace
 
-int fvd_axis_table(int S, unsigned short* i0, unsigned short* i1, float* l0, float* l1) {
-    const float scale = (float)S / (float)FV_OUT;                  // area_pixel_compute_scale: fl32(S / 224)
-    for (int dpos = 0; dpos < FV_OUT; ++dpos) {
-        // scale * (d + 0.5) is exact in double (24 x 9 bits) and so is the subtraction: ONE rounding, the fused multiply-subtract's value
-        float src = (float)((double)scale * ((double)dpos + 0.5) - 0.5);
-        if (src < 0.0f) src = 0.0f;
-        int a = (int)src;                                          // floor: src >= 0
-        if (a > S - 1) a = S - 1;
-        const float lam = src - (float)a;
-        i0[dpos] = (unsigned short)a;
-        i1[dpos] = (unsigned short)(a + 1 < S ? a + 1 : S - 1);
-        l1[dpos] = lam;
-        l0[dpos] = 1.0f - lam;
-    }
-    return 0;
-}
-
 int launch_fvd_clips(const float* const* parts, const int* frames, const int64_t* bstride, int nparts, int Bsel, int row_start, int row_step,
                      int C, int S, float* out, hipStream_t s) {
     MCVD_REQUIRE(parts && frames && bstride && out, "fvd_clips: NULL argument");
@@ -222,7 +204,12 @@ int launch_fvd_clips(const float* const* parts, const int* frames, const int64_t
     }
     p.nparts = nparts;
     FvdTable tab;
-    fvd_axis_table(S, tab.i0, tab.i1, tab.l0, tab.l1);
+    int i0[FV_OUT], i1[FV_OUT];
+    bilinear_axis_table(S, FV_OUT, i0, i1, tab.l0, tab.l1);
+    for (int d = 0; d < FV_OUT; ++d) {      // S <= 32768: the indices fit 16 bits
+        tab.i0[d] = (unsigned short)i0[d];
+        tab.i1[d] = (unsigned short)i1[d];
+    }
     const int64_t total = (int64_t)Bsel * (C == 3 ? 3 : 1) * T * FV_OUT * FV_Q;
     const int64_t blocks = (total + FV_THREADS - 1) / FV_THREADS;
     MCVD_REQUIRE(blocks < (1LL << 31), "fvd_clips: %lld workgroups exceed one launch", (long long)blocks);

@@ -1,4 +1,5 @@
-// LPIPS v0.1 on the AlexNet feature stack (kernels/lpips.cpp): the net object behind mcvd_lpips_* and the general strided conv.
+// LPIPS v0.1 on the AlexNet feature stack (kernels/lpips.cpp): the net object behind mcvd_lpips_*.  Its convs and pools are the detector
+// nets' shared ones (detector_ops.h).
 //
 // Workspace bound: frames are processed in chunks of at most LPIPS_CHUNK frames.  A chunk of n frames holds, for its 2 n images, the
 // normalised 3 x 128 x 128 input and the five taps with the two pooled maps between them: 443 136 floats (1.77 MB) per frame, plus
@@ -6,11 +7,10 @@
 // 114 MB + 64 * 256 * C * H bytes, whatever B * T is.  It is allocated on the first call (for min(B * T, LPIPS_CHUNK) frames) and grows
 // only when a later call brings a larger chunk or taller frames; the resize tables are built once per input size.
 #pragma once
-#include <map>
 #include <string>
 #include <vector>
 
-#include "common.h"
+#include "detector_ops.h"
 
 struct mcvd_ctx;
 
@@ -23,29 +23,21 @@ constexpr int LPIPS_TAPS = 5;
 struct LpipsLayer { int feat, slice, Cin, Cout, ks, stride, pad, H, OH, pool; };      // pool: MaxPool2d(3, 2) in front (H is the conv's input size)
 extern const LpipsLayer LPIPS_LAYERS[LPIPS_TAPS];
 
-// general conv as an implicit GEMM on v_mfma_f32_32x32x2_f32: any kernel size, stride and zero padding, M = images x output pixels
-// flattened.  Packed weights: wp[k * CoutP + co], k = (ci * ks + ky) * ks + kx, K padded to a multiple of 16 and Cout to one of 64, zeros.
-int conv_gemm_kp(int Cin, int ks);
-int conv_gemm_coutp(int Cout);
-int launch_pack_conv_gemm(const float* w, float* wp, int Cout, int Cin, int ks, hipStream_t s);      // wp: conv_gemm_kp * conv_gemm_coutp floats
-int launch_conv_gemm(const float* x, const float* wp, const float* bias, float* y, int N, int Cin, int H, int W, int Cout, int ks, int stride,
-                     int pad, int relu, hipStream_t s);
-int launch_maxpool3s2(const float* x, float* y, long long NC, int H, int W, hipStream_t s);
-
 }  // namespace mcvd
 
 struct mcvd_lpips {
     mcvd_ctx* ctx = nullptr;
     bool finalized = false;
     std::vector<float> w[mcvd::LPIPS_TAPS], b[mcvd::LPIPS_TAPS], lin[mcvd::LPIPS_TAPS], shift, scale;      // host copies until finalize
-    float* params = nullptr;                                     // device: packed weights, biases, lin vectors
-    float *wp[mcvd::LPIPS_TAPS] = {}, *bias[mcvd::LPIPS_TAPS] = {}, *lind[mcvd::LPIPS_TAPS] = {};
+    float* params = nullptr;                                     // device: packed weights, biases (the convs' beta), tap tables, lin vectors
+    mcvd::ConvParams conv[mcvd::LPIPS_TAPS];
+    float* lind[mcvd::LPIPS_TAPS] = {};
     float sh[3] = {}, sc[3] = {};
     float* ws = nullptr;                                         // chunk workspace (see the bound above)
-    int ws_frames = 0;
+    size_t ws_bytes = 0;
     unsigned char* rows = nullptr;                               // uint8 result of the horizontal resize pass
     size_t rows_bytes = 0;
-    std::map<int, std::pair<int*, int>> tabs;                    // input size -> (device table: first tap | tap count | coefficients, taps per output)
+    mcvd::TableCache tabs;                                       // input size -> (device table: first tap | tap count | coefficients, taps per output)
     ~mcvd_lpips();
 };
 

@@ -150,20 +150,18 @@ def summarize(vid_mse, vid_ssim, preds_per_test=1, suffix=""):
 _LPIPS_CONVS = ((0, "slice1"), (3, "slice2"), (6, "slice3"), (8, "slice4"), (10, "slice5"))
 
 
-class LpipsNet:
-    """The reference's eval_models.PerceptualLoss(model='net-lin', net='alex') (version 0.1, eval mode) on the device.
+class _DeviceNet:
+    """What LpipsNet and FidInception share: a net object of the library (mcvd_<_KIND>_create / _set_param / _finalize / _destroy) on a
+    scorenet's context and stream, or on this module's own context."""
+    _KIND = None
 
-        net = LpipsNet(scorenet=hipnet)                       # or LpipsNet(device="cuda:0")
-        net.load_backbone(torchvision_alexnet_state_dict)     # keys features.N.weight / bias; classifier keys are ignored
-        net.load_linear("weights/v0.1/alex.pth")              # the reference's lin layers (path or state dict)
-        # or net.load_state_dict(pnetlin.state_dict()) for a whole PNetLin dict
-
-    Runs on the scorenet's context and stream when given one, else on this module's own context (as frame_metrics).  Missing weights are
-    an error at the first use (MCVD_ESTATE names the tensor)."""
+    @classmethod
+    def _require_gpu(cls):
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{cls.__name__} needs a ROCm GPU (MI355X); there is no CPU fallback")
 
     def __init__(self, device=None, scorenet=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("LpipsNet needs a ROCm GPU (MI355X); there is no CPU fallback")
+        self._require_gpu()
         self.scorenet = scorenet
         if scorenet is not None:
             self.device = scorenet.device
@@ -173,10 +171,7 @@ class LpipsNet:
         self._net = C.c_void_p()
         self._final = False
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib.mcvd_lpips_create(self._ctx(), C.byref(self._net)), "lpips_create")
-        # ScalingLayer (models/networks_basic.py:93-94): constants of the architecture, not learned weights
-        self._set("scaling_layer.shift", torch.tensor([-.030, -.088, -.188]))
-        self._set("scaling_layer.scale", torch.tensor([.458, .448, .450]))
+            _lib.check(getattr(_lib.lib, f"mcvd_{self._KIND}_create")(self._ctx(), C.byref(self._net)), f"{self._KIND}_create")
 
     def _ctx(self):
         if self.scorenet is not None:
@@ -187,8 +182,45 @@ class LpipsNet:
     def _set(self, name, t):
         t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
         shape = (C.c_int64 * t.dim())(*t.shape)
-        _lib.check(_lib.lib.mcvd_lpips_set_param(self._net, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), 0), f"lpips_set_param({name})")
+        _lib.check(getattr(_lib.lib, f"mcvd_{self._KIND}_set_param")(self._net, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), 0),
+                   f"{self._KIND}_set_param({name})")
         self._final = False
+
+    def finalize(self):
+        if not self._final:
+            with torch.cuda.device(self.device):
+                self._ctx()
+                _lib.check(getattr(_lib.lib, f"mcvd_{self._KIND}_finalize")(self._net), f"{self._KIND}_finalize")
+            self._final = True
+        return self
+
+    def __del__(self):
+        try:
+            if getattr(self, "_net", None):
+                getattr(_lib.lib, f"mcvd_{self._KIND}_destroy")(self._net)
+                self._net = None
+        except Exception:
+            pass
+
+
+class LpipsNet(_DeviceNet):
+    """The reference's eval_models.PerceptualLoss(model='net-lin', net='alex') (version 0.1, eval mode) on the device.
+
+        net = LpipsNet(scorenet=hipnet)                       # or LpipsNet(device="cuda:0")
+        net.load_backbone(torchvision_alexnet_state_dict)     # keys features.N.weight / bias; classifier keys are ignored
+        net.load_linear("weights/v0.1/alex.pth")              # the reference's lin layers (path or state dict)
+        # or net.load_state_dict(pnetlin.state_dict()) for a whole PNetLin dict
+
+    Runs on the scorenet's context and stream when given one, else on this module's own context (as frame_metrics).  Missing weights are
+    an error at the first use (MCVD_ESTATE names the tensor)."""
+
+    _KIND = "lpips"
+
+    def __init__(self, device=None, scorenet=None):
+        super().__init__(device, scorenet)
+        # ScalingLayer (models/networks_basic.py:93-94): constants of the architecture, not learned weights
+        self._set("scaling_layer.shift", torch.tensor([-.030, -.088, -.188]))
+        self._set("scaling_layer.scale", torch.tensor([.458, .448, .450]))
 
     def load_backbone(self, state_dict):
         for idx, _ in _LPIPS_CONVS:
@@ -211,22 +243,6 @@ class LpipsNet:
         for name, t in sd.items():
             self._set(name, t)
         return self
-
-    def finalize(self):
-        if not self._final:
-            with torch.cuda.device(self.device):
-                self._ctx()
-                _lib.check(_lib.lib.mcvd_lpips_finalize(self._net), "lpips_finalize")
-            self._final = True
-        return self
-
-    def __del__(self):
-        try:
-            if getattr(self, "_net", None):
-                _lib.lib.mcvd_lpips_destroy(self._net)
-                self._net = None
-        except Exception:
-            pass
 
 
 @torch.no_grad()
@@ -839,7 +855,7 @@ del _n, _co, _ci, _kh, _kw, _k
 _FID_BLOCK_SHAPES = ((64, 73, 73), (192, 35, 35), (768, 17, 17), (2048, 1, 1))
 
 
-class FidInception:
+class FidInception(_DeviceNet):
     """The reference's evaluation.inception.InceptionV3(output_blocks, resize_input, normalize_input) -- the FID variant
     (use_fid_inception=True), eval mode, no gradients -- on the device, as a `detector=` for fid_pr, fast_fid and NearestNeighbors:
 
@@ -852,36 +868,15 @@ class FidInception:
     when given one, else on this module's own context (as LpipsNet).  Missing weights are an error at the first use (MCVD_ESTATE names
     the tensor).  There is no CPU fallback."""
 
+    _KIND = "inception"
+
     def __init__(self, output_blocks=(3,), resize_input=True, normalize_input=True, device=None, scorenet=None):
-        if not torch.cuda.is_available():
-            raise RuntimeError("FidInception needs a ROCm GPU (MI355X); there is no CPU fallback")
+        self._require_gpu()      # the order of the errors: no GPU, then bad arguments, before anything is created
         blocks = sorted(set(int(b) for b in output_blocks))
         if not blocks or blocks[0] < 0 or blocks[-1] > 3:
             raise ValueError(f"FidInception: output_blocks {tuple(output_blocks)} must be a non-empty subset of 0..3")
         self.output_blocks, self.resize_input, self.normalize_input = blocks, bool(resize_input), bool(normalize_input)
-        self.scorenet = scorenet
-        if scorenet is not None:
-            self.device = scorenet.device
-        else:
-            dev = torch.device(device if device is not None else "cuda")
-            self.device = torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
-        self._net = C.c_void_p()
-        self._final = False
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib.mcvd_inception_create(self._ctx(), C.byref(self._net)), "inception_create")
-
-    def _ctx(self):
-        if self.scorenet is not None:
-            self.scorenet._bind_stream()
-            return self.scorenet._ctx
-        return _package_ctx(self.device)
-
-    def _set(self, name, t):
-        t = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
-        shape = (C.c_int64 * t.dim())(*t.shape)
-        _lib.check(_lib.lib.mcvd_inception_set_param(self._net, name.encode(), C.c_void_p(t.data_ptr()), shape, t.dim(), 0),
-                   f"inception_set_param({name})")
-        self._final = False
+        super().__init__(device, scorenet)
 
     def load_state_dict(self, sd_or_path):
         """The reference's pt_inception-2015-12-05-6726825d.pth (path or dict): `X.conv.weight`, `X.bn.weight|bias|running_mean|running_var`.
@@ -899,14 +894,6 @@ class FidInception:
             if tuple(t.shape) != want:
                 raise ValueError(f"FidInception.load_state_dict: {name} has shape {tuple(t.shape)}, expected {want}")
             self._set(name, t)
-        return self
-
-    def finalize(self):
-        if not self._final:
-            with torch.cuda.device(self.device):
-                self._ctx()
-                _lib.check(_lib.lib.mcvd_inception_finalize(self._net), "inception_finalize")
-            self._final = True
         return self
 
     @torch.no_grad()
@@ -934,14 +921,6 @@ class FidInception:
             _lib.check(_lib.lib.mcvd_inception_forward(self._net, C.c_void_p(x.data_ptr()), n, H, W, int(self.resize_input),
                                                        int(self.normalize_input), mask, *ptrs), "inception_forward")
         return [outs[b] for b in self.output_blocks]
-
-    def __del__(self):
-        try:
-            if getattr(self, "_net", None):
-                _lib.lib.mcvd_inception_destroy(self._net)
-                self._net = None
-        except Exception:
-            pass
 
 
 # ---- nearest neighbours of samples in a data set (evaluation/nearest_neighbor.py) -----------------------------------------------------------

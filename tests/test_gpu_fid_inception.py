@@ -1,5 +1,5 @@
-"""GPU: the FID InceptionV3 on the device -- mcvd_inception_*, mcvd_op_conv2d_rect, mcvd_op_pool3, mcvd_op_global_avg, mcvd_op_resize299
-(kernels/inception.cpp) and metrics.FidInception -- against fp64 torch, against tests/inception_ref.py (the fp64 restatement) and against
+"""GPU: the FID InceptionV3 on the device -- mcvd_inception_* and mcvd_op_resize299 (kernels/inception.cpp), mcvd_op_conv2d_rect,
+mcvd_op_pool3 and mcvd_op_global_avg (the detector nets' shared ops, kernels/detector_ops.cpp) and metrics.FidInception -- against fp64 torch, against tests/inception_ref.py (the fp64 restatement) and against
 what the REAL evaluation.inception.InceptionV3 computed over the seeded weights (fixture fid_inception.pt; tests/test_fid_inception_cpu.py).
 
 Gates (none is a figure of the code under test):

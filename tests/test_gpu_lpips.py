@@ -1,4 +1,5 @@
-"""GPU: LPIPS on the device -- mcvd_lpips_* and mcvd_op_conv2d_strided (kernels/lpips.cpp) through the C ABI -- against tests/lpips_ref.py
+"""GPU: LPIPS on the device -- mcvd_lpips_* (kernels/lpips.cpp) and mcvd_op_conv2d_strided (the detector nets' one conv,
+kernels/detector_ops.cpp) through the C ABI -- against tests/lpips_ref.py
 (the integer resize and the fp64 restatement) and against what the REAL PerceptualLoss / NCSNRunner.video_gen computed over the seeded
 backbone (fixtures lpips_direct.pt, lpips_runner_*.pt; cases in tests/test_lpips_cpu.py).
 
@@ -12,7 +13,8 @@ Gates:
     the frame values and are held to the same relative gate (conf95 = 1.96 sem moves by at most twice the per-video bound);
   * mcvd_op_conv2d_strided against F.conv2d in fp64: |y - y64| <= min((K + 2) 2^-24, 2e-6) x conv(|x|, |w|) + |bias| per element -- the
     fp32 bound of a K-term fma chain plus the bias add and the final rounding, capped by the 2e-6 this repository holds its other fp32
-    convs to (test_conv_bf16x3_is_fp32_accurate).
+    convs to (test_conv_bf16x3_is_fp32_accurate);
+  * mcvd_op_conv2d_strided against mcvd_op_conv2d_rect without alpha: equal (one kernel; a bias add is its fma epilogue with alpha absent).
 Measured ratios are printed by every test.
 """
 import ctypes as C
@@ -80,10 +82,12 @@ def test_every_frame_of_the_direct_fixture(golden_dir):
 
 
 SHAPES = [(4, 3, 128, 128, 64, 11, 4, 2), (4, 64, 15, 15, 192, 5, 1, 2), (6, 192, 7, 7, 384, 3, 1, 1), (6, 384, 7, 7, 256, 3, 1, 1),
-          (6, 256, 7, 7, 256, 3, 1, 1), (2, 5, 37, 29, 70, 7, 3, 2), (3, 17, 20, 33, 33, 1, 2, 0), (1, 8, 9, 9, 8, 3, 1, 1), (5, 6, 11, 13, 100, 5, 2, 4)]
+          (6, 256, 7, 7, 256, 3, 1, 1), (2, 5, 37, 29, 70, 7, 3, 2), (3, 17, 20, 33, 33, 1, 2, 0), (1, 8, 9, 9, 8, 3, 1, 1), (5, 6, 11, 13, 100, 5, 2, 4),
+          (1, 2, 20, 20, 8, 17, 1, 8)]      # the last: 17 taps per side, beyond the 4 bits a tap once had in the conv's table
+IDS = ["alex1", "alex2", "alex3", "alex4", "alex5", "k7s3", "k1s2", "b1", "k5s2p4", "k17"]
 
 
-@pytest.mark.parametrize("shape", SHAPES, ids=["alex1", "alex2", "alex3", "alex4", "alex5", "k7s3", "k1s2", "b1", "k5s2p4"])
+@pytest.mark.parametrize("shape", SHAPES, ids=IDS)
 def test_conv2d_strided_against_fp64(shape):
     B, Cin, H, W, Cout, ks, stride, pad = shape
     from mcvd_pytorch_amd import _lib
@@ -105,6 +109,28 @@ def test_conv2d_strided_against_fp64(shape):
         bound = min((K + 2) * 2.0 ** -24, 2e-6)
         print(f"  conv {shape} relu {relu} bias {b is not None}: max err / conv(|x|,|w|) {err:.3e} (bound {bound:.3e})")
         assert torch.isfinite(y).all() and err <= bound
+
+
+@pytest.mark.parametrize("name", ["b1", "k1s2", "alex1"])
+def test_conv2d_strided_is_conv2d_rect_without_alpha(name):
+    """The two ops are one kernel: op_conv2d_strided(x, w, bias, relu) equals op_conv2d_rect(x, w, alpha=None, beta=bias, kh = kw = ks,
+    ph = pw = pad, relu, c0 = 0, Ctot = Cout) -- a bias add is the fma epilogue with alpha absent.  b1: one image, less than one tile in
+    every dimension; k1s2: a 1 x 1 kernel that must not take the plain-load path; alex1: 11 taps per side."""
+    B, Cin, H, W, Cout, ks, stride, pad = SHAPES[IDS.index(name)]
+    from mcvd_pytorch_amd import _lib
+    ctx = Ctx()
+    gen = torch.Generator().manual_seed(Cin * 100 + ks)
+    x = torch.randn(B, Cin, H, W, generator=gen).cuda()
+    w = (torch.randn(Cout, Cin, ks, ks, generator=gen) / (Cin * ks * ks) ** 0.5).cuda()
+    bias = (0.1 * torch.randn(Cout, generator=gen)).cuda()
+    OH, OW = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    for relu in (0, 1):
+        a = torch.full((B, Cout, OH, OW), float("nan"), device="cuda")
+        b = torch.full((B, Cout, OH, OW), float("nan"), device="cuda")
+        _lib.check(_lib.lib.mcvd_op_conv2d_strided(ctx.h, P(x), P(w), P(bias), B, Cin, H, W, Cout, ks, stride, pad, relu, P(a)), "conv2d_strided")
+        _lib.check(_lib.lib.mcvd_op_conv2d_rect(ctx.h, P(x), P(w), None, P(bias), B, Cin, H, W, Cout, ks, ks, stride, pad, pad, relu, P(b), 0, Cout),
+                   "conv2d_rect")
+        assert torch.isfinite(a).all() and torch.equal(a, b), (name, relu)
 
 
 def test_tap_tensors_of_the_two_stored_images(golden_dir):
