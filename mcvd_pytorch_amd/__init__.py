@@ -10,7 +10,8 @@ from .samplers import ddim_sampler, ddpm_sampler, fpndm_sampler, get_sampler  # 
 from .scorenet import HipScoreNet, get_model  # noqa: F401
 from .checkpoint import load_model, load_states_into  # noqa: F401
 from .runner import (conditioning_fn, data_transform, evaluate_video_gen, fast_fid, frames_to_uint8, inverse_data_transform,  # noqa: F401
-                     nearest_neighbors, save_video_pred, task_conditioning, test_checkpoints, video_gen, video_gen_aliases, video_tasks)
+                     nearest_neighbors, sample, save_video_pred, stretch_image, task_conditioning, test_checkpoints, video_gen, video_gen_aliases,
+                     video_tasks)
 from .metrics import (FidInception, LpipsNet, NearestNeighbors, VideoMetrics, feature_stats, fid_from_features, fid_from_stats, fid_pr, frame_lpips,  # noqa: F401
                       frame_metrics, frechet_distance, fvd_clips, fvd_gates, knn_radii, knn_search, manifold_hits, precision_recall, video_lpips)
 from .losses import anneal_dsm_score_estimation  # noqa: F401
@@ -21,4 +22,4 @@ __all__ = ["HipScoreNet", "get_model", "ddpm_sampler", "ddim_sampler", "fpndm_sa
            "frame_metrics", "VideoMetrics", "LpipsNet", "frame_lpips", "video_lpips", "anneal_dsm_score_estimation", "test_checkpoints",
            "fvd_gates", "fvd_clips", "feature_stats", "frechet_distance", "knn_radii", "manifold_hits", "precision_recall",
            "fid_from_features", "fid_from_stats", "fid_pr", "fast_fid", "knn_search", "FidInception",
-           "NearestNeighbors", "nearest_neighbors", "evaluate_video_gen", "video_gen_aliases"]
+           "NearestNeighbors", "nearest_neighbors", "evaluate_video_gen", "video_gen_aliases", "sample", "stretch_image"]

@@ -824,6 +824,269 @@ def fast_fid(config, scorenet, real, detector=None, cond_batches=None, ckpts=Non
     return out
 
 
+def stretch_image(X, ch, imsize):
+    """[B, T*ch, imsize, imsize] -> [B, ch, imsize, T*imsize]: the frames of each row side by side, left to right (stretch_image,
+    runners/ncsn_runner.py:150-151).  Reshapes and permutes only, on the device X is on."""
+    return X.reshape(len(X), -1, ch, imsize, imsize).permute(0, 2, 1, 4, 3).reshape(len(X), ch, -1, imsize).permute(0, 1, 3, 2)
+
+
+@torch.no_grad()
+def sample(config, scorenet, batches=None, *, cond_batches=None, ckpt_dir=None, real=None, detector=None, out_dir=None, sampler=None,
+           init_noise_fn=None, seed=None, shard=None, log=None):
+    """NCSNRunner.sample() (runners/ncsn_runner.py:914-1301), the mode `main.py --sample` runs, as one call, up to the tensors the reference
+    hands to make_grid and torch.save.  Returns a dict where the reference returns None; frames stay on the device (the `.to('cpu')` of
+    :1142 and :1273 is not reproduced).
+
+      * checkpoint (:915-932): ckpt = "latest" when sampling.ckpt_id is None, else the id.  With `ckpt_dir`, checkpoint.pt or
+        checkpoint_{ckpt}.pt is loaded through checkpoint.load_states_into: states[0] ('module.' keys), then with model.ema the EMA shadow
+        states[-1].  Without `ckpt_dir` the net is used as it is;
+      * batches: any iterable of `x` or `(x, _)`, x [B, T, C, S, S] in [0, 1] with B = sampling.batch_size: the caller's loader (the
+        reference builds it with shuffle=True; the order is the caller's).  Another batch length is a ValueError (the reference
+        mis-shapes its sampler call);
+      * plain branch (`not sampling.fid`, :1096-1188): with data_init or a conditional config one batch goes through data_transform and
+        conditioning_fn(num_frames_pred=data.num_frames).  z is torch.randn on the device, under model.gamma the centred variate
+        Gamma(k_cum[0], rate 1 / theta_t[0]) - k_cum[0] theta_t[0] drawn as video_gen and fast_fid draw it; `init_noise_fn(0, shape,
+        device)` replaces z.  Under sampling.data_init the sampler starts from sqrt(alphas[0]) real + sqrt(1 - alphas[0]) z.  The sampler
+        call carries the kwargs of :1135-1142 -- cond, cond_mask, n_steps_each, step_lr, verbose=True, final_only, denoise,
+        subsample_steps, clip_before, log=True, gamma -- and, without final_only, steps_on_device=True;
+      * the result: 'ckpt'; with final_only 'samples' = stretch_image(inverse_data_transform(frames [B, C nf, S, S])), else 'steps', the
+        same of every step image in order; 'nrow' (:1156, :1170).  A conditional config adds (:1175-1188) the stretched 'real' and
+        'cond' ('futr' too with future frames, split off cond at num_frames_cond C channels), 'padding' = 0.5 ones(B, C, S, 2),
+        'full_row' = cat([cond, padding, real, padding, sample(, futr)], -1) -- the tensor the reference hands to make_grid, where
+        `sample` is the last step's image -- and 'nrow_full' (:1183);
+      * FID branch (`sampling.fid`, :1190-1301): n_rounds = num_samples4fid // batch_size rounds.  Each draws z (`init_noise_fn(round,
+        shape, device)`); under data_init takes the next batch of `batches`, started over when it runs out, and mixes it in, its cond
+        serving as cond (:1244); otherwise a conditional config takes the next batch of `cond_batches`, started over likewise; calls the
+        sampler with verbose=False, log=True; inverse_data_transform.  The rounds are concatenated on the device to 'samples'
+        [n_rounds B, C nf, S, S] -- not reshaped to (-1, C, S, S) as fast_fid does -- and scored with metrics.fid_pr(real, samples,
+        detector, k=fast_fid.pr_nn_k), `real` and `detector` as in fast_fid -> {'ckpt', 'fids': {ckpt: v}, 'precisions': {ckpt: v},
+        'recalls': {ckpt: v}, 'samples'}.  `log` (default logging.info) receives the reference's "ckpt: ..., fid: ..." line;
+      * out_dir: what the reference torch.save()s, as CPU tensors -- samples_{ckpt}.pt, or samples_{i:04d}.pt per step, and under a
+        conditional config samples_full_{ckpt}.pt (the same `sample`, :1188); in the FID branch samples_{ckpt}.pt.  'files' lists the
+        names in the order written.  No PNG, no make_grid, no pickles and no YAML.
+
+    Noise.  Without `seed=` the init z is as above and the step noise the samplers' own.  With `seed=` both are Philox streams keyed by
+    the GLOBAL row, as in evaluate_video_gen: the init z is mcvd_randn's layout at the draw word INIT_NOISE_DRAW, the step noise the
+    samplers' `seed` / `sample_offset` stream; the plain branch runs under `seed`, FID round i under seed + (i << 20).
+
+    Sharding.  shard=(rank, world): the rank takes the rows dist.shard_rows(B, rank, world) of every batch and of z (`init_noise_fn` is
+    then asked for the rank's shape) and hands the first of them to the samplers as sample_offset.  It needs `seed=` and, under
+    model.gamma, an `init_noise_fn` (ValueError otherwise).  The rank returns its rows and 'shard': (rank, world); no collective is
+    made, nothing is scored and no file is written: the caller concatenates -- in the FID branch round by round, a rank's 'samples'
+    holding its rows of round 0, then of round 1, ... ('rounds' says how many).
+
+    Defects of the reference that are documented and not reproduced: `cond_mask` is unbound at :1135 for an unconditional config without
+    data_init -- None is passed; model.gamma with data_init reads an undefined `used_alphas` (:1127, :1250) -- refused, as video_gen
+    refuses :1496; :1147 reshapes a step image to (B, C, S, S), which raises for data.num_frames > 1 -- reshaped to C nf, as :1162 does;
+    the FID branch stops with a NameError at :1285 (`precisions` and `recalls` are never defined) -- here they are filled; its sampler
+    call omits final_only, so every step goes to the CPU and only the last is used -- final_only=True is passed.  sampling.inpainting
+    and sampling.interpolation call the Langevin samplers with `sigmas`, which is commented out at :934-935: both raise
+    NotImplementedError, and so does model.version SMLD."""
+    import logging
+    import os
+    from math import sqrt
+    from . import metrics
+    from .checkpoint import load_states_into
+    from .dist import shard_rows
+    log = log or logging.info
+    d, s, m = config.data, config.sampling, config.model
+    if str(getattr(m, "version", "DDPM")).upper() == "SMLD":
+        raise NotImplementedError("sample with model.version SMLD is not on the HIP path (DESIGN.md section 8)")
+    fid = bool(getattr(s, "fid", False))
+    if not fid and getattr(s, "inpainting", False):
+        raise NotImplementedError("sampling.inpainting: the reference calls anneal_Langevin_dynamics_inpainting, a Langevin sampler of the "
+                                  "SMLD nets (:979), which is not on the HIP path (DESIGN.md section 8)")
+    if not fid and getattr(s, "interpolation", False):
+        raise NotImplementedError("sampling.interpolation: the reference calls anneal_Langevin_dynamics_interpolation, a Langevin sampler of "
+                                  "the SMLD nets (:1060), which is not on the HIP path (DESIGN.md section 8)")
+    gamma = bool(getattr(m, "gamma", False))
+    data_init = bool(getattr(s, "data_init", False))
+    if gamma and data_init:
+        raise NameError("name 'used_alphas' is not defined (runners/ncsn_runner.py:1127, :1250: the reference cannot run model.gamma with "
+                        "sampling.data_init; refused here as well)")
+    rank, world = (0, 1) if shard is None else (int(shard[0]), int(shard[1]))
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"sample: shard = {shard!r} is not (rank, world) with 0 <= rank < world")
+    if world > 1 and seed is None:
+        raise ValueError("sample: a sharded run needs seed= (the Philox streams are keyed by the global row; torch's generator is not)")
+    if world > 1 and gamma and init_noise_fn is None:
+        raise ValueError("sample: a sharded run of a model.gamma config needs init_noise_fn (the default gamma init is drawn from torch's "
+                         "CPU generator, which is not row-keyed)")
+    conditional = d.num_frames_cond > 0                               # :950
+    future = getattr(d, "num_frames_future", 0)                       # :954
+    B = int(s.batch_size)
+    if B < 1:
+        raise ValueError(f"sample: sampling.batch_size must be at least 1, got {B}")
+    if fid:
+        n_rounds = int(s.num_samples4fid) // B                        # :1191-1192
+        if n_rounds < 1:
+            raise ValueError(f"sample: sampling.num_samples4fid = {s.num_samples4fid} is smaller than sampling.batch_size = {B}: nothing "
+                             "would be sampled")
+        if data_init and batches is None:
+            raise ValueError("sample: sampling.fid with sampling.data_init: batches is needed")
+        if conditional and not data_init and cond_batches is None:
+            raise ValueError("sample: sampling.fid with data.num_frames_cond > 0: cond_batches is needed")
+        if world == 1 and real is None:
+            raise ValueError("sample: sampling.fid: `real` is needed (the data set's features, a .pt / .pth path of them, or images)")
+    elif (data_init or conditional) and batches is None:
+        raise ValueError("sample: sampling.data_init or data.num_frames_cond > 0: batches is needed")
+
+    ckpt = "latest" if getattr(s, "ckpt_id", None) is None else s.ckpt_id               # :915-921
+    net = scorenet.module if hasattr(scorenet, "module") else scorenet                   # :947
+    if ckpt_dir is not None:
+        name = "checkpoint.pt" if ckpt == "latest" else f"checkpoint_{ckpt}.pt"
+        states = torch.load(os.path.join(ckpt_dir, name), map_location="cpu", weights_only=False)
+        load_states_into(net, states, use_ema=bool(getattr(m, "ema", False)))          # :926-932
+    net.eval()                                                                           # :945
+    dev = net.device
+    C, nf, nc, S = d.channels, d.num_frames, d.num_frames_cond, d.image_size
+    begin, end = shard_rows(B, rank, world)
+    rows = end - begin
+    shape = (rows, C * nf, S, S)
+    run = sampler or get_sampler(config)
+
+    def loader(source, what):
+        """next() over `source`, started over when it runs out (:1235-1241, :1256-1262); every batch must hold B clips."""
+        it = [None]
+
+        def take():
+            for attempt in range(2):
+                if it[0] is None:
+                    it[0] = iter(source)
+                try:
+                    b = next(it[0])
+                    break
+                except StopIteration:
+                    it[0] = None
+            else:
+                raise ValueError(f"sample: {what} is empty")
+            x = b[0] if isinstance(b, (list, tuple)) else b
+            if len(x) != B:
+                raise ValueError(f"sample: a batch of {what} holds {len(x)} clips, sampling.batch_size is {B} (the reference's sampler call "
+                                 "would be mis-shaped)")
+            return data_transform(config, x.to(dev)[begin:end])
+        return take
+
+    def draw_z(i, call_seed):
+        if init_noise_fn is not None:
+            return init_noise_fn(i, shape, dev)
+        if gamma:                                                     # :1112-1115, :1225-1228, drawn as video_gen draws it
+            k0, th0 = float(net.k_cum[0]), float(net.theta_t[0])
+            g = torch.distributions.gamma.Gamma(torch.full(shape, k0), torch.full(shape, 1.0 / th0)).sample().to(dev)
+            return g - k0 * th0
+        if call_seed is not None:
+            return _philox_init(net, call_seed, begin, shape, dev)
+        return torch.randn(shape, device=dev)                         # :1117, :1230
+
+    def mixed(x0, z):                                                 # :1126-1128, :1249-1251
+        alpha = net.alphas[0]
+        return alpha.sqrt() * x0 + (1 - alpha).sqrt() * z
+
+    def noise_kw(call_seed):
+        return {} if call_seed is None else dict(seed=call_seed, sample_offset=begin)
+
+    common = dict(n_steps_each=s.n_steps_each, step_lr=s.step_lr, denoise=s.denoise, subsample_steps=getattr(s, "subsample", None),
+                  clip_before=getattr(s, "clip_before", True), log=True, gamma=gamma)
+    out = {"ckpt": ckpt}
+    if world > 1:
+        out["shard"] = (rank, world)
+    files = []
+
+    def stretched_01(frames):
+        """Network-range frames [n, C T, S, S] -> [0, 1] frames side by side (an empty shard has no rows to infer T from)."""
+        if len(frames) == 0:
+            return frames.new_zeros((0, C, S, frames.shape[1] // C * S))
+        return stretch_image(inverse_data_transform(config, frames), C, S)
+
+    def save(tensor, name):
+        if out_dir is not None and world == 1:
+            torch.save(tensor.detach().to("cpu"), os.path.join(out_dir, name))
+            files.append(name)
+
+    if not fid:                                                       # :1096-1188
+        x_real = cond = cond_mask = None
+        if data_init or conditional:                                  # :1098-1103
+            x_real, cond, cond_mask = conditioning_fn(config, loader(batches, "batches")(), num_frames_pred=nf, conditional=conditional)
+        call_seed = None if seed is None else int(seed)
+        z = draw_z(0, call_seed)
+        init = mixed(x_real, z) if data_init else z                   # :1121-1130
+        final_only = bool(s.final_only)
+        C_nf = C * nf
+        images = []
+        if rows > 0:                                                  # (an empty shard samples nothing)
+            extra = {} if final_only else dict(steps_on_device=True)
+            all_samples = run(init, scorenet, cond=cond, cond_mask=cond_mask, verbose=True, final_only=final_only, **common, **extra,
+                              **noise_kw(call_seed))                  # :1135-1142
+            images = [all_samples[-1]] if final_only else list(all_samples)
+        nrow = ceil(sqrt(nf * B) / nf)                                # :1156, :1170
+        stretched = []
+        for i, frames in enumerate(images):                           # :1145-1173
+            frames = frames.reshape(frames.shape[0], C_nf, S, S)      # :1162 (:1147 names C alone: see the docstring)
+            stretched.append(stretched_01(frames))
+            save(stretched[-1], f"samples_{ckpt}.pt" if final_only else "samples_{:04d}.pt".format(i))
+        if not stretched:
+            stretched = [torch.zeros((0, C, S, nf * S), device=dev)]
+        last = stretched[-1]
+        if final_only:
+            out["samples"] = last
+        else:
+            out["steps"] = stretched
+        out["nrow"] = nrow
+        if conditional:                                               # :1175-1188
+            real01 = stretched_01(x_real)
+            if future > 0:
+                cond, futr = torch.tensor_split(cond, (nc * C,), dim=1)
+                futr = stretched_01(futr)
+            cond01 = stretched_01(cond)
+            padding = 0.5 * torch.ones(len(real01), C, S, 2, device=dev)
+            width = nc + nf * 2 + future
+            out["real"], out["cond"] = real01, cond01
+            if future > 0:
+                out["futr"] = futr
+            out["padding"] = padding
+            out["full_row"] = torch.cat([cond01, padding, real01, padding, last] + ([futr] if future > 0 else []), dim=-1)
+            out["nrow_full"] = ceil(sqrt(width * B) / width)          # :1183
+            save(last, f"samples_full_{ckpt}.pt")                     # :1188 saves `sample`, not the full row
+        out["files"] = files
+        return out
+
+    # ---- FID branch (:1190-1301)
+    take_init = loader(batches, "batches") if data_init else None
+    take_cond = loader(cond_batches, "cond_batches") if (conditional and not data_init) else None
+    parts = []
+    for i in range(n_rounds):                                         # :1216
+        call_seed = None if seed is None else int(seed) + (i << _SEED_SHIFT)
+        z = draw_z(i, call_seed)
+        cond = None
+        if data_init:                                                 # :1234-1251
+            x_real, cond, _ = conditioning_fn(config, take_init(), num_frames_pred=nf, conditional=conditional)
+            init = mixed(x_real, z)
+        else:
+            init = z
+            if conditional:                                           # :1255-1265
+                _, cond, _ = conditioning_fn(config, take_cond(), num_frames_pred=nf, conditional=conditional)
+        if rows == 0:
+            parts.append(torch.zeros(shape, device=dev))
+            continue
+        all_samples = run(init, scorenet, cond=cond, verbose=False, final_only=True, **common, **noise_kw(call_seed))      # :1267-1273
+        final = all_samples[-1].reshape(all_samples[-1].shape[0], C * nf, S, S)                                           # :1275-1276
+        parts.append(inverse_data_transform(config, final))
+    gen_samples = torch.cat(parts, dim=0)                             # :1278
+    out["samples"] = gen_samples
+    if world > 1:
+        out["rounds"] = n_rounds
+        out["files"] = files
+        return out
+    k = config.fast_fid.pr_nn_k                                       # :1283
+    score_net = None if getattr(net, "plan_only", False) else net
+    fid_v, precision, recall = metrics.fid_pr(real, gen_samples, detector, k=k, scorenet=score_net)      # :1284
+    out["fids"], out["precisions"], out["recalls"] = {ckpt: fid_v}, {ckpt: precision}, {ckpt: recall}
+    log("ckpt: {}, fid: {}, precision: {}, recall: {}".format(ckpt, fid_v, precision, recall))           # :1286
+    save(gen_samples, f"samples_{ckpt}.pt")                           # :1301
+    out["files"] = files
+    return out
+
+
 def nearest_neighbors(samples, data_batches, detector, k=10, n_samples=10, out_path=None, scorenet=None):
     """The loop of get_nearest_neighbors (evaluation/nearest_neighbor.py:70-114): the `k` data images nearest, in the detector's feature
     space, to each of the first `n_samples` rows of `samples` (a tensor, or the path of fast_fid's samples_{ckpt}.pt) or to its mirrored

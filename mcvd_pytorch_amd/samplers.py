@@ -68,7 +68,7 @@ def _f(t):
 @torch.no_grad()
 def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False, denoise=True, subsample_steps=None,
             same_noise=False, noise_val=None, frac_steps=None, verbose=False, log=False, clip_before=True, t_min=-1,
-            gamma=False, noise=None, seed=None, sample_offset=0, cond_noise=None, **kwargs):
+            gamma=False, noise=None, seed=None, sample_offset=0, cond_noise=None, steps_on_device=False, **kwargs):
     net = _unwrap(scorenet)
     if gamma and not getattr(net, "gamma", False):
         raise AttributeError("'HipScoreNet' object has no attribute 'k_cum' (gamma=True needs a model.gamma net, models/__init__.py:224, :118)")
@@ -243,7 +243,7 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
             cn = _f(c_beta.sqrt()) if just_beta else _f(((1 - c_alpha_prev) / (1 - c_alpha) * c_beta).sqrt())   # :326/:328
         update(grad, None if split else z, c_x0a, c_x0b, c0, c1, 0.0 if split else cn)
         if not final_only:
-            images.append(x.to("cpu"))                                              # :292-293
+            images.append(x.clone() if steps_on_device else x.to("cpu"))            # :292-293
         if need_log:                                                                # :295-308
             g = -1 / (1 - c_alpha).sqrt().item() * grad
             grad_norm = torch.norm(g.reshape(B, -1), dim=-1).mean()
@@ -262,7 +262,7 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
         last_noise = ((L - 1) * torch.ones(B, device=dev)).long()
         x = x - _f((1 - alphas[-1]).sqrt()) * call_net(x, last_noise)
         if not final_only:
-            images.append(x.to("cpu"))
+            images.append(x if steps_on_device else x.to("cpu"))                    # (a new tensor: nothing writes to it again)
     _lib.check(_lib.lib.mcvd_ctx_check_range(net._ctx), "sampler (f16x2 range guard)")      # no-op unless the option f16x2 is on
     if final_only:
         return x.unsqueeze(0)
@@ -273,7 +273,8 @@ def ddpm_sampler(x_mod, scorenet, cond=None, just_beta=False, final_only=False, 
                  same_noise=False, noise_val=None, frac_steps=None, verbose=False, log=False, clip_before=True,
                  t_min=-1, gamma=False, **kwargs):
     """Reference: models/__init__.py:206-340.  Extra kwargs understood here: `noise` ([n_draws,B,C,H,W] injected
-    sequence), `seed`, `sample_offset` (global index of row 0, for sharded runs)."""
+    sequence), `seed`, `sample_offset` (global index of row 0, for sharded runs), `steps_on_device` (with `final_only=False`
+    the step images are kept as device copies and the stacked result stays on the device; the values are the same)."""
     return _sample(_lib.SAMPLER_DDPM, x_mod, scorenet, cond=cond, just_beta=just_beta, final_only=final_only,
                    denoise=denoise, subsample_steps=subsample_steps, same_noise=same_noise, noise_val=noise_val,
                    frac_steps=frac_steps, verbose=verbose, log=log, clip_before=clip_before, t_min=t_min, gamma=gamma,
@@ -290,14 +291,15 @@ def ddim_sampler(x_mod, scorenet, cond=None, final_only=False, denoise=True, sub
 
 @torch.no_grad()
 def fpndm_sampler(x_mod, scorenet, cond=None, final_only=False, denoise=True, subsample_steps=None, verbose=False, log=True,
-                  clip_before=True, t_min=-1, gamma=False, **kwargs):
+                  clip_before=True, t_min=-1, gamma=False, steps_on_device=False, **kwargs):
     """F-PNDM: reference models/__init__.py:38-99 (FPNDM_sampler) with models/pndm.py (gen_order_4 :41-52, runge_kutta :3-17,
     transfer :19-33), behaviour mirrored statement by statement: steps 0, skip, 2*skip, ... with t_next = the previous step
     (-1 first), alpha table = flipped `alphas` indexed by t + 1, network label = t, float midpoint label (t + t_next) / 2;
     Runge-Kutta for the first three steps (4 network evaluations each), 4th-order Adams-Bashforth afterwards.  `denoise`,
     `t_min`, `gamma`, `verbose`, `log` are accepted and unused, as in the reference.  Deterministic (no noise draws).
     The network evaluations are HIP forwards; the combinations and the transfer are the library's mcvd_lincomb /
-    mcvd_pndm_transfer kernels (one rounding per operation, in the reference's order)."""
+    mcvd_pndm_transfer kernels (one rounding per operation, in the reference's order).  `steps_on_device` keeps the step images
+    of `final_only=False` on the device."""
     net = _unwrap(scorenet)
     if subsample_steps is None:
         raise TypeError("FPNDM_sampler needs subsample_steps (the reference divides by it, models/__init__.py:60)")
@@ -377,7 +379,7 @@ def fpndm_sampler(x_mod, scorenet, cond=None, final_only=False, denoise=True, su
             noise = lincomb([e_1, e_2, e_3, e_4], [1.0, 2.0, 2.0, 1.0], _f(torch.tensor(1 / 6)))
         x = transfer(x, t, t_next, noise)                                           # pndm.py:51
         if not final_only:
-            images.append(x.to("cpu"))
+            images.append(x if steps_on_device else x.to("cpu"))                    # (transfer returns a new tensor every step)
     _lib.check(_lib.lib.mcvd_ctx_check_range(net._ctx), "FPNDM sampler (f16x2 range guard)")      # no-op unless the option f16x2 is on
     if final_only:
         return x.unsqueeze(0)
