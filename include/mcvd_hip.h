@@ -59,8 +59,8 @@ extern "C" {
 #define MCVD_EHIP (-2)     /* HIP runtime error */
 #define MCVD_ESTATE (-3)   /* call order violated (e.g. forward before finalize, missing parameter) */
 #define MCVD_ENOMEM (-4)
-#define MCVD_ERANGE (-5)   /* option "f16x2" only: a network output was not finite -- an activation left the fp16 range of the two-piece
-                              kernels (|x| beyond ~1e3 behind a GroupNorm), or the model diverged.  Rerun with f16x2 = 0 (the default) */
+#define MCVD_ERANGE (-5)   /* options "f16x2" / "f16x1" only: a network output was not finite -- an activation left the fp16 range of the
+                              fp16 kernels (|x| beyond ~1e3 behind a GroupNorm), or the model diverged.  Rerun with the option at 0 (the default) */
 
 #define MCVD_MAX_LEVELS 8
 
@@ -124,12 +124,23 @@ int mcvd_ctx_set_stream(mcvd_ctx* ctx, void* hip_stream);
  *         ~1e-6 lose relative precision (fp16 denormals).  The library therefore (1) gives these kernels GroupNorm-ed inputs only -- a conv
  *         over a raw tensor (stem, shortcuts, NIN_3) always runs the fp32-range kernels -- and (2) clamps nothing: an overflow becomes Inf
  *         / NaN and is REPORTED (MCVD_ERANGE, mcvd_ctx_check_range) instead of saturating silently.
+ *     "f16x1" (default 0): ALSO offer, for every 3x3 conv "f16x2" would be allowed to take (GroupNorm-ed input, not SPADE-fused, "winograd"
+ *         on), a Winograd kernel that rounds each MFMA operand to ONE fp16 value (11 significant bits) and accumulates in fp32: shape ids
+ *         24 / 25.  A DRAFT arithmetic -- preview / sweep quality, NOT within the parity tolerances: per conv the error is bounded by
+ *         (2^-10 + 2^-22 + (16 Cin + 4) 2^-24) of the summed magnitudes in the transform domain, config 2's DDPM-100 frames move by up to
+ *         6e-3 (half a grey level), for 1.35 x the frames/s of the default and 1.14 x those of "f16x2" (profiles/f16x1_time.txt,
+ *         profiles/f16x1_drift.txt).  The 1x1 GEMMs and the attention (HBM-bound; the softmax amplifies logit error), the stem, shortcuts,
+ *         NIN_3, the GEMM-form last conv and the detector nets stay exactly where "f16x2" / "bf16x3" put them.  The fp16 range, the two
+ *         guards and MCVD_ERANGE of "f16x2" apply; the message names the option that is on.  The kernel reads the first pieces of the
+ *         two-piece weight image, which is packed when either option is first switched on.  0 means that NO one-piece kernel runs: a
+ *         table that names 24 / 25 runs them as 10 / 11 (4 / 8 when "bf16x3" is off as well), also for convs with a raw input.
  *   KERNEL SELECTION
  *     "autotune" (1): time the candidate kernels per distinct layer shape on first use of a batch size and keep the fastest (a table
  *         imported through mcvd_model_set_tuning is used as is, with or without autotune; the arithmetic options above always win over it).
  *     "conv_shape" (-1 auto): force a kernel family for every conv (tests): 0/1/2/3 the 256/128/64-pixel / split-K direct tiles, 4 fp32
  *         Winograd F(2x2,3x3) (8: with its 2-way split of the input channels), 5 / 6 / 9 the fp32 all-DMA 1x1 GEMM (16 / 32 channels per
  *         chunk / 64 pixels per wave), 10 / 11 three-piece bf16 Winograd (11: K split), 12 / 13 two-piece fp16 Winograd (13: K split),
+ *         24 / 25 one-piece fp16 Winograd (25: K split; the draft arithmetic of "f16x1": kernels/conv_wino1h.cpp),
  *         14 / 15 the split-operand 1x1 GEMM with two fp16 / three bf16 pieces, 16 / 17 the three-piece bf16 Winograd kernel as PERSISTENT
  *         workgroups (one per CU walks a range of (region, cout tile[, K half]) items, the staging pipeline runs on across items; results
  *         bit-identical to 10 / 11; 17: K split), 18 / 19 the three-piece bf16 Winograd kernel with the input channels in 4 / 8 parts and
@@ -178,12 +189,12 @@ int mcvd_ctx_set_stream(mcvd_ctx* ctx, void* hip_stream);
  *         tiles by LDS-DMA (head dims 32 / 64 / 96, default arithmetic, a device of its own); bit-identical to 0 (the attention kernel splits
  *         K / V itself, once per query tile).  "profile" (0/1): see mcvd_model_profile_read.
  * Environment variables read ONCE at mcvd_ctx_create set the same options: MCVD_AUTOTUNE, MCVD_SIDE_STREAM, MCVD_WINOGRAD, MCVD_CONV_DMA1,
- * MCVD_BF16X3, MCVD_F16X2, MCVD_GRAPH, MCVD_GN_STATS, MCVD_SPADE_FUSE, MCVD_NAIVE; MCVD_ALLOW_SHARED_DEVICE (see mcvd_ctx_create) is read there
+ * MCVD_BF16X3, MCVD_F16X2, MCVD_F16X1, MCVD_GRAPH, MCVD_GN_STATS, MCVD_SPADE_FUSE, MCVD_NAIVE; MCVD_ALLOW_SHARED_DEVICE (see mcvd_ctx_create) is read there
  * too.  Nothing else in the production library reads the
  * environment (the diagnostics build, csrc/build.py --diag, adds timing-only ablation hooks). */
 int mcvd_ctx_set_option(mcvd_ctx* ctx, const char* key, int value);
-/* Option "f16x2" only (the default three-piece bf16 arithmetic has the fp32 range and needs no guard): every UNet forward run while the
- * option is on is followed by a scan of its epsilon for non-finite values (nothing is clamped in the two-piece fp16 kernels: an
+/* Options "f16x2" / "f16x1" only (the default three-piece bf16 arithmetic has the fp32 range and needs no guard): every UNet forward run while
+ * one of them is on is followed by a scan of its epsilon for non-finite values (nothing is clamped in the fp16 kernels: an
  * out-of-range activation becomes Inf, then NaN).  This call synchronises the context's stream, returns MCVD_ERANGE (and a message in
  * mcvd_last_error) if any forward since the last call produced one, else 0, and clears the record.  mcvd_sampler_run / mcvd_fpndm_run
  * call it themselves before they return; a caller of mcvd_unet_forward* calls it when it wants the verdict. */
@@ -199,7 +210,7 @@ int mcvd_ctx_check_range(mcvd_ctx* ctx);
 #define MCVD_ESELFTEST (-6)
 int mcvd_ctx_selftest(mcvd_ctx* ctx);
 /* Forgets a pending range verdict without reporting it (no synchronisation).  mcvd_sampler_run / mcvd_fpndm_run call it on entry, the
- * Python host loops at the start of every sampler call, and a change of the option "f16x2" implies it: a flag left behind by an earlier,
+ * Python host loops at the start of every sampler call, and a change of the option "f16x2" or "f16x1" implies it: a flag left behind by an earlier,
  * unrelated forward (or by a call that returned an error before its own check) must not fail the next run. */
 int mcvd_ctx_clear_range(mcvd_ctx* ctx);
 /* Diagnostics: when set (device pointer to [n_blocks][8] uint64, or NULL to disable), mcvd_op_conv2d's MFMA kernel records per

@@ -215,6 +215,7 @@ int mcvd_ctx_create(int device, void* hip_stream, mcvd_ctx** out) {
     if (const char* t = getenv("MCVD_CONV_DMA1")) c->conv_dma1 = atoi(t);
     if (const char* t = getenv("MCVD_BF16X3")) c->bf16x3 = atoi(t);
     if (const char* t = getenv("MCVD_F16X2")) c->f16x2 = atoi(t);
+    if (const char* t = getenv("MCVD_F16X1")) c->f16x1 = atoi(t);
     if (const char* t = getenv("MCVD_GRAPH")) c->graph = atoi(t);
     if (const char* t = getenv("MCVD_GN_STATS")) c->gn_stats = atoi(t);
     if (const char* t = getenv("MCVD_SPADE_FUSE")) c->spade_fuse = atoi(t);
@@ -278,14 +279,16 @@ int mcvd_ctx_set_stats_buffer(mcvd_ctx* ctx, float* device_floats) {
 int mcvd_ctx_check_range(mcvd_ctx* ctx) {
     API_TRY
     MCVD_REQUIRE(ctx, "ctx is NULL");
-    if (!ctx->range_flag) return 0;                // no forward has run under f16x2
+    if (!ctx->range_flag) return 0;                // no forward has run under f16x2 / f16x1
     int hit = 0;
     MCVD_HIP_CHECK(hipMemcpyAsync(&hit, ctx->range_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     MCVD_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (!hit) return 0;
     MCVD_HIP_CHECK(hipMemsetAsync(ctx->range_flag, 0, sizeof(int), ctx->stream));
-    set_error("f16x2: a UNet forward produced non-finite values -- an activation left the fp16 range of the two-piece kernels, or the model "
-              "diverged; rerun with the option f16x2 = 0 (the default three-piece bf16 arithmetic has the fp32 range)");
+    const char* opt = ctx->f16x2 && ctx->f16x1 ? "f16x2 + f16x1" : ctx->f16x1 ? "f16x1" : "f16x2";      // the option(s) in force
+    set_error("%s: a UNet forward produced non-finite values -- an activation left the fp16 range of the %s kernels, or the model "
+              "diverged; rerun with the option%s = 0 (the default three-piece bf16 arithmetic has the fp32 range)", opt,
+              ctx->f16x2 && ctx->f16x1 ? "fp16" : ctx->f16x1 ? "one-piece fp16" : "two-piece", ctx->f16x2 && ctx->f16x1 ? "s f16x2 and f16x1" : ctx->f16x1 ? " f16x1" : " f16x2");
     return MCVD_ERANGE;
     API_CATCH
 }
@@ -312,23 +315,23 @@ int mcvd_ctx_selftest(mcvd_ctx* ctx) {
     const float *x = dev, *w = dev + nx, *bias = w + nw, *coef = bias + Cout, *res = coef + 2 * Cin;
     float* y = dev + host.size();
     // The test runs under ITS OWN options: whatever the caller left set on the context (a forced kernel, a statistics buffer the
-    // epilogue would write 96-channel partials into, SPADE maps, a debug buffer, the f16x2 arithmetic) is put aside and restored.
+    // epilogue would write 96-channel partials into, SPADE maps, a debug buffer, the f16x2 / f16x1 arithmetic) is put aside and restored.
     // A launch that cannot run (hipMalloc, a launch error) is NOT a verdict: the state stays 0 ("not yet run"), bf16x3 stays as it
     // was and the real error is returned; only a test that ran and mismatched switches the option off (MCVD_ESELFTEST).
     struct Saved {
         mcvd_ctx* c;
-        int conv_shape, naive_conv, f16x2, bf16x3, spade_fuse;
+        int conv_shape, naive_conv, f16x2, f16x1, bf16x3, spade_fuse;
         float* stats_buf;
         const float *spade_gb, *spade_coef2;
         unsigned long long* dbg;
-        explicit Saved(mcvd_ctx* c_) : c(c_), conv_shape(c_->conv_shape), naive_conv(c_->naive_conv), f16x2(c_->f16x2), bf16x3(c_->bf16x3),
+        explicit Saved(mcvd_ctx* c_) : c(c_), conv_shape(c_->conv_shape), naive_conv(c_->naive_conv), f16x2(c_->f16x2), f16x1(c_->f16x1), bf16x3(c_->bf16x3),
                                        spade_fuse(c_->spade_fuse), stats_buf(c_->stats_buf), spade_gb(c_->spade_gb), spade_coef2(c_->spade_coef2),
                                        dbg(c_->dbg) {
-            c->naive_conv = 0; c->f16x2 = 0; c->bf16x3 = 1; c->spade_fuse = 0;
+            c->naive_conv = 0; c->f16x2 = 0; c->f16x1 = 0; c->bf16x3 = 1; c->spade_fuse = 0;
             c->stats_buf = nullptr; c->spade_gb = nullptr; c->spade_coef2 = nullptr; c->dbg = nullptr;
         }
         ~Saved() {
-            c->conv_shape = conv_shape; c->naive_conv = naive_conv; c->f16x2 = f16x2; c->spade_fuse = spade_fuse;
+            c->conv_shape = conv_shape; c->naive_conv = naive_conv; c->f16x2 = f16x2; c->f16x1 = f16x1; c->spade_fuse = spade_fuse;
             if (c->wino_selftest >= 0) c->bf16x3 = bf16x3;            // a failed verdict keeps the option off
             c->stats_buf = stats_buf; c->spade_gb = spade_gb; c->spade_coef2 = spade_coef2; c->dbg = dbg;
         }
@@ -396,6 +399,10 @@ int mcvd_ctx_set_option(mcvd_ctx* ctx, const char* key, int value) {
     else if (!strcmp(key, "f16x2")) {
         if (ctx->f16x2 != value) (void)mcvd_ctx_clear_range(ctx);        // a verdict of the other arithmetic's forwards is stale
         ctx->f16x2 = value;
+    }
+    else if (!strcmp(key, "f16x1")) {
+        if (ctx->f16x1 != value) (void)mcvd_ctx_clear_range(ctx);        // as f16x2
+        ctx->f16x1 = value;
     }
     else if (!strcmp(key, "conv_cot")) ctx->conv_cot = value;
     else if (!strcmp(key, "persist_grid")) ctx->persist_grid = value;
@@ -652,7 +659,7 @@ int mcvd_model_finalize(mcvd_model* m) {
     m->finalized = true;
     m->packed_h_valid = false;             // the two-piece fp16 forms follow the weights: repacked on the next use under f16x2
     ++m->epoch;
-    if (m->ctx->f16x2)
+    if (m->ctx->f16x2 || m->ctx->f16x1)
         if (int rc = m->ensure_f16x2_weights()) return rc;
     // once per context: the hand-scheduled Winograd kernels against the compiler-scheduled one, on this device (a failure switches the
     // option bf16x3 off and is reported by mcvd_ctx_selftest / mcvd_last_error; the model stays usable on the fp32-MFMA kernels)
@@ -776,7 +783,7 @@ int mcvd_model_set_tuning(mcvd_model* m, int B, const int* shapes, const int* co
     MCVD_REQUIRE(n == (int)m->ops.size(), "set_tuning: %d entries for a plan of %d ops (tuning of another model?)", n, (int)m->ops.size());
     for (int i = 0; i < n; ++i) {
         const bool conv = m->ops[i].kind == OP_CONV;
-        MCVD_REQUIRE(conv ? (((shapes[i] >= -1 && shapes[i] <= 23) || shapes[i] == 36 || shapes[i] == 40) && cots[i] >= 0 && cots[i] <= 9) : shapes[i] == -1,
+        MCVD_REQUIRE(conv ? (((shapes[i] >= -1 && shapes[i] <= CK_WINO1H_K2) || shapes[i] == 36 || shapes[i] == 40) && cots[i] >= 0 && cots[i] <= 9) : shapes[i] == -1,
                      "set_tuning: entry %d (shape %d, cout tile %d) does not fit op kind %d", i, shapes[i], cots[i], (int)m->ops[i].kind);
     }
     if (m->ctx) m->sync_tuning_options();         // the table belongs to the options in force now; a later option change drops it
@@ -1018,7 +1025,7 @@ int mcvd_sampler_run(mcvd_model* m, int kind, float* x, const float* cond, const
         if (int rc = m->forward(x, m->labels, cond, m->eps_buf, B)) return rc;
         if (int rc = launch_axpy_out(x, m->eps_buf, sqrtf(1.0f - al[L - 1]), n, s)) return rc;
     }
-    return m->ctx->f16x2 ? mcvd_ctx_check_range(m->ctx) : 0;      // f16x2 range guard: a non-finite epsilon anywhere in the loop is an error
+    return (m->ctx->f16x2 || m->ctx->f16x1) ? mcvd_ctx_check_range(m->ctx) : 0;      // f16x2 / f16x1 range guard: a non-finite epsilon anywhere in the loop is an error
     API_CATCH
 }
 
@@ -1107,7 +1114,7 @@ int mcvd_fpndm_run(mcvd_model* m, float* x, const float* cond, int subsample_ste
         if (int rc = transfer(x, x, (float)t, (float)t_next, comb)) return rc;            // pndm.py:51 (in place: elementwise)
         t_prev = t;
     }
-    return m->ctx->f16x2 ? mcvd_ctx_check_range(m->ctx) : 0;      // f16x2 range guard
+    return (m->ctx->f16x2 || m->ctx->f16x1) ? mcvd_ctx_check_range(m->ctx) : 0;      // f16x2 / f16x1 range guard
     API_CATCH
 }
 
@@ -1427,7 +1434,7 @@ int mcvd_dsm_loss(mcvd_model* m, const float* x, const int64_t* labels, const fl
     m->cond_mask = cond_mask;
     if (int rc = m->forward(pb, labels, cond, m->eps_buf, B)) return rc;
     if (int rc = launch_dsm_loss(zb, m->eps_buf, B, per, (flags & MCVD_DSM_L1) ? 1 : 0, part, loss_rows, s)) return rc;
-    return m->ctx->f16x2 ? mcvd_ctx_check_range(m->ctx) : 0;      // f16x2 range guard, as the samplers
+    return (m->ctx->f16x2 || m->ctx->f16x1) ? mcvd_ctx_check_range(m->ctx) : 0;      // f16x2 / f16x1 range guard, as the samplers
     API_CATCH
 }
 

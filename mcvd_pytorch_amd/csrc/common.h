@@ -171,6 +171,10 @@ bool conv_wino2h_usable(const ConvArgs& a);
 int launch_conv_wino2h(const ConvArgs& a, hipStream_t s);
 long conv_wino2h_weight_floats(int CinP, int CoutP);          // size of the wph buffer (header + pieces), in floats
 int launch_pack_wino2h_weight(const float* w, float* wh, int Cout, int Cin, int CinP, int CoutP, hipStream_t s);   // wh zero-filled
+// ... with ONE fp16 piece per operand (a draft arithmetic: 11-bit operands, fp32 accumulate; conv_wino1h.cpp): shape ids 24 / 25 (25: 2-way
+// K split); reads the first piece of the same ConvArgs::wph
+bool conv_wino1h_usable(const ConvArgs& a);
+int launch_conv_wino1h(const ConvArgs& a, hipStream_t s);
 // 1x1 GEMM on the 16-bit matrix pipes with split operands (conv1x1_h2.cpp), cout tile a.cot = 1..4: np = 3 three bf16 pieces
 // (fp32-equivalent; tile shape id 15; needs ConvArgs::wpb), np = 2 two fp16 pieces (tile shape id 14; needs ConvArgs::wph); the
 // pieces come from the packed fp32 matrix wp (launch_pack_conv1x1_h2)
@@ -259,7 +263,7 @@ int launch_sampler_update(int kind, float* x, const float* eps, const float* noi
 int launch_renoise(float* x, const float* noise, float ca, float cb, int64_t n, int use_philox, uint64_t seed,
                    uint64_t sample_offset, uint64_t draw, int64_t per_sample, hipStream_t s);
 int launch_axpy_out(float* x, const float* eps, float c, int64_t n, hipStream_t s);   // x -= c * eps
-int launch_nonfinite_flag(const float* v, int64_t n, int* flag, hipStream_t s);          // *flag = 1 if any v[i] is Inf / NaN (f16x2 range guard)
+int launch_nonfinite_flag(const float* v, int64_t n, int* flag, hipStream_t s);          // *flag = 1 if any v[i] is Inf / NaN (f16x2 / f16x1 range guard)
 int launch_pack_frames_u8(const float* in, uint8_t* out, int B, int T, int C, int HW, hipStream_t s);
 // per-frame MSE (fp32) and SSIM (fp64) of video_gen's test mode, kernels/metrics.cpp; part: frame_metrics_scratch_bytes of device scratch
 int64_t frame_metrics_scratch_bytes(int frames, int H, int W);

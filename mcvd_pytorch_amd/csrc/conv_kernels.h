@@ -13,7 +13,7 @@ enum ConvKernel : int {
     CK_WINO = 4, CK_DMA1 = 5, CK_DMA1_CK32 = 6, /* 7 unused */ CK_WINO_K2 = 8, CK_DMA1_PX64 = 9,
     CK_WINO3 = 10, CK_WINO3_K2 = 11, CK_WINO2H = 12, CK_WINO2H_K2 = 13, CK_GEMM1_F16X2 = 14, CK_GEMM1_BF16X3 = 15,
     CK_WINO3P = 16, CK_WINO3P_K2 = 17, CK_WINO3_K4 = 18, CK_WINO3_K8 = 19, CK_WINO3P_K4 = 20, /* 21 unused */
-    CK_GEMM3_TAPS = 22, CK_GEMM3_IM2COL = 23,
+    CK_GEMM3_TAPS = 22, CK_GEMM3_IM2COL = 23, CK_WINO1H = 24, CK_WINO1H_K2 = 25,
     CK_RETIRED_SPADE_WINO = 36, CK_RETIRED_SPADE_WINO_K2 = 40      // round-5 tables: the per-layer fused SPADE loader, gone; read as CK_AUTO
 };
 
@@ -27,7 +27,8 @@ enum ConvFamily : int {
     CF_WINO,        // Winograd F(2x2,3x3), fp32 MFMA (conv_wino.cpp)
     CF_WINO2H,      // ... on the fp16 pipe, two-piece operands (conv_wino2h.cpp)
     CF_WINO3,       // ... on the bf16 pipe, three-piece operands (conv_wino3.cpp)
-    CF_WINO3P       // ... the same as persistent workgroups (conv_wino3p.cpp)
+    CF_WINO3P,      // ... the same as persistent workgroups (conv_wino3p.cpp)
+    CF_WINO1H       // ... on the fp16 pipe, ONE-piece operands: a draft arithmetic (conv_wino1h.cpp)
 };
 
 enum ConvWeights : int { CW_WP, CW_WPW, CW_WPH, CW_WPB };      // the ConvArgs weight image the kernel reads
@@ -37,41 +38,44 @@ struct ConvKernelDesc {
     const char* name;
     ConvFamily family;
     int ks;                // kernel size served (0: 1 and 3)
-    int pieces;            // operand pieces: 0 fp32, 2 fp16, 3 bf16
+    int pieces;            // operand pieces: 0 fp32, 1 fp16 (one rounding: 11 bits), 2 fp16, 3 bf16
     int kparts;            // K split: 0 none, else ConvArgs::ksplit
     bool own_cot;          // takes a cout tile of its own (ConvArgs::cot is not the direct kernel's)
     ConvWeights weights;
     int no_f16x2;          // the id it becomes when the option f16x2 is off or the input is raw
     int no_bf16x3;         // the id it becomes when the option bf16x3 is off
+    int no_f16x1;          // the id it becomes when the option f16x1 is off or the input is raw (applied in front of no_bf16x3)
     int fallback[7];       // what a launch with this hint tries, in order, each only if usable; -1 ends the list, then the direct-tile heuristic
 };
 
 inline constexpr ConvKernelDesc kConvKernels[] = {
-    //  id               name              family     ks pc kp own_cot weights  no_f16x2         no_bf16x3        fallback
-    {CK_TILE256,      "tile256",        CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE256,      CK_TILE256,      {-1}},
-    {CK_TILE128,      "tile128",        CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE128,      CK_TILE128,      {-1}},
-    {CK_TILE64,       "tile64",         CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE64,       CK_TILE64,       {-1}},
-    {CK_TILE_SPLITK,  "tile64_splitk",  CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE_SPLITK,  CK_TILE_SPLITK,  {-1}},
-    {CK_WINO,         "wino",           CF_WINO,    3, 0, 0, false, CW_WPW, CK_WINO,         CK_WINO,         {CK_WINO, -1}},
-    {CK_DMA1,         "dma1",           CF_DMA1,    1, 0, 0, true,  CW_WP,  CK_DMA1,         CK_DMA1,         {CK_DMA1, -1}},
-    {CK_DMA1_CK32,    "dma1_ck32",      CF_DMA1,    1, 0, 0, true,  CW_WP,  CK_DMA1_CK32,    CK_DMA1_CK32,    {CK_DMA1_CK32, -1}},
-    {CK_WINO_K2,      "wino_k2",        CF_WINO,    3, 0, 2, false, CW_WPW, CK_WINO_K2,      CK_WINO_K2,      {CK_WINO_K2, CK_WINO, -1}},
-    {CK_DMA1_PX64,    "dma1_px64",      CF_DMA1,    1, 0, 0, true,  CW_WP,  CK_DMA1_PX64,    CK_DMA1_PX64,    {CK_DMA1_PX64, -1}},
-    {CK_WINO3,        "wino3",          CF_WINO3,   3, 3, 0, false, CW_WPB, CK_WINO3,        CK_WINO,         {CK_WINO3, CK_WINO, -1}},
-    {CK_WINO3_K2,     "wino3_k2",       CF_WINO3,   3, 3, 2, false, CW_WPB, CK_WINO3_K2,     CK_WINO_K2,      {CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
-    {CK_WINO2H,       "wino2h",         CF_WINO2H,  3, 2, 0, false, CW_WPH, CK_WINO3,        CK_WINO2H,       {CK_WINO2H, CK_WINO, -1}},
-    {CK_WINO2H_K2,    "wino2h_k2",      CF_WINO2H,  3, 2, 2, false, CW_WPH, CK_WINO3_K2,     CK_WINO2H_K2,    {CK_WINO2H_K2, CK_WINO2H, CK_WINO, -1}},
-    {CK_GEMM1_F16X2,  "gemm1_f16x2",    CF_SPLIT1,  1, 2, 0, true,  CW_WPH, CK_GEMM1_BF16X3, CK_GEMM1_F16X2,  {CK_GEMM1_F16X2, -1}},
-    {CK_GEMM1_BF16X3, "gemm1_bf16x3",   CF_SPLIT1,  1, 3, 0, true,  CW_WPB, CK_GEMM1_BF16X3, CK_DMA1,         {CK_GEMM1_BF16X3, -1}},
-    {CK_WINO3P,       "wino3p",         CF_WINO3P,  3, 3, 0, false, CW_WPB, CK_WINO3P,       CK_WINO,         {CK_WINO3P, CK_WINO3, CK_WINO, -1}},
-    {CK_WINO3P_K2,    "wino3p_k2",      CF_WINO3P,  3, 3, 2, false, CW_WPB, CK_WINO3P_K2,    CK_WINO_K2,      {CK_WINO3P_K2, CK_WINO3P, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
-    {CK_WINO3_K4,     "wino3_k4",       CF_WINO3,   3, 3, 4, false, CW_WPB, CK_WINO3_K4,     CK_WINO_K2,      {CK_WINO3_K4, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
-    {CK_WINO3_K8,     "wino3_k8",       CF_WINO3,   3, 3, 8, false, CW_WPB, CK_WINO3_K8,     CK_WINO_K2,      {CK_WINO3_K8, CK_WINO3_K4, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
-    {CK_WINO3P_K4,    "wino3p_k4",      CF_WINO3P,  3, 3, 4, false, CW_WPB, CK_WINO3P_K4,    CK_WINO_K2,      {CK_WINO3P_K4, CK_WINO3P_K2, CK_WINO3P, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
-    {CK_GEMM3_TAPS,   "gemm3_taps",     CF_GEMM3,   3, 3, 0, true,  CW_WPB, CK_GEMM3_TAPS,   CK_GEMM3_TAPS,   {-1}},     // (bf16x3 off: the model falls
-    {CK_GEMM3_IM2COL, "gemm3_im2col",   CF_GEMM3,   3, 3, 0, true,  CW_WPB, CK_GEMM3_IM2COL, CK_GEMM3_IM2COL, {-1}},     //  back to CK_AUTO itself)
+    //  id               name              family     ks pc kp own_cot weights  no_f16x2         no_bf16x3        no_f16x1         fallback
+    {CK_TILE256,      "tile256",        CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE256,      CK_TILE256,      CK_TILE256,      {-1}},
+    {CK_TILE128,      "tile128",        CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE128,      CK_TILE128,      CK_TILE128,      {-1}},
+    {CK_TILE64,       "tile64",         CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE64,       CK_TILE64,       CK_TILE64,       {-1}},
+    {CK_TILE_SPLITK,  "tile64_splitk",  CF_TILE,    0, 0, 0, false, CW_WP,  CK_TILE_SPLITK,  CK_TILE_SPLITK,  CK_TILE_SPLITK,  {-1}},
+    {CK_WINO,         "wino",           CF_WINO,    3, 0, 0, false, CW_WPW, CK_WINO,         CK_WINO,         CK_WINO,         {CK_WINO, -1}},
+    {CK_DMA1,         "dma1",           CF_DMA1,    1, 0, 0, true,  CW_WP,  CK_DMA1,         CK_DMA1,         CK_DMA1,         {CK_DMA1, -1}},
+    {CK_DMA1_CK32,    "dma1_ck32",      CF_DMA1,    1, 0, 0, true,  CW_WP,  CK_DMA1_CK32,    CK_DMA1_CK32,    CK_DMA1_CK32,    {CK_DMA1_CK32, -1}},
+    {CK_WINO_K2,      "wino_k2",        CF_WINO,    3, 0, 2, false, CW_WPW, CK_WINO_K2,      CK_WINO_K2,      CK_WINO_K2,      {CK_WINO_K2, CK_WINO, -1}},
+    {CK_DMA1_PX64,    "dma1_px64",      CF_DMA1,    1, 0, 0, true,  CW_WP,  CK_DMA1_PX64,    CK_DMA1_PX64,    CK_DMA1_PX64,    {CK_DMA1_PX64, -1}},
+    {CK_WINO3,        "wino3",          CF_WINO3,   3, 3, 0, false, CW_WPB, CK_WINO3,        CK_WINO,         CK_WINO3,        {CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3_K2,     "wino3_k2",       CF_WINO3,   3, 3, 2, false, CW_WPB, CK_WINO3_K2,     CK_WINO_K2,      CK_WINO3_K2,     {CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO2H,       "wino2h",         CF_WINO2H,  3, 2, 0, false, CW_WPH, CK_WINO3,        CK_WINO2H,       CK_WINO2H,       {CK_WINO2H, CK_WINO, -1}},
+    {CK_WINO2H_K2,    "wino2h_k2",      CF_WINO2H,  3, 2, 2, false, CW_WPH, CK_WINO3_K2,     CK_WINO2H_K2,    CK_WINO2H_K2,    {CK_WINO2H_K2, CK_WINO2H, CK_WINO, -1}},
+    {CK_GEMM1_F16X2,  "gemm1_f16x2",    CF_SPLIT1,  1, 2, 0, true,  CW_WPH, CK_GEMM1_BF16X3, CK_GEMM1_F16X2,  CK_GEMM1_F16X2,  {CK_GEMM1_F16X2, -1}},
+    {CK_GEMM1_BF16X3, "gemm1_bf16x3",   CF_SPLIT1,  1, 3, 0, true,  CW_WPB, CK_GEMM1_BF16X3, CK_DMA1,         CK_GEMM1_BF16X3, {CK_GEMM1_BF16X3, -1}},
+    {CK_WINO3P,       "wino3p",         CF_WINO3P,  3, 3, 0, false, CW_WPB, CK_WINO3P,       CK_WINO,         CK_WINO3P,       {CK_WINO3P, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3P_K2,    "wino3p_k2",      CF_WINO3P,  3, 3, 2, false, CW_WPB, CK_WINO3P_K2,    CK_WINO_K2,      CK_WINO3P_K2,    {CK_WINO3P_K2, CK_WINO3P, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3_K4,     "wino3_k4",       CF_WINO3,   3, 3, 4, false, CW_WPB, CK_WINO3_K4,     CK_WINO_K2,      CK_WINO3_K4,     {CK_WINO3_K4, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3_K8,     "wino3_k8",       CF_WINO3,   3, 3, 8, false, CW_WPB, CK_WINO3_K8,     CK_WINO_K2,      CK_WINO3_K8,     {CK_WINO3_K8, CK_WINO3_K4, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_WINO3P_K4,    "wino3p_k4",      CF_WINO3P,  3, 3, 4, false, CW_WPB, CK_WINO3P_K4,    CK_WINO_K2,      CK_WINO3P_K4,    {CK_WINO3P_K4, CK_WINO3P_K2, CK_WINO3P, CK_WINO3_K2, CK_WINO3, CK_WINO, -1}},
+    {CK_GEMM3_TAPS,   "gemm3_taps",     CF_GEMM3,   3, 3, 0, true,  CW_WPB, CK_GEMM3_TAPS,   CK_GEMM3_TAPS,   CK_GEMM3_TAPS,   {-1}},     // (bf16x3 off: the model falls
+    {CK_GEMM3_IM2COL, "gemm3_im2col",   CF_GEMM3,   3, 3, 0, true,  CW_WPB, CK_GEMM3_IM2COL, CK_GEMM3_IM2COL, CK_GEMM3_IM2COL, {-1}},     //  back to CK_AUTO itself)
+    {CK_WINO1H,       "wino1h",         CF_WINO1H,  3, 1, 0, false, CW_WPH, CK_WINO1H,       CK_WINO1H,       CK_WINO3,        {CK_WINO1H, CK_WINO, -1}},
+    {CK_WINO1H_K2,    "wino1h_k2",      CF_WINO1H,  3, 1, 2, false, CW_WPH, CK_WINO1H_K2,    CK_WINO1H_K2,    CK_WINO3_K2,     {CK_WINO1H_K2, CK_WINO1H, CK_WINO, -1}},
 };
-inline constexpr ConvKernelDesc kNoConvKernel = {CK_AUTO, "auto", CF_NONE, 0, 0, 0, false, CW_WP, CK_AUTO, CK_AUTO, {-1}};
+inline constexpr ConvKernelDesc kNoConvKernel = {CK_AUTO, "auto", CF_NONE, 0, 0, 0, false, CW_WP, CK_AUTO, CK_AUTO, CK_AUTO, {-1}};
 
 // the descriptor of an id; kNoConvKernel for CK_AUTO and for anything that is not a kernel (an option or an imported table can hold any integer)
 constexpr const ConvKernelDesc& conv_kernel(int id) {
@@ -84,6 +88,7 @@ constexpr int k_parts(int id) { return conv_kernel(id).kparts; }
 constexpr int pieces(int id) { return conv_kernel(id).pieces; }
 constexpr int without_f16x2(int id) { return conv_kernel(id).id == id ? conv_kernel(id).no_f16x2 : id; }
 constexpr int without_bf16x3(int id) { return conv_kernel(id).id == id ? conv_kernel(id).no_bf16x3 : id; }
+constexpr int without_f16x1(int id) { return conv_kernel(id).id == id ? conv_kernel(id).no_f16x1 : id; }
 
 // ---- the table, checked ----
 namespace conv_kernels_check {
@@ -119,8 +124,9 @@ constexpr bool fallbacks_sound() {
 // a remap stays within the kernel size, drops exactly the pieces the option names and keeps a K split where the target family has one
 constexpr bool remaps_sound() {
     for (const ConvKernelDesc& k : kConvKernels) {
-        const ConvKernelDesc &f = conv_kernel(k.no_f16x2), &b = conv_kernel(k.no_bf16x3);
-        if (!known(k.no_f16x2) || !known(k.no_bf16x3) || f.ks != k.ks || b.ks != k.ks) return false;
+        const ConvKernelDesc &f = conv_kernel(k.no_f16x2), &b = conv_kernel(k.no_bf16x3), &o = conv_kernel(k.no_f16x1);
+        if (!known(k.no_f16x2) || !known(k.no_bf16x3) || !known(k.no_f16x1) || f.ks != k.ks || b.ks != k.ks || o.ks != k.ks) return false;
+        if (k.pieces == 1 ? (o.pieces != 3 || o.kparts != k.kparts) : o.id != k.id) return false;
         if (k.pieces == 2 ? (f.pieces != 3 || f.kparts != k.kparts) : f.id != k.id) return false;
         if (k.pieces == 3 && k.family != CF_GEMM3 ? (b.pieces != 0 || (b.kparts != 0) != (k.kparts != 0)) : b.id != k.id) return false;
     }
@@ -129,7 +135,9 @@ constexpr bool remaps_sound() {
 static_assert(ids_unique(), "conv kernel ids must be unique");
 static_assert(!known(7) && !known(21) && !known(CK_AUTO) && !known(CK_RETIRED_SPADE_WINO) && !known(CK_RETIRED_SPADE_WINO_K2), "7 and 21 stay unused; retired ids are not kernels");
 static_assert(fallbacks_sound(), "a fallback list names an unknown id, another kernel size, or does not get simpler");
-static_assert(remaps_sound(), "an option remap names an unknown id, changes the kernel size or loses the K split");
+static_assert(remaps_sound(), "an option remap names an unknown id, changes the kernel size, drops the wrong pieces or loses the K split");
+static_assert(fallback_is(CK_WINO1H_K2, {25, 24, 4}), "fallback list of 25");
+static_assert(fallback_is(CK_WINO1H, {24, 4}), "fallback list of 24");
 static_assert(fallback_is(CK_WINO3P_K4, {20, 17, 16, 11, 10, 4}), "fallback list of 20");
 static_assert(fallback_is(CK_WINO3_K8, {19, 18, 11, 10, 4}), "fallback list of 19");
 static_assert(fallback_is(CK_WINO3_K4, {18, 11, 10, 4}), "fallback list of 18");
@@ -146,6 +154,10 @@ static_assert(fallback_is(0, {}) && fallback_is(3, {}) && fallback_is(22, {}) &&
 static_assert(without_f16x2(12) == 10 && without_f16x2(13) == 11 && without_f16x2(14) == 15 && without_f16x2(15) == 15 && without_f16x2(99) == 99, "f16x2 off");
 static_assert(without_bf16x3(10) == 4 && without_bf16x3(16) == 4 && without_bf16x3(15) == 5 && without_bf16x3(11) == 8 && without_bf16x3(17) == 8 &&
               without_bf16x3(18) == 8 && without_bf16x3(19) == 8 && without_bf16x3(20) == 8 && without_bf16x3(22) == 22 && without_bf16x3(99) == 99, "bf16x3 off");
+static_assert(without_f16x1(24) == 10 && without_f16x1(25) == 11 && without_f16x1(12) == 12 && without_f16x1(10) == 10 && without_f16x1(99) == 99 &&
+              without_f16x2(24) == 24 && without_bf16x3(25) == 25, "f16x1 off: the one-piece ids become the three-piece ones; the other options leave them alone");
+static_assert(without_bf16x3(without_f16x1(24)) == 4 && without_bf16x3(without_f16x1(25)) == 8, "f16x1 and bf16x3 off: the fp32-MFMA kernels");
+static_assert(pieces(24) == 1 && pieces(25) == 1 && k_parts(25) == 2 && is_winograd(24) && is_winograd(25), "the one-piece rows");
 }  // namespace conv_kernels_check
 
 }  // namespace mcvd

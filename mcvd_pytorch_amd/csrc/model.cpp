@@ -776,7 +776,7 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
             a.act = op.act;
             a.wp = packed + op.wp;
             a.wpw = op.wpw >= 0 ? packed + op.wpw : nullptr;
-            a.wph = (op.wph >= 0 && packed_h_valid) ? packed_h + op.wph : nullptr;      // present only while the option f16x2 is on
+            a.wph = (op.wph >= 0 && packed_h_valid) ? packed_h + op.wph : nullptr;      // present only while the option f16x2 or f16x1 is on
             a.wpb = op.wpb >= 0 ? packed + op.wpb : nullptr;
             a.bias = packed + op.bias;
             a.res = op.res.kind == REF_NONE ? nullptr : resolve(op.res, x, cond, out, B);
@@ -807,8 +807,10 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
                 a.cot = tuned_cot[oi];
                 // an imported table from a run under other options: the options win.  f16x2 hints go to their bf16x3 counterparts when
                 // f16x2 is off -- and for convs with a raw input in any case (f16x2 range guard, below); bf16x3 hints go to the fp32-MFMA
-                // kernels when bf16x3 is off (conv_kernels.h: no_f16x2 / no_bf16x3)
+                // kernels when bf16x3 is off; one-piece hints go to their bf16x3 counterparts when f16x1 is off or the input is raw, in
+                // front of the bf16x3 remap (conv_kernels.h: no_f16x2 / no_f16x1 / no_bf16x3)
                 const bool raw_in = op.coef.kind == REF_NONE;
+                if ((!ctx->f16x1 || raw_in) && without_f16x1(a.shape_hint) != a.shape_hint) a.shape_hint = without_f16x1(a.shape_hint);
                 if ((!ctx->f16x2 || raw_in) && without_f16x2(a.shape_hint) != a.shape_hint) {
                     a.shape_hint = without_f16x2(a.shape_hint);
                     if (conv_kernel(a.shape_hint).own_cot && !conv_kernel_usable(a.shape_hint, a)) a.cot = op.cot;
@@ -1022,7 +1024,7 @@ int mcvd_model::autotune(int B) {
             a.act = op.act;
             a.wp = packed + op.wp;
             a.wpw = op.wpw >= 0 ? packed + op.wpw : nullptr;
-            a.wph = (op.wph >= 0 && packed_h_valid) ? packed_h + op.wph : nullptr;      // present only while the option f16x2 is on
+            a.wph = (op.wph >= 0 && packed_h_valid) ? packed_h + op.wph : nullptr;      // present only while the option f16x2 or f16x1 is on
             a.wpb = op.wpb >= 0 ? packed + op.wpb : nullptr;
             a.bias = packed + op.bias;
             a.res = op.res.kind == REF_NONE ? nullptr : resolve(op.res, scratch_io, scratch_io, scratch_io, B);
@@ -1116,6 +1118,12 @@ int mcvd_model::autotune(int B) {
             if (op.ks == 3 && ctx->winograd && f16_ok && !spade_fused)            // Winograd on the fp16 pipe, two-piece operands
                 for (int id : {CK_WINO2H, CK_WINO2H_K2})
                     if (int rc = offer(id, op.cot)) return rc;
+            // ... one-piece operands (the draft arithmetic "f16x1"): the same convs, under the same guard.  The 1x1 GEMMs below and the
+            // attention have no one-piece form: they stay where f16x2 / bf16x3 put them
+            const bool f16x1_ok = ctx->f16x1 && a.coef != nullptr;
+            if (op.ks == 3 && ctx->winograd && f16x1_ok && !spade_fused)
+                for (int id : {CK_WINO1H, CK_WINO1H_K2})
+                    if (int rc = offer(id, op.cot)) return rc;
             if (op.ks == 1 && ctx->conv_dma1) {        // the 1x1 GEMMs, cout tiles of their own
                 // small cout tiles first: the sweep of every 1x1 layer shape (profiles/r02_conv1x1_candidates.txt) has tiles 1-3 winning
                 // everywhere; 6 / 9 never did
@@ -1152,11 +1160,11 @@ int mcvd_model::autotune(int B) {
 }
 
 // The options that decide which kernels the autotuner may offer: tables tuned (or imported) under other settings are dropped --
-// "f16x2" = 0 must really mean that no two-piece fp16 kernel runs.  Called before a table is looked up and before one is imported
+// "f16x2" = 0 must really mean that no two-piece fp16 kernel runs, "f16x1" = 0 that no one-piece kernel does.  Called before a table is looked up and before one is imported
 // (mcvd_model_set_tuning stamps its table with the options in force at the import).
 void mcvd_model::sync_tuning_options() {
     const int sig = (ctx->winograd ? 1 : 0) | (ctx->conv_dma1 ? 2 : 0) | (ctx->bf16x3 ? 4 : 0) | (ctx->f16x2 ? 8 : 0) |
-                    (ctx->spade_fuse ? 16 : 0) | (ctx->conv_wdma ? 32 : 0);
+                    (ctx->spade_fuse ? 16 : 0) | (ctx->conv_wdma ? 32 : 0) | (ctx->f16x1 ? 64 : 0);
     if (sig != tuned_sig) {
         if (tuned_sig >= 0) { tuned_cache.clear(); tuned_B = 0; }
         tuned_sig = sig;
@@ -1164,7 +1172,8 @@ void mcvd_model::sync_tuning_options() {
 }
 
 // The two-piece fp16 forms of the weights (1.3 x the fp32 bytes for config 2) are packed when the option f16x2 first needs them, not at
-// every finalize: default-arithmetic models never allocate them.
+// every finalize: default-arithmetic models never allocate them.  The option f16x1 needs them too: its kernel reads the first
+// pieces out of the same image.
 int mcvd_model::ensure_f16x2_weights() {
     if (packed_h_valid || packed_h_floats == 0) return 0;
     hipStream_t s = ctx->stream;
@@ -1225,9 +1234,9 @@ int mcvd_model::prepare_B(int B) {
     // autotune() then times (the launches carry the capacity as well, ConvArgs::part_floats)
     sync_tuning_options();
     if (int rc = ensure_ksplit(B)) return rc;
-    // (a forced two-piece kernel family -- tests -- needs the pieces as well as the option does)
-    const bool forced_h = pieces(ctx->conv_shape) == 2 || ctx->conv_shape1 == CK_GEMM1_F16X2;
-    if (ctx->f16x2 || forced_h)
+    // (a forced two-piece or one-piece kernel family -- tests -- needs the pieces as well as the option does)
+    const bool forced_h = pieces(ctx->conv_shape) == 2 || pieces(ctx->conv_shape) == 1 || ctx->conv_shape1 == CK_GEMM1_F16X2;
+    if (ctx->f16x2 || ctx->f16x1 || forced_h)
         if (int rc = ensure_f16x2_weights()) return rc;
     if (!ctx->naive_conv && tuned_B != B) {
         auto it = tuned_cache.find(B);
@@ -1265,11 +1274,11 @@ int mcvd_model::prepare_cond(const float* cond, int B) {
     return 0;
 }
 
-// f16x2 range guard, second half (the first: convs over raw tensors never take the two-piece fp16 kernels, autotune()): the forward's
+// f16x2 / f16x1 range guard, second half (the first: convs over raw tensors never take the fp16 kernels, autotune()): the forward's
 // epsilon is scanned for Inf / NaN; mcvd_ctx_check_range turns a hit into MCVD_ERANGE.
 int mcvd_model::forward(const float* x, const void* lab, const float* cond, float* out, int B) {
     if (int rc = forward_unchecked(x, lab, cond, out, B)) return rc;
-    if (!ctx->f16x2) return 0;
+    if (!ctx->f16x2 && !ctx->f16x1) return 0;
     if (!ctx->range_flag) {
         MCVD_HIP_CHECK(hipMalloc((void**)&ctx->range_flag, sizeof(int)));
         MCVD_HIP_CHECK(hipMemsetAsync(ctx->range_flag, 0, sizeof(int), ctx->stream));

@@ -39,6 +39,9 @@ struct mcvd_ctx {
     int f16x2 = 0;                 // offer the two-piece fp16 kernels (conv_wino2h.cpp, conv1x1_h2.cpp, attention_h2.cpp with NP = 2: 22-bit operands,
                                    //    fp16 exponent range, fp32 accumulate) as well.  OFF by default: narrower arithmetic than the reference's.
                                    //    Convs with a raw (not normalised) input never take them; see model.cpp "f16x2 range guard"
+    int f16x1 = 0;                 // offer the ONE-piece fp16 Winograd kernel (conv_wino1h.cpp: operands rounded to 11 bits, fp16 exponent range, fp32
+                                   //    accumulate) for the 3x3 convs f16x2 may take.  A DRAFT arithmetic, OFF by default: it does not meet the parity
+                                   //    tolerances.  1x1 GEMMs and attention stay where f16x2 / bf16x3 put them.  Same range guard as f16x2
     int conv_dma1 = 1;             // offer the all-DMA 1x1 GEMM kernel (conv1x1_dma.cpp) to the autotuner
     int conv_wdma = 1;             // weight chunks by LDS-DMA (1) or register staging (0)
     int share_fence = 0;           // 1: a context that shares its device keeps the split-operand attention kernels off it (the round-5 workaround; the cause is gone)
@@ -57,7 +60,7 @@ struct mcvd_ctx {
     const float* spade_gb = nullptr;     // mcvd_op_conv2d: SPADE prologue inputs of the next convs (mcvd_ctx_set_spade_inputs; tests)
     const float* spade_coef2 = nullptr;
     float* stats_buf = nullptr;          // mcvd_op_conv2d: where the conv's GroupNorm partials go (mcvd_ctx_set_stats_buffer; tests)
-    int* range_flag = nullptr;     // device word: set by nonfinite_flag_kernel after a forward under f16x2 (mcvd_ctx_check_range reads + clears it)
+    int* range_flag = nullptr;     // device word: set by nonfinite_flag_kernel after a forward under f16x2 / f16x1 (mcvd_ctx_check_range reads + clears it)
     float* scratch = nullptr;      // small device scratch for stand-alone ops (kernel taps, packed weights)
     size_t scratch_bytes = 0;
     int ensure_scratch(size_t bytes);
@@ -178,7 +181,7 @@ struct mcvd_model {
     float* packed = nullptr;          // kernel-layout weights (device)
     long long* coef2_desc_dev = nullptr;   // SPADE nets: {arena offset, emb_off, C} of every (1 + scale, shift) table (launch_coef2_all), uploaded at finalize
     int coef2_first = -1, coef2_count = 0, coef2_cmax = 0;      // plan index of the first OP_COEF2 (it fills every table), number of tables, widest
-    float* packed_h = nullptr;        // the two-piece fp16 forms (ConvPack::wph offsets), allocated + packed on first use under the option f16x2
+    float* packed_h = nullptr;        // the two-piece fp16 forms (ConvPack::wph offsets), allocated + packed on first use under the option f16x2 or f16x1 (which reads the first pieces)
     int64_t packed_h_floats = 0;
     bool packed_h_valid = false;      // cleared by mcvd_model_finalize (new weights)
     int ensure_f16x2_weights();
@@ -226,7 +229,7 @@ struct mcvd_model {
                                       //    -1 never launched): what mcvd_model_op_kernel reports
     std::vector<int> tuned_shape, tuned_cot;
     int tuned_B = 0;
-    int tuned_sig = -1;            // the kernel-offer options (winograd, conv_dma1, bf16x3, f16x2, spade_fuse, conv_wdma) the tables were tuned under
+    int tuned_sig = -1;            // the kernel-offer options (winograd, conv_dma1, bf16x3, f16x2, spade_fuse, conv_wdma, f16x1) the tables were tuned under
     // every batch size tuned (or imported through mcvd_model_set_tuning) so far: alternating batch sizes do not re-tune
     std::map<int, std::pair<std::vector<int>, std::vector<int>>> tuned_cache;
     int autotune(int B);

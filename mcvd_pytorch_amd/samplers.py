@@ -126,7 +126,7 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
         if cond_noise.dim() != 5 or tuple(cond_noise.shape[1:]) != tuple(cond.shape) or cond_noise.shape[0] < n_fwd:
             raise RuntimeError(f"cond_noise has shape {tuple(cond_noise.shape)}; need at least [{n_fwd}, {', '.join(map(str, cond.shape))}]")
 
-    _lib.check(_lib.lib.mcvd_ctx_clear_range(net._ctx), "clear_range")      # the f16x2 range verdict below is about THIS call's forwards
+    _lib.check(_lib.lib.mcvd_ctx_clear_range(net._ctx), "clear_range")      # the f16x2 / f16x1 range verdict below is about THIS call's forwards
     fast = final_only and not verbose and not log and not same_noise and noise_val is None and frac_steps is None
     if gamma and not gamma_device and t_min > 0 and n_exec > 0:
         fast = False                   # DDIM with a gamma re-noise draw: the host loop (the device loop's gamma stream belongs to the DDPM sampler)
@@ -263,7 +263,7 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
         x = x - _f((1 - alphas[-1]).sqrt()) * call_net(x, last_noise)
         if not final_only:
             images.append(x if steps_on_device else x.to("cpu"))                    # (a new tensor: nothing writes to it again)
-    _lib.check(_lib.lib.mcvd_ctx_check_range(net._ctx), "sampler (f16x2 range guard)")      # no-op unless the option f16x2 is on
+    _lib.check(_lib.lib.mcvd_ctx_check_range(net._ctx), "sampler (f16x2 / f16x1 range guard)")      # no-op unless one of the two options is on
     if final_only:
         return x.unsqueeze(0)
     return torch.stack(images)
@@ -380,7 +380,7 @@ def fpndm_sampler(x_mod, scorenet, cond=None, final_only=False, denoise=True, su
         x = transfer(x, t, t_next, noise)                                           # pndm.py:51
         if not final_only:
             images.append(x if steps_on_device else x.to("cpu"))                    # (transfer returns a new tensor every step)
-    _lib.check(_lib.lib.mcvd_ctx_check_range(net._ctx), "FPNDM sampler (f16x2 range guard)")      # no-op unless the option f16x2 is on
+    _lib.check(_lib.lib.mcvd_ctx_check_range(net._ctx), "FPNDM sampler (f16x2 / f16x1 range guard)")      # no-op unless one of the two options is on
     if final_only:
         return x.unsqueeze(0)
     return torch.stack(images)
