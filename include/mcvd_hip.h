@@ -121,26 +121,33 @@ int mcvd_ctx_set_stream(mcvd_ctx* ctx, void* hip_stream);
  *     "f16x2" (default 0): ALSO offer the two-piece fp16 kernels -- operands rounded to two fp16 pieces (22-23 significant bits where fp32
  *         has 24; fp16 exponent range), three piece products: ~15 % faster end to end, NARROWER than the reference's fp32.  Range: the
  *         pieces are finite for |activation| < ~1e3 (a Winograd transform value is a sum of four, times 2^4, against 65504); values below
- *         ~1e-6 lose relative precision (fp16 denormals).  The library therefore (1) gives these kernels GroupNorm-ed inputs only -- a conv
- *         over a raw tensor (stem, shortcuts, NIN_3) always runs the fp32-range kernels -- and (2) clamps nothing: an overflow becomes Inf
- *         / NaN and is REPORTED (MCVD_ERANGE, mcvd_ctx_check_range) instead of saturating silently.
- *     "f16x1" (default 0): ALSO offer, for every 3x3 conv "f16x2" would be allowed to take (GroupNorm-ed input, not SPADE-fused, "winograd"
- *         on), a Winograd kernel that rounds each MFMA operand to ONE fp16 value (11 significant bits) and accumulates in fp32: shape ids
- *         24 / 25.  A DRAFT arithmetic -- preview / sweep quality, NOT within the parity tolerances: per conv the error is bounded by
+ *         ~1e-6 lose relative precision (fp16 denormals).  The library therefore (1) gives these kernels NORMALISED inputs only: GroupNorm-ed ones,
+ *         and the 3x3 convs behind a SPADE norm (the ResBlock convs and the last conv of a SPADE net), which read the tensor spade_apply
+ *         materialises -- silu(((A x + B)(1 + gamma) + beta) s1 + b2), as bounded as a GroupNorm-ed value up to the cond-derived gamma /
+ *         beta.  A conv over a raw tensor (stem, shortcuts, NIN_3, a conv behind a FIR resampler, the cond-only SPADE prep convs
+ *         mlp_shared / mlp_gamma / mlp_beta) always runs the fp32-range kernels.  With "spade_fuse" = 1 the SPADE modulation stays in the
+ *         fp32 Winograd loader (shape ids 4 / 8) and neither fp16 option reaches those convs.  And (2) it clamps nothing: an overflow --
+ *         also one behind a SPADE norm with a huge gamma -- becomes Inf / NaN and is REPORTED (MCVD_ERANGE, mcvd_ctx_check_range) instead
+ *         of saturating silently.
+ *     "f16x1" (default 0): ALSO offer, for every 3x3 conv "f16x2" would be allowed to take (GroupNorm-ed or SPADE-normalised input, not SPADE-fused,
+ *         "winograd" on), a Winograd kernel that rounds each MFMA operand to ONE fp16 value (11 significant bits) and accumulates in fp32:
+ *         shape ids 24 / 25 / 27.  A DRAFT arithmetic -- preview / sweep quality, NOT within the parity tolerances: per conv the error is bounded by
  *         (2^-10 + 2^-22 + (16 Cin + 4) 2^-24) of the summed magnitudes in the transform domain, config 2's DDPM-100 frames move by up to
  *         6e-3 (half a grey level), for 1.35 x the frames/s of the default and 1.14 x those of "f16x2" (profiles/f16x1_time.txt,
  *         profiles/f16x1_drift.txt).  The 1x1 GEMMs and the attention (HBM-bound; the softmax amplifies logit error), the stem, shortcuts,
  *         NIN_3, the GEMM-form last conv and the detector nets stay exactly where "f16x2" / "bf16x3" put them.  The fp16 range, the two
  *         guards and MCVD_ERANGE of "f16x2" apply; the message names the option that is on.  The kernel reads the first pieces of the
  *         two-piece weight image, which is packed when either option is first switched on.  0 means that NO one-piece kernel runs: a
- *         table that names 24 / 25 runs them as 10 / 11 (4 / 8 when "bf16x3" is off as well), also for convs with a raw input.
+ *         table that names 24 / 25 / 27 runs them as 10 / 11 / 18 (4 / 8 / 8 when "bf16x3" is off as well), also for convs with a raw input.
  *   KERNEL SELECTION
  *     "autotune" (1): time the candidate kernels per distinct layer shape on first use of a batch size and keep the fastest (a table
  *         imported through mcvd_model_set_tuning is used as is, with or without autotune; the arithmetic options above always win over it).
  *     "conv_shape" (-1 auto): force a kernel family for every conv (tests): 0/1/2/3 the 256/128/64-pixel / split-K direct tiles, 4 fp32
  *         Winograd F(2x2,3x3) (8: with its 2-way split of the input channels), 5 / 6 / 9 the fp32 all-DMA 1x1 GEMM (16 / 32 channels per
  *         chunk / 64 pixels per wave), 10 / 11 three-piece bf16 Winograd (11: K split), 12 / 13 two-piece fp16 Winograd (13: K split),
- *         24 / 25 one-piece fp16 Winograd (25: K split; the draft arithmetic of "f16x1": kernels/conv_wino1h.cpp),
+ *         24 / 25 one-piece fp16 Winograd (25: K split; the draft arithmetic of "f16x1": kernels/conv_wino1h.cpp), 26 / 27 the two-piece /
+ *         one-piece fp16 Winograd kernels with the input channels in 4 parts (a chunk count that divides by 4, at least three 16-channel
+ *         chunks per part; else 13 / 25, then 12 / 24; with their option off they are 18),
  *         14 / 15 the split-operand 1x1 GEMM with two fp16 / three bf16 pieces, 16 / 17 the three-piece bf16 Winograd kernel as PERSISTENT
  *         workgroups (one per CU walks a range of (region, cout tile[, K half]) items, the staging pipeline runs on across items; results
  *         bit-identical to 10 / 11; 17: K split), 18 / 19 the three-piece bf16 Winograd kernel with the input channels in 4 / 8 parts and

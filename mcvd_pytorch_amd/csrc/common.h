@@ -154,7 +154,7 @@ bool conv_wino_supported(int ks, int H, int W);      // geometry only (decides w
 int conv_wino_cout_tile(int Cout);
 bool conv_wino_usable(const ConvArgs& a);            // shape id 4 applies to this launch
 int launch_conv_wino(const ConvArgs& a, hipStream_t s);
-int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s);      // second pass of the 2-way K split (both Winograd kernels)
+int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s);      // second pass of the K split, 2 / 4 / 8 parts (every Winograd kernel)
 // the same convolution with the channel contraction on the bf16 matrix pipe at fp32 accuracy (three exact bf16 pieces per operand,
 // six piece products, weights pre-split at pack time; conv_wino3.cpp): tile shape ids 10 / 11 (11: 2-way K split); needs ConvArgs::wpb
 bool conv_wino3_usable(const ConvArgs& a);

@@ -14,6 +14,7 @@ enum ConvKernel : int {
     CK_WINO3 = 10, CK_WINO3_K2 = 11, CK_WINO2H = 12, CK_WINO2H_K2 = 13, CK_GEMM1_F16X2 = 14, CK_GEMM1_BF16X3 = 15,
     CK_WINO3P = 16, CK_WINO3P_K2 = 17, CK_WINO3_K4 = 18, CK_WINO3_K8 = 19, CK_WINO3P_K4 = 20, /* 21 unused */
     CK_GEMM3_TAPS = 22, CK_GEMM3_IM2COL = 23, CK_WINO1H = 24, CK_WINO1H_K2 = 25,
+    CK_WINO2H_K4 = 26, CK_WINO1H_K4 = 27,
     CK_RETIRED_SPADE_WINO = 36, CK_RETIRED_SPADE_WINO_K2 = 40      // round-5 tables: the per-layer fused SPADE loader, gone; read as CK_AUTO
 };
 
@@ -74,6 +75,8 @@ inline constexpr ConvKernelDesc kConvKernels[] = {
     {CK_GEMM3_IM2COL, "gemm3_im2col",   CF_GEMM3,   3, 3, 0, true,  CW_WPB, CK_GEMM3_IM2COL, CK_GEMM3_IM2COL, CK_GEMM3_IM2COL, {-1}},     //  back to CK_AUTO itself)
     {CK_WINO1H,       "wino1h",         CF_WINO1H,  3, 1, 0, false, CW_WPH, CK_WINO1H,       CK_WINO1H,       CK_WINO3,        {CK_WINO1H, CK_WINO, -1}},
     {CK_WINO1H_K2,    "wino1h_k2",      CF_WINO1H,  3, 1, 2, false, CW_WPH, CK_WINO1H_K2,    CK_WINO1H_K2,    CK_WINO3_K2,     {CK_WINO1H_K2, CK_WINO1H, CK_WINO, -1}},
+    {CK_WINO2H_K4,    "wino2h_k4",      CF_WINO2H,  3, 2, 4, false, CW_WPH, CK_WINO3_K4,     CK_WINO2H_K4,    CK_WINO2H_K4,    {CK_WINO2H_K4, CK_WINO2H_K2, CK_WINO2H, CK_WINO, -1}},
+    {CK_WINO1H_K4,    "wino1h_k4",      CF_WINO1H,  3, 1, 4, false, CW_WPH, CK_WINO1H_K4,    CK_WINO1H_K4,    CK_WINO3_K4,     {CK_WINO1H_K4, CK_WINO1H_K2, CK_WINO1H, CK_WINO, -1}},
 };
 inline constexpr ConvKernelDesc kNoConvKernel = {CK_AUTO, "auto", CF_NONE, 0, 0, 0, false, CW_WP, CK_AUTO, CK_AUTO, CK_AUTO, {-1}};
 
@@ -136,6 +139,8 @@ static_assert(ids_unique(), "conv kernel ids must be unique");
 static_assert(!known(7) && !known(21) && !known(CK_AUTO) && !known(CK_RETIRED_SPADE_WINO) && !known(CK_RETIRED_SPADE_WINO_K2), "7 and 21 stay unused; retired ids are not kernels");
 static_assert(fallbacks_sound(), "a fallback list names an unknown id, another kernel size, or does not get simpler");
 static_assert(remaps_sound(), "an option remap names an unknown id, changes the kernel size, drops the wrong pieces or loses the K split");
+static_assert(fallback_is(CK_WINO1H_K4, {27, 25, 24, 4}), "fallback list of 27");
+static_assert(fallback_is(CK_WINO2H_K4, {26, 13, 12, 4}), "fallback list of 26");
 static_assert(fallback_is(CK_WINO1H_K2, {25, 24, 4}), "fallback list of 25");
 static_assert(fallback_is(CK_WINO1H, {24, 4}), "fallback list of 24");
 static_assert(fallback_is(CK_WINO3P_K4, {20, 17, 16, 11, 10, 4}), "fallback list of 20");
@@ -158,6 +163,11 @@ static_assert(without_f16x1(24) == 10 && without_f16x1(25) == 11 && without_f16x
               without_f16x2(24) == 24 && without_bf16x3(25) == 25, "f16x1 off: the one-piece ids become the three-piece ones; the other options leave them alone");
 static_assert(without_bf16x3(without_f16x1(24)) == 4 && without_bf16x3(without_f16x1(25)) == 8, "f16x1 and bf16x3 off: the fp32-MFMA kernels");
 static_assert(pieces(24) == 1 && pieces(25) == 1 && k_parts(25) == 2 && is_winograd(24) && is_winograd(25), "the one-piece rows");
+static_assert(CK_WINO2H_K4 == 26 && CK_WINO1H_K4 == 27 && pieces(26) == 2 && pieces(27) == 1 && k_parts(26) == 4 && k_parts(27) == 4 &&
+              conv_kernel(26).family == CF_WINO2H && conv_kernel(27).family == CF_WINO1H, "the 4-way K split of the two fp16 Winograd kernels");
+static_assert(without_f16x2(26) == 18 && without_f16x1(26) == 26 && without_bf16x3(26) == 26 && without_f16x1(27) == 18 && without_f16x2(27) == 27 &&
+              without_bf16x3(27) == 27, "their option off: the three-piece 4-way split; the other options leave them alone");
+static_assert(without_bf16x3(without_f16x2(26)) == 8 && without_bf16x3(without_f16x1(27)) == 8, "... and bf16x3 off as well: the fp32-MFMA 2-way split");
 }  // namespace conv_kernels_check
 
 }  // namespace mcvd

@@ -16,7 +16,8 @@
 //   * activations: the transformed values are rounded with one v_cvt_pk_f16_f32 per channel pair and position and parked in ONE
 //     fp16 plane [position][k half][k pair][tile]: 16 KB per chunk.  The word index inside the plane is conv_wino2h.cpp's (the piece
 //     was the outermost index, 4096 words = a multiple of the 64 banks), so the bank pattern of its stores and reads is unchanged.
-//   * a value beyond the fp16 range becomes Inf, the accumulator NaN: the library keeps raw tensors away (model.cpp: range guard).
+//   * a value beyond the fp16 range becomes Inf, the accumulator NaN: the library keeps raw tensors away (model.cpp: range guard)
+//     and its non-finite scan reports the normalised ones that get there all the same (behind a SPADE norm: H1_ACT_SCALE below).
 // Everything else -- region of 8 x 16 output pixels = 32 tiles or two 8x8 images (G8), 32*COT output channels, 16 input channels per
 // chunk, 512 threads = two waves per SIMD in opposite phase, one barrier per chunk, the XCD block-id map, the K split, the epilogue
 // with its GroupNorm partials, in-flight data in named registers and hand-counted vmcnt -- is conv_wino2h.cpp's, which has the story.
@@ -41,12 +42,20 @@ constexpr int H1_T = 32;         // tiles per workgroup (4 x 8 tiles = 8 x 16 ou
 constexpr int H1_NT = 512;
 constexpr int H1_PP = 24;        // LDS patch row pitch (conv_wino.cpp: WR_PP)
 constexpr int H1_VW = 16 * 2 * 4 * H1_T;          // 32-bit words of one V chunk: [position][half][pair][tile]
+constexpr int H1_MINCH_K4 = 3;  // chunks per part of the 4-way K split, at least: the prologue requests the raw patches of THREE chunks (c_begin,
+                                 // c_begin + 1, c_begin + 2) before the first MFMA, and the loop keeps that distance.  In a shorter part the third
+                                 // request (clamped, in bounds) fetches and activates a chunk of the NEXT part -- work another workgroup does
+                                 // already, on the critical path of a part that has one or two chunks of its own to hide it behind: four such
+                                 // parts pay the prologue four times for nothing.  (Id 25, the 2-way form, keeps the rule it was tuned under: two chunks.)
 constexpr int H1_HDR = 4;        // header floats in front of the packed weight pieces: |w|max, scale, 1 / scale, -
 constexpr float H1_ACT_SCALE = 16.0f;             // activations enter the patch times 2^4 (exact): transformed values of the
                                                   // order 10..1e3, clear of the fp16 denormal range (conv_wino2h.cpp).  |B^T d B| must
-                                                  // stay below 65504 / 16 ~ 4094 (GroupNorm-ed inputs -- the only ones the library
-                                                  // gives this kernel -- cannot get there); beyond it the result is NaN, not a
-                                                  // saturated number
+                                                  // stay below 65504 / 16 ~ 4094, hence |d| < 65504 / 64 ~ 1023 (|B^T d B| <= 4 max|d|).  The
+                                                  // library gives this kernel normalised inputs only: GroupNorm-ed ones through the
+                                                  // prologue, SPADE-normalised ones as the tensor spade_apply materialises (PRO 0).  The
+                                                  // first cannot get there; the second can where the cond-derived gamma / beta are
+                                                  // huge.  Beyond it the result is NaN, not a saturated number, and the model's
+                                                  // non-finite scan reports it (MCVD_ERANGE)
 
 // (lo, hi) -> packed fp16 pair, round to nearest even (v_cvt_pk_f16_f32)
 __device__ __forceinline__ unsigned h1_cvt_pk(float lo, float hi) {
@@ -54,7 +63,8 @@ __device__ __forceinline__ unsigned h1_cvt_pk(float lo, float hi) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2));
 }
 // PRO: 0 raw input, 1 affine, 2 affine + SiLU (the GroupNorm / temb prologue of conv_wino.cpp)
-// a.ksplit == 2 (grid.y = 2): half of the input channels per workgroup, raw partial result to a.part[half] (conv_wino.cpp).
+// a.ksplit == 2 / 4 (grid.y = that many): one part of the input channels per workgroup, raw partial result to a.part[part]; the reduce
+//     pass of conv_wino.cpp sums the parts in a fixed order.
 // G8: 8x8 images -- the 32 tiles of a workgroup are TWO whole images (16 tiles each, image i at patch columns 10 i .. 10 i + 9); every
 //     halo element is zero padding, so only the 2 x 64 interior pixels per channel are loaded (slots 0-3 of the six; the other two
 //     fetch a dummy) and the halo of both patch buffers is zeroed once.  The coefficient table holds both samples.
@@ -311,9 +321,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][ct][r] = 0.0f;
 
-    // ---- chunk range of this workgroup (a.ksplit == 2: blockIdx.y picks one half of the input channels)
+    // ---- chunk range of this workgroup (a.ksplit == 2 / 4: blockIdx.y picks one part of the input channels)
     const int nch_all = a.CinP / CK;
-    const int ksp = a.ksplit == 2 ? 2 : 1, kh = ksp == 2 ? (int)blockIdx.y : 0;
+    const int ksp = a.ksplit >= 2 ? a.ksplit : 1, kh = ksp >= 2 ? (int)blockIdx.y : 0;          // 2 or 4 parts of the input channels
     const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
 
     // ---- prologue (conv_wino2h.cpp).  Issue order = need order: the coefficients of the sample (into the registers of the third patch), the
@@ -557,7 +567,7 @@ static int wino1h_launch2(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
     const size_t lds = wino1h_lds_bytes(a.Cin, G8);
     const int nreg = G8 ? (a.B + 1) / 2 : a.B * (a.H / 8) * (a.W / 16);
-    const int ksp = a.ksplit == 2 ? 2 : 1;
+    const int ksp = a.ksplit >= 2 ? a.ksplit : 1;
     dim3 grid(((nreg + 7) / 8) * 8 * (a.CoutP / BCO), ksp);
     static PerDeviceOnce raised;
     if (raised.first_use()) {
@@ -567,7 +577,7 @@ static int wino1h_launch2(const ConvArgs& a, hipStream_t s) {
     }
     hipLaunchKernelGGL((conv_wino1h_kernel<COT, PRO, G8>), grid, dim3(H1_NT), lds, s, a);
     MCVD_HIP_CHECK(hipGetLastError());
-    if (ksp == 2) return launch_wino_ksplit_reduce(a, s);
+    if (ksp >= 2) return launch_wino_ksplit_reduce(a, s);
     if (a.stats) set_last_conv_stats_np(G8 ? 1 : (a.H / 8) * (a.W / 16));
     return 0;
 }
@@ -584,14 +594,17 @@ static int wino1h_launch(const ConvArgs& a, hipStream_t s) {
     return (a.H == 8 && a.W == 8) ? wino1h_launch1<COT, true>(a, s) : wino1h_launch1<COT, false>(a, s);
 }
 
-// Shape ids 24 / 25 apply to this launch: regions of 8 x 16 output pixels or 8 x 8 images (two per workgroup), no SPADE prologue,
-// conv_wino2h.cpp's packed weight pieces present (25: and an even chunk count).
+// Shape ids 24 / 25 / 27 apply to this launch: regions of 8 x 16 output pixels or 8 x 8 images (two per workgroup), no SPADE prologue,
+// conv_wino2h.cpp's packed weight pieces present (25: and an even chunk count, two chunks per part at least; 27: a chunk count that
+// divides by 4, H1_MINCH_K4 chunks per part at least; both: room for the parts in a.part).
 bool conv_wino1h_usable(const ConvArgs& a) {
     const bool g8 = a.H == 8 && a.W == 8;
+    const int nch = a.CinP / H1_CK;
     return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= 1024 &&
            a.CinP % H1_CK == 0 && (a.C1 == 0 || a.C0 % H1_CK == 0) && a.H * a.W <= 16384 &&
            (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino1h_lds_bytes(a.Cin, g8) <= 160 * 1024 &&
-           (a.ksplit != 2 || ((a.CinP / H1_CK) % 2 == 0 && a.CinP / H1_CK >= 4 && conv_part_fits(a)));
+           (a.ksplit < 2 || ((a.ksplit == 2 || (a.ksplit == 4 && nch / 4 >= H1_MINCH_K4)) && nch % a.ksplit == 0 && nch >= 2 * a.ksplit &&
+                             conv_part_fits(a)));
 }
 
 // a.wph: the layout of launch_pack_wino2h_weight, packed for conv_wino_cout_tile(Cout); the first piece is read.

@@ -51,12 +51,20 @@ constexpr int H2_T = 32;         // tiles per workgroup (4 x 8 tiles = 8 x 16 ou
 constexpr int H2_NT = 512;
 constexpr int H2_PP = 24;        // LDS patch row pitch (conv_wino.cpp: WR_PP)
 constexpr int H2_VW = 2 * 16 * 2 * 4 * H2_T;      // 32-bit words of one V chunk: [piece][position][half][pair][tile]
+constexpr int H2_MINCH_K4 = 3;  // chunks per part of the 4-way K split, at least: the prologue requests the raw patches of THREE chunks (c_begin,
+                                 // c_begin + 1, c_begin + 2) before the first MFMA, and the loop keeps that distance.  In a shorter part the third
+                                 // request (clamped, in bounds) fetches and activates a chunk of the NEXT part -- work another workgroup does
+                                 // already, on the critical path of a part that has one or two chunks of its own to hide it behind: four such
+                                 // parts pay the prologue four times for nothing.  (Id 13, the 2-way form, keeps the rule it was tuned under: two chunks.)
 constexpr int H2_HDR = 4;        // header floats in front of the packed weight pieces: |w|max, scale, 1 / scale, -
 constexpr float H2_ACT_SCALE = 16.0f;             // activations enter the patch times 2^4 (exact): transformed values of the
                                                   // order 10..1e3, second pieces clear of the fp16 denormal range.  |B^T d B| must
-                                                  // stay below 65504 / 16 ~ 4094 (GroupNorm-ed inputs -- the only ones the library
-                                                  // gives this kernel -- cannot get there); beyond it the result is NaN, not a
-                                                  // saturated number
+                                                  // stay below 65504 / 16 ~ 4094, hence |d| < 65504 / 64 ~ 1023 (|B^T d B| <= 4 max|d|).  The
+                                                  // library gives this kernel normalised inputs only: GroupNorm-ed ones through the
+                                                  // prologue, SPADE-normalised ones as the tensor spade_apply materialises (PRO 0).  The
+                                                  // first cannot get there; the second can where the cond-derived gamma / beta are
+                                                  // huge.  Beyond it the result is NaN, not a saturated number, and the model's
+                                                  // non-finite scan reports it (MCVD_ERANGE)
 
 // (lo, hi) -> packed fp16 pair, round to nearest even (v_cvt_pk_f16_f32)
 __device__ __forceinline__ unsigned h2_cvt_pk(float lo, float hi) {
@@ -76,7 +84,8 @@ __device__ __forceinline__ void h2_split2(f32x2 v, unsigned& w1, unsigned& w2) {
 }
 
 // PRO: 0 raw input, 1 affine, 2 affine + SiLU (the GroupNorm / temb prologue of conv_wino.cpp)
-// a.ksplit == 2 (grid.y = 2): half of the input channels per workgroup, raw partial result to a.part[half] (conv_wino.cpp).
+// a.ksplit == 2 / 4 (grid.y = that many): one part of the input channels per workgroup, raw partial result to a.part[part]; the reduce
+//     pass of conv_wino.cpp sums the parts in a fixed order.
 // EXP != 0 (built with -DMCVD_DIAG only): timing-only ablations of the K loop (wrong results; env MCVD_WINO2H_EXP, tests/gpu_diag.py w3exp): bit 0 no tile
 //     transform, bit 1 no patch activation/park, bit 2 no VMEM in the loop, bit 3 no B-operand reads, bit 4 no MFMA.
 // G8: 8x8 images -- the 32 tiles of a workgroup are TWO whole images (16 tiles each, image i at patch columns 10 i .. 10 i + 9); every
@@ -370,9 +379,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         tprev = now;                                                                                            \
     }
 
-    // ---- chunk range of this workgroup (a.ksplit == 2: blockIdx.y picks one half of the input channels)
+    // ---- chunk range of this workgroup (a.ksplit == 2 / 4: blockIdx.y picks one part of the input channels)
     const int nch_all = a.CinP / CK;
-    const int ksp = a.ksplit == 2 ? 2 : 1, kh = ksp == 2 ? (int)blockIdx.y : 0;
+    const int ksp = a.ksplit >= 2 ? a.ksplit : 1, kh = ksp >= 2 ? (int)blockIdx.y : 0;          // 2 or 4 parts of the input channels
     const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
 
     // ---- prologue.  Issue order = need order: the coefficients of the sample (into the registers of the third patch), the raw patches of
@@ -651,7 +660,7 @@ static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
     const size_t lds = wino2h_lds_bytes(a.Cin, G8);
     const int nreg = G8 ? (a.B + 1) / 2 : a.B * (a.H / 8) * (a.W / 16);
-    const int ksp = a.ksplit == 2 ? 2 : 1;
+    const int ksp = a.ksplit >= 2 ? a.ksplit : 1;
     dim3 grid(((nreg + 7) / 8) * 8 * (a.CoutP / BCO), ksp);
     ConvArgs k = a;
     int rc = 0;
@@ -684,7 +693,7 @@ static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
     }
     if (rc) return rc;
     MCVD_HIP_CHECK(hipGetLastError());
-    if (ksp == 2) return launch_wino_ksplit_reduce(a, s);
+    if (ksp >= 2) return launch_wino_ksplit_reduce(a, s);
     if (a.stats) set_last_conv_stats_np(G8 ? 1 : (a.H / 8) * (a.W / 16));
     return 0;
 }
@@ -701,14 +710,17 @@ static int wino2h_launch(const ConvArgs& a, hipStream_t s) {
     return (a.H == 8 && a.W == 8) ? wino2h_launch1<COT, true>(a, s) : wino2h_launch1<COT, false>(a, s);
 }
 
-// Shape ids 12 / 13 apply to this launch: regions of 8 x 16 output pixels or 8 x 8 images (two per workgroup), no SPADE prologue,
-// pre-split packed weights present (13: and an even chunk count).
+// Shape ids 12 / 13 / 26 apply to this launch: regions of 8 x 16 output pixels or 8 x 8 images (two per workgroup), no SPADE prologue,
+// pre-split packed weights present (13: and an even chunk count, two chunks per part at least; 26: a chunk count that divides by 4,
+// H2_MINCH_K4 chunks per part at least; both: room for the parts in a.part).
 bool conv_wino2h_usable(const ConvArgs& a) {
     const bool g8 = a.H == 8 && a.W == 8;
+    const int nch = a.CinP / H2_CK;
     return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= 1024 &&
            a.CinP % H2_CK == 0 && (a.C1 == 0 || a.C0 % H2_CK == 0) && a.H * a.W <= 16384 &&
            (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino2h_lds_bytes(a.Cin, g8) <= 160 * 1024 &&
-           (a.ksplit != 2 || ((a.CinP / H2_CK) % 2 == 0 && a.CinP / H2_CK >= 4 && conv_part_fits(a)));
+           (a.ksplit < 2 || ((a.ksplit == 2 || (a.ksplit == 4 && nch / 4 >= H2_MINCH_K4)) && nch % a.ksplit == 0 && nch >= 2 * a.ksplit &&
+                             conv_part_fits(a)));
 }
 
 // a.wph: the layout of launch_pack_wino2h_weight, packed for conv_wino_cout_tile(Cout).

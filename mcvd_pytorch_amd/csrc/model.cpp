@@ -809,7 +809,7 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
                 // f16x2 is off -- and for convs with a raw input in any case (f16x2 range guard, below); bf16x3 hints go to the fp32-MFMA
                 // kernels when bf16x3 is off; one-piece hints go to their bf16x3 counterparts when f16x1 is off or the input is raw, in
                 // front of the bf16x3 remap (conv_kernels.h: no_f16x2 / no_f16x1 / no_bf16x3)
-                const bool raw_in = op.coef.kind == REF_NONE;
+                const bool raw_in = conv_input_raw(op);
                 if ((!ctx->f16x1 || raw_in) && without_f16x1(a.shape_hint) != a.shape_hint) a.shape_hint = without_f16x1(a.shape_hint);
                 if ((!ctx->f16x2 || raw_in) && without_f16x2(a.shape_hint) != a.shape_hint) {
                     a.shape_hint = without_f16x2(a.shape_hint);
@@ -1098,32 +1098,43 @@ int mcvd_model::autotune(int B) {
             }
             if (op.ks == 3 && ctx->winograd)               // the K split fills the CUs on 8x8 layers
                 if (int rc = offer(CK_WINO_K2, op.cot)) return rc;
+            // (region, cout tile) pairs of a Winograd launch: few of them leave CUs idle, and the deeper K splits are offered
+            const bool g8 = op.H == 8 && op.W == 8;
+            const long pairs = op.ks == 3 ? (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout))) : 0;
+            const bool few_pairs = op.ks == 3 && 2 * pairs < 1024;
             if (op.ks == 3 && ctx->winograd && ctx->bf16x3 && !spade_fused) {     // Winograd on the bf16 pipe, three exact pieces per operand
                 for (int id : {CK_WINO3, CK_WINO3_K2, CK_WINO3P, CK_WINO3P_K2})    // (persistent: the staging pipeline runs on across the items of a CU)
                     if (int rc = offer(id, op.cot)) return rc;
                 // 4 / 8 K parts are offered where the 2-way split leaves the chip with less than a few workgroups per CU (the measurement
                 // decides; above that the reduce pass only costs)
-                const bool g8 = op.H == 8 && op.W == 8;
-                const long pairs = (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout)));
-                if (2 * pairs < 1024) {
+                if (few_pairs) {
                     for (int id : {CK_WINO3_K4, CK_WINO3P_K4})
                         if (int rc = offer(id, op.cot)) return rc;
                     if (4 * pairs < 1024)
                         if (int rc = offer(CK_WINO3_K8, op.cot)) return rc;
                 }
             }
-            // f16x2 range guard: the two-piece fp16 kernels see GroupNorm-ed inputs only (a.coef set: normalised, O(1) by construction).
-            // A conv over a RAW tensor (stem, shortcuts, NIN_3) has no bound on its input and stays on the fp32-range kernels.
-            const bool f16_ok = ctx->f16x2 && a.coef != nullptr;
-            if (op.ks == 3 && ctx->winograd && f16_ok && !spade_fused)            // Winograd on the fp16 pipe, two-piece operands
+            // f16x2 range guard: the two-piece fp16 kernels see NORMALISED inputs only -- GroupNorm-ed (a.coef set: O(1) by construction) or
+            // SPADE-normalised, which here is the tensor spade_apply materialises (a.coef == nullptr at the launch, and as bounded as the
+            // other up to the cond-derived gamma / beta: an overflow there ends as NaN in eps, which the non-finite scan reports as
+            // MCVD_ERANGE).  A conv over a RAW tensor (stem, shortcuts, NIN_3, the SPADE prep convs) has no bound on its input and stays on
+            // the fp32-range kernels.  With spade_fuse = 1 the modulation stays in the fp32 Winograd loader: no fp16 kernel has that loader.
+            const bool f16_ok = ctx->f16x2 && !conv_input_raw(op);
+            if (op.ks == 3 && ctx->winograd && f16_ok && !spade_fused) {          // Winograd on the fp16 pipe, two-piece operands
                 for (int id : {CK_WINO2H, CK_WINO2H_K2})
                     if (int rc = offer(id, op.cot)) return rc;
+                if (few_pairs)                                                    // (the 4-way split: where the three-piece kernel is offered it)
+                    if (int rc = offer(CK_WINO2H_K4, op.cot)) return rc;
+            }
             // ... one-piece operands (the draft arithmetic "f16x1"): the same convs, under the same guard.  The 1x1 GEMMs below and the
             // attention have no one-piece form: they stay where f16x2 / bf16x3 put them
-            const bool f16x1_ok = ctx->f16x1 && a.coef != nullptr;
-            if (op.ks == 3 && ctx->winograd && f16x1_ok && !spade_fused)
+            const bool f16x1_ok = ctx->f16x1 && !conv_input_raw(op);
+            if (op.ks == 3 && ctx->winograd && f16x1_ok && !spade_fused) {
                 for (int id : {CK_WINO1H, CK_WINO1H_K2})
                     if (int rc = offer(id, op.cot)) return rc;
+                if (few_pairs)
+                    if (int rc = offer(CK_WINO1H_K4, op.cot)) return rc;
+            }
             if (op.ks == 1 && ctx->conv_dma1) {        // the 1x1 GEMMs, cout tiles of their own
                 // small cout tiles first: the sweep of every 1x1 layer shape (profiles/r02_conv1x1_candidates.txt) has tiles 1-3 winning
                 // everywhere; 6 / 9 never did

@@ -141,6 +141,13 @@ struct Op {
     int gn_src = -1;               // consumers of GroupNorm coefficients (conv, FIR, SPADE apply): the plan's OP_GN that computes `coef`
 };
 
+// The range guard of the fp16 arithmetics (options f16x2 / f16x1) asks one question of a conv: is its input RAW -- no norm in front, so
+// no bound on it (the stem, the shortcuts, NIN_3, the convs behind a FIR resampler, the cond-only SPADE prep convs)?  Not raw: a GroupNorm
+// in front (coef, applied in the kernel's prologue) or a SPADE norm (gb), whether the Winograd loader modulates or spade_apply has
+// materialised silu(((A x + B)(1 + gamma) + beta) s1 + b2) -- as the launch sees it that tensor has no coefficients, but it is a
+// normalised value all the same.  autotune() and the remap of an imported table both ask here, of the PLAN's op, not of the launch.
+inline bool conv_input_raw(const Op& op) { return op.coef.kind == REF_NONE && op.gb.kind == REF_NONE; }
+
 struct DenseEntry {
     std::string weight, bias;
     int ch;

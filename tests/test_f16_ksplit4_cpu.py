@@ -1,0 +1,83 @@
+"""CPU: the 4-way K split of the two fp16 Winograd kernels (shape ids 26 / 27; conv_wino2h.cpp, conv_wino1h.cpp) -- the partition of the
+16-channel chunks into parts and the rule that admits a layer, restated here and walked over every layer shape up to 1024 channels.
+
+The kernels: `nch = CinP / 16` chunks; workgroup (.., blockIdx.y = part) contracts chunks [part * nch / 4, (part + 1) * nch / 4) and writes its raw
+partial result to a.part[part]; chunk c reads channels 16 c .. 16 c + 15 from x0 when 16 c < C0, else from x1 (one source per chunk).
+usable(): nch % 4 == 0, nch / 4 >= MINCH_K4 = 3 (the prologue requests the patches of three chunks; a shorter part would fetch its
+neighbour's), no chunk across the concat seam (C1 == 0 or C0 % 16 == 0), Cin <= 1024 -- and room for four partial results, which is the
+caller's buffer and not restated here.  The table rows and static_asserts of conv_kernels.h are checked by every build of the library.
+"""
+import os
+import re
+
+CK = 16
+MINCH_K4 = 3
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "mcvd_pytorch_amd", "csrc")
+
+
+def usable_k4(Cin, CinP, C0, C1):
+    nch = CinP // CK
+    return (Cin <= 1024 and CinP % CK == 0 and (C1 == 0 or C0 % CK == 0)
+            and nch % 4 == 0 and nch >= 2 * 4 and nch // 4 >= MINCH_K4)
+
+
+def parts(nch, ksp):
+    """[(c_begin, c_end)] per blockIdx.y, the kernels' expression."""
+    return [(kh * (nch // ksp), kh * (nch // ksp) + nch // ksp) for kh in range(ksp)]
+
+
+def chunk_source(c, Cin, C0):
+    """The source the loader picks for chunk c (LOAD_PR: cb = min(c * CK, Cin - 1); second = cb >= C0)."""
+    return 1 if min(c * CK, Cin - 1) >= C0 else 0
+
+
+def test_the_restated_minimum_is_the_kernels():
+    for f, name in (("conv_wino1h.cpp", "H1_MINCH_K4"), ("conv_wino2h.cpp", "H2_MINCH_K4")):
+        src = open(os.path.join(CSRC, "kernels", f)).read()
+        m = re.search(r"constexpr int %s = (\d+);" % name, src)
+        assert m and int(m.group(1)) == MINCH_K4, (f, m and m.group(0))
+        assert re.search(r"a\.ksplit == 4 && nch / 4 >= %s" % name, src), f"{f}: usable() does not state the minimum"
+    table = open(os.path.join(CSRC, "conv_kernels.h")).read()
+    assert "CK_WINO2H_K4 = 26" in table and "CK_WINO1H_K4 = 27" in table
+
+
+def test_every_admitted_layer_is_partitioned_soundly():
+    admitted = seam_inside_a_part = 0
+    for CinP in range(CK, 1024 + 1, CK):
+        for Cin in sorted({CinP, CinP - 7, CinP - CK + 1}):         # full last chunk, padded ones
+            for C0 in range(1, Cin + 1):
+                C1 = Cin - C0
+                if not usable_k4(Cin, CinP, C0, C1):
+                    continue
+                admitted += 1
+                nch = CinP // CK
+                pp = parts(nch, 4)
+                owner = [0] * nch
+                for b, e in pp:
+                    assert e - b >= MINCH_K4, (CinP, b, e)
+                    assert 0 <= b < e <= nch
+                    for c in range(b, e):
+                        owner[c] += 1
+                    # the three patches the prologue requests are this part's own chunks
+                    assert b + 2 < e
+                assert owner == [1] * nch, (CinP, pp)
+                for c in range(nch):                                  # every channel of a chunk comes from the source the loader picks
+                    lo, hi = c * CK, min(c * CK + CK, Cin)
+                    if lo >= Cin:
+                        continue
+                    src = chunk_source(c, Cin, C0)
+                    assert all((ch >= C0) == bool(src) for ch in (lo, hi - 1)), (Cin, C0, c)
+                if C1 and any(b * CK < C0 < e * CK for b, e in pp):
+                    seam_inside_a_part += 1
+    assert admitted > 1000 and seam_inside_a_part > 100, (admitted, seam_inside_a_part)
+
+
+def test_the_rule_refuses_what_it_must():
+    assert usable_k4(192, 192, 192, 0)                      # 12 chunks: the shortest admissible parts
+    assert not usable_k4(128, 128, 128, 0)                  # 8 chunks: parts of two, shorter than the prologue's three requests
+    assert not usable_k4(288, 288, 288, 0)                  # 18 chunks: not divisible by 4
+    assert not usable_k4(256, 256, 100, 156)                # the seam inside a chunk
+    assert usable_k4(256, 256, 160, 96)                     # the seam inside a part (chunk 10 of 16), on a chunk boundary
+    assert not usable_k4(1040, 1040, 1040, 0)               # beyond the coefficient table
+    assert usable_k4(250, 256, 250, 0)                      # a padded last chunk
