@@ -165,8 +165,11 @@ int mcvd_ctx_set_stream(mcvd_ctx* ctx, void* hip_stream);
  *     "conv_shape1" (-1): the same for the 1x1 convs only (they follow "conv_shape" otherwise), so that a test can put every 3x3 AND
  *         every 1x1 conv of a model on chosen kernels at once.  "conv_cot": cout tile (32-channel units) mcvd_op_conv2d requests with
  *         conv_shape 5 / 6 / 9 / 14 / 15.
- *     "naive_attn": 0 auto (three-piece bf16 flash kernel for head dims 32..128, two-piece fp16 when "f16x2" is on, else the fp32 flash
- *         kernel), 1 one-thread-per-query test kernel, 2 fp32 flash kernel, 3 / 4 force the two-piece fp16 / three-piece bf16 kernel.
+ *     "naive_attn": 0 auto (three-piece bf16 flash kernels -- head dims 32..128, and the wide-head kernel for 160..1024, which divides
+ *         the head dim over the waves of a workgroup: n_head_channels = -1 on a wide level; in 160..256 beyond 256 tokens the fp32 flash
+ *         kernel, which measured faster there -- two-piece fp16 when "f16x2" is on, else the fp32 flash kernel), 1 one-thread-per-query test kernel, 2 fp32 flash kernel (head dims up to 256; beyond: the one-thread-per-query
+ *         kernel), 3 / 4 force the two-piece fp16 / three-piece bf16 kernels where one applies.  A head dim or a token count that is no
+ *         multiple of 32 runs the one-thread-per-query kernel under every value.  mcvd_last_attention_kernel reports what ran.
  *     "naive_conv" (0/1): one-thread-per-output conv kernel (tests triangulate with it).
  *     "winograd" / "conv_dma1" (1): offer the Winograd / all-DMA 1x1 kernels to the autotuner.  "conv_wdma" (1: direct-conv weight chunks
  *         by LDS-DMA, 0: register staging).
@@ -312,6 +315,9 @@ int mcvd_model_op_info(mcvd_model* m, int i, int info[8]);
  * 15 three-piece bf16 1x1 GEMM; -2 the one-thread-per-output test kernel); -1 for an op that is not a conv or never ran.  Tests
  * use it to assert that a forced or imported kernel table is what executed (a graph replay re-runs what its capture recorded). */
 int mcvd_model_op_kernel(mcvd_model* m, int i);
+
+/* The kernel attention op i ran in the last forward (the numbers of mcvd_last_attention_kernel); -1 for any other op or one that never ran. */
+int mcvd_model_op_attention_kernel(mcvd_model* m, int i);
 
 /* Launch counters of the fused forms that have no reference counterpart (diagnostics / tests), cumulative over the model's forwards:
  * what = 0: attention blocks whose K and V went from the q|k|v projection to the attention kernel pre-split (option "attn_presplit",
@@ -575,6 +581,11 @@ int mcvd_op_resize299(mcvd_ctx* ctx, const float* x, int64_t n, int H, int W, in
  * Winograd, 12 / 13 two-piece fp16 Winograd, 14 / 15 split-operand 1x1 GEMM); -1 none yet.  A forced "conv_shape" that does not apply to a
  * launch falls back -- tests use this to assert what really ran (per op of a model: mcvd_model_op_kernel). */
 int mcvd_last_conv_kernel(void);
+/* Which attention kernel the calling thread's last attention launch (mcvd_op_attention or a model forward) ran: 0 one thread per query,
+ * 1 fp32 flash (head dims 32..256), 2 / 3 two-piece fp16 / three-piece bf16 flash (head dims 32..128), 4 three-piece fed with K / V
+ * pre-split by the q|k|v projection (a model forward only), 5 / 6 two-piece / three-piece wide-head kernel (head dims 160..1024);
+ * -1 none yet.  Numbers are never reused. */
+int mcvd_last_attention_kernel(void);
 /* SPADE prologue of the Winograd conv kernel (layerspp.py:164-171, :530-535): while set (non-NULL gb), mcvd_op_conv2d computes
  * conv(silu(((A x + B)(1 + gamma) + beta) * s1 + b2)) with (A, B) = coef, gamma | beta = gb:[B, 2*Cin, H, W] and (s1, b2) =
  * coef2:[B, Cin, 2] (NULL: (1, 0)); needs conv_shape 4 or 8, ks 3, coef and act.  Inside a model forward this is what a SPADE net's

@@ -70,6 +70,7 @@ _PROTOS = {
     "mcvd_model_set_tuning": (_i, [_vp, _i, _vp, _vp, _i]),
     "mcvd_model_graph_stats": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "mcvd_last_conv_kernel": (_i, []),
+    "mcvd_last_attention_kernel": (_i, []),
     "mcvd_last_conv_stats_np": (_i, []),
     "mcvd_ctx_set_stats_buffer": (_i, [_vp, _vp]),
     "mcvd_ctx_set_spade_inputs": (_i, [_vp, _vp, _vp]),
@@ -77,6 +78,7 @@ _PROTOS = {
     "mcvd_model_profile_read": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "mcvd_model_op_info": (_i, [_vp, _i, C.POINTER(_i)]),
     "mcvd_model_op_kernel": (_i, [_vp, _i]),
+    "mcvd_model_op_attention_kernel": (_i, [_vp, _i]),
     "mcvd_model_fused_launches": (C.c_long, [_vp, _i]),
     "mcvd_model_module_output": (_i, [_vp, _i, _i, _vp, _i64, C.POINTER(_i), C.POINTER(_i)]),
     "mcvd_sampler_run": (_i, [_vp, _i, _vp, _vp, _vp, _u64, _u64, _i, _i, C.c_double, _i]),

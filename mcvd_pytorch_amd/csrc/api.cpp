@@ -873,6 +873,11 @@ int mcvd_model_op_kernel(mcvd_model* m, int i) {
     return m->ran_kernel[i];
 }
 
+int mcvd_model_op_attention_kernel(mcvd_model* m, int i) {
+    if (!m || i < 0 || i >= (int)m->ops.size() || m->ops[i].kind != OP_ATTN || (size_t)i >= m->ran_attn.size()) return -1;
+    return m->ran_attn[i];
+}
+
 long mcvd_model_fused_launches(mcvd_model* m, int what) { return (m && what >= 0 && what < 4) ? m->fused_launches[what] : -1; }
 
 int mcvd_model_module_output(mcvd_model* m, int module, int B, float* dst, int64_t capacity, int* C, int* H) {
@@ -1531,6 +1536,8 @@ int mcvd_op_conv2d(mcvd_ctx* ctx, const float* x0, int C0, const float* x1, int 
 }
 
 int mcvd_last_conv_kernel(void) { return last_conv_kernel(); }
+
+int mcvd_last_attention_kernel(void) { return last_attention_kernel(); }
 
 int mcvd_last_conv_stats_np(void) { return last_conv_stats_np(); }
 

@@ -213,7 +213,7 @@ int launch_gn_coef(const GnArgs& a, hipStream_t s);
 int launch_gn_finalize(const GnArgs& a, const float* st0, int np0, const float* st1, int np1, hipStream_t s);
 
 // ------------------------------------------------------------------ attention
-bool attention_mfma_supported(int C, int heads, int HW);      // head dim 32..256 in steps of 32, HW % 32 == 0; else the general kernel
+bool attention_mfma_supported(int C, int heads, int HW);      // head dim 32..256 in steps of 32, HW % 32 == 0
 int launch_attention_mfma(const float* qkv, float* out, int B, int C, int heads, int HW, hipStream_t s);
 int launch_attention_naive(const float* qkv, float* out, int B, int C, int heads, int HW, hipStream_t s);
 // the flash kernel on the 16-bit matrix pipes with split operands (attention_h2.cpp; np = 3 three bf16 pieces, fp32-equivalent; np = 2
@@ -224,9 +224,16 @@ int launch_attention_h2(const float* qkv, float* out, int B, int C, int heads, i
 // LDS-DMA, no VALU instruction touches them; head dims 32 / 64 / 96.  Bit-identical to launch_attention_h2(.., 3).
 bool attn_h2p_supported(int C, int heads, int HW);
 int launch_attention_h2p(const float* qkv, const float* kv_img, float* out, int B, int C, int heads, int HW, hipStream_t s);
-// which attention kernel a launch takes: mode = the "naive_attn" option (0 auto: the fp16-pipe kernel when f16x2 is on and it applies,
-// else the fp32 flash kernel; 1 the one-thread-per-query kernel; 2 the fp32 flash kernel; 3 the fp16-pipe kernel where it applies)
+// WIDE heads on the same pipes with the same arithmetic (attention_wide.cpp; np as above): the head dim is divided over the 8 waves of a
+// workgroup, which exchange partial score tiles through the LDS in a fixed order; head dim 160..1024 in steps of 32, HW % 32 == 0
+bool attention_wide_supported(int C, int heads, int HW);
+int launch_attention_wide(const float* qkv, float* out, int B, int C, int heads, int HW, hipStream_t s, int np);
+// which attention kernel a launch takes is ONE table, attn_kernels.h (attn_kernel_for): mode = the "naive_attn" option -- 0 auto (the
+// two-piece fp16 kernels when f16x2 is on, else the three-piece bf16 kernels when bf16x3 is on: attention_h2.cpp for head dims up to 128,
+// attention_wide.cpp for 160..1024; else as 2), 1 the one-thread-per-query kernel, 2 the fp32 flash kernel (head dims up to 256, else the
+// one-thread-per-query kernel), 3 / 4 the two- / three-piece kernels where one applies.  D % 32 != 0 or HW % 32 != 0: one thread per query.
 int launch_attention(int mode, int f16x2, int bf16x3, const float* qkv, float* out, int B, int C, int heads, int HW, hipStream_t s);
+int last_attention_kernel();                  // the kernel (attn_kernels.h: AttnKernel) this thread's last launch_attention / launch_attention_h2p ran; -1 none yet
 
 // ------------------------------------------------------------------ FIR resampling
 // form 0: the LDS-strip kernels where their geometry applies (power-of-two widths 8..256), else the register forms; 1: register forms only

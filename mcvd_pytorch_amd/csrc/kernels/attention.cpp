@@ -133,12 +133,10 @@ bool attention_mfma_supported(int C, int heads, int HW) {
 }
 
 int launch_attention_mfma(const float* qkv, float* out, int B, int C, int heads, int HW, hipStream_t s) {
-    MCVD_REQUIRE(heads > 0 && C % heads == 0, "attention: C=%d heads=%d", C, heads);
+    // The flash kernel keeps Q and the O accumulators of a head in registers: head dims 32..256 in steps of 32.  Which launch comes here is
+    // attn_kernels.h's decision (wider heads: attention_wide.cpp; odd widths, HW not a multiple of 32: the one-thread-per-query kernel below).
+    MCVD_REQUIRE(attention_mfma_supported(C, heads, HW), "fp32 flash attention: unsupported (C=%d heads=%d HW=%d)", C, heads, HW);
     const int D = C / heads;
-    // The flash kernel keeps Q and the O accumulators of a head in registers: head dims 32..256 in steps of 32.  Anything else
-    // (n_head_channels = -1 on a wide level -> one head of C channels, layerspp.py:219-228; odd widths; HW not a multiple of 32)
-    // runs the general one-thread-per-query kernel: correct for every shape, far slower.
-    if (!attention_mfma_supported(C, heads, HW)) return launch_attention_naive(qkv, out, B, C, heads, HW, s);
     const float scale = (float)pow((double)D, -0.5);   // int(C)**-0.5 as a Python double, then fp32 (layerspp.py:239)
     dim3 grid((HW + 127) / 128, B * heads);
     const size_t lds = (size_t)D * (32 + 33) * sizeof(float);

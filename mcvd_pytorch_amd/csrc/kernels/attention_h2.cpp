@@ -27,10 +27,12 @@
 //         operand with four conflict-free ds_read_b32.
 //       V pieces stay in operand order [sub-tile][step][piece][64 lanes][4 dwords] (one ds_read_b128 per operand); the staging lanes
 //         are permuted (lane = g | row << 1 | h << 4 | s2 << 5) so that 16 consecutive lanes write 128 contiguous bytes.
-// Head dims 32..128 (Q pieces + O accumulators + the register prefetch of the next tile fit two waves per SIMD); anything else stays
-// on attention.cpp.
+// Head dims 32..128 (Q pieces + O accumulators + the register prefetch of the next tile fit two waves per SIMD); wider heads divide the
+// head dim over the waves of a workgroup (attention_wide.cpp, 160..1024), anything else stays on attention.cpp.  Which kernel a launch
+// takes: attn_kernels.h.
 #include <math.h>
 
+#include "../attn_kernels.h"
 #include "../common.h"
 #include "pieces.h"
 
@@ -439,6 +441,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_h2p_kernel(const float* __res
     }
 }
 
+static thread_local int g_last_attention_kernel = -1;      // the AttnKernel this thread's last launch ran
+int last_attention_kernel() { return g_last_attention_kernel; }
+
 bool attn_h2p_supported(int C, int heads, int HW) {
     if (heads <= 0 || C % heads != 0) return false;
     const int D = C / heads;
@@ -454,6 +459,7 @@ int launch_attention_h2p(const float* qkv, const float* kv_img, float* out, int 
     const int nqt = (HW + 32 * NWq - 1) / (32 * NWq), nbh = B * heads;
     dim3 grid((unsigned)(((nbh + 7) / 8) * 8 * nqt));
     const size_t lds = (size_t)2 * 3072 * (D / 32) * sizeof(unsigned);
+    g_last_attention_kernel = AK_SPLIT3_PRESPLIT;
     const unsigned* img = reinterpret_cast<const unsigned*>(kv_img);
 #define AHP_CASE(DT, NW)                                                                                                  \
     case DT: {                                                                                                            \
@@ -505,15 +511,18 @@ int launch_attention_h2(const float* qkv, float* out, int B, int C, int heads, i
     return np == 2 ? attn_h2_launch<2>(qkv, out, B, C, heads, HW, s) : attn_h2_launch<3>(qkv, out, B, C, heads, HW, s);
 }
 
-// mode = the "naive_attn" option: 0 auto (the split-operand kernel where it applies: two fp16 pieces when f16x2 is on, else three bf16
-// pieces when bf16x3 is on; else the fp32 flash kernel), 1 the one-thread-per-query kernel, 2 the fp32 flash kernel, 3 two fp16 pieces
-// where the kernel applies, 4 three bf16 pieces where it applies
+// mode = the "naive_attn" option; which kernel it means for a shape is attn_kernels.h's table (attn_kernel_for), here it is launched
 int launch_attention(int mode, int f16x2, int bf16x3, const float* qkv, float* out, int B, int C, int heads, int HW, hipStream_t s) {
-    if (mode == 1) return launch_attention_naive(qkv, out, B, C, heads, HW, s);
-    const bool sup = attention_h2_supported(C, heads, HW);
-    if (sup && (mode == 3 || (mode == 0 && f16x2))) return launch_attention_h2(qkv, out, B, C, heads, HW, s, 2);
-    if (sup && (mode == 4 || (mode == 0 && bf16x3))) return launch_attention_h2(qkv, out, B, C, heads, HW, s, 3);
-    return launch_attention_mfma(qkv, out, B, C, heads, HW, s);
+    const AttnKernel k = attn_kernel_for(mode, f16x2, bf16x3, C, heads, HW);
+    g_last_attention_kernel = k;
+    switch (k) {
+        case AK_FLASH_F32: return launch_attention_mfma(qkv, out, B, C, heads, HW, s);
+        case AK_SPLIT2: return launch_attention_h2(qkv, out, B, C, heads, HW, s, 2);
+        case AK_SPLIT3: return launch_attention_h2(qkv, out, B, C, heads, HW, s, 3);
+        case AK_WIDE2: return launch_attention_wide(qkv, out, B, C, heads, HW, s, 2);
+        case AK_WIDE3: return launch_attention_wide(qkv, out, B, C, heads, HW, s, 3);
+        default: return launch_attention_naive(qkv, out, B, C, heads, HW, s);
+    }
 }
 
 }  // namespace mcvd

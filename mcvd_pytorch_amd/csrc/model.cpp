@@ -977,14 +977,20 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
             // stream of this one -- keeps the split-operand attention kernels off it: api.cpp, mcvd_ctx_shares_device)
             const bool shared = ctx->share_fence && mcvd_ctx_shares_device(ctx);
             const size_t ai = (size_t)(&op - ops.data());
+            if (ran_attn.size() != ops.size()) ran_attn.assign(ops.size(), -1);
+            int rc;
             if (ai < kv_live.size() && kv_live[ai]) {                     // K and V were written pre-split by the projection of this forward
                 kv_live[ai] = 0;
                 ++fused_launches[0];
-                return launch_attention_h2p(resolve(op.src0, x, cond, out, B), resolve(op.kv, x, cond, out, B), resolve(op.dst, x, cond, out, B), B,
-                                            op.Cout, op.heads, op.H * op.W, s);
+                rc = launch_attention_h2p(resolve(op.src0, x, cond, out, B), resolve(op.kv, x, cond, out, B), resolve(op.dst, x, cond, out, B), B,
+                                          op.Cout, op.heads, op.H * op.W, s);
+            } else {
+                // (which kernel: attn_kernels.h, attn_kernel_for)
+                rc = launch_attention(ctx->naive_attn, shared ? 0 : ctx->f16x2, shared ? 0 : ctx->bf16x3, resolve(op.src0, x, cond, out, B), resolve(op.dst, x, cond, out, B), B,
+                                      op.Cout, op.heads, op.H * op.W, s);
             }
-            return launch_attention(ctx->naive_attn, shared ? 0 : ctx->f16x2, shared ? 0 : ctx->bf16x3, resolve(op.src0, x, cond, out, B), resolve(op.dst, x, cond, out, B), B,
-                                    op.Cout, op.heads, op.H * op.W, s);
+            ran_attn[ai] = last_attention_kernel();
+            return rc;
         }
         default:
             set_error("forward: unknown op kind %d", (int)op.kind);

@@ -234,6 +234,7 @@ struct mcvd_model {
     int launch_gn(const mcvd::Op& op, const float* x, const void* labels, const float* cond, float* out, int B);
     std::vector<int> ran_kernel;      // per conv op: the kernel family its last launch REALLY ran (last_conv_kernel(); -2 the naive kernel,
                                       //    -1 never launched): what mcvd_model_op_kernel reports
+    std::vector<int> ran_attn;        // per OP_ATTN: the kernel (attn_kernels.h: AttnKernel) its last launch ran, -1 never launched: mcvd_model_op_attention_kernel
     std::vector<int> tuned_shape, tuned_cot;
     int tuned_B = 0;
     int tuned_sig = -1;            // the kernel-offer options (winograd, conv_dma1, bf16x3, f16x2, spade_fuse, conv_wdma, f16x1) the tables were tuned under

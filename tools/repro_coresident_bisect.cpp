@@ -34,6 +34,7 @@ void set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(
 const char* get_error() { return g_err; }
 int launch_attention_naive(const float*, float*, int, int, int, int, hipStream_t) { return -1; }
 int launch_attention_mfma(const float*, float*, int, int, int, int, hipStream_t) { return -1; }
+int launch_attention_wide(const float*, float*, int, int, int, int, hipStream_t, int) { return -1; }
 }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
