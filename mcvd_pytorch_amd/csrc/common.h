@@ -149,6 +149,14 @@ int conv_kernel_launch(int id, const ConvArgs& a, hipStream_t s);
 int launch_im2col3x3(const float* x0, int C0, const float* x1, int C1, float* col, int B, int H, int W, int K, hipStream_t s);
 int launch_taps_shift_add(const float* z, const float* bias, const float* res, float scale, float* y, int B, int Cout, int H, int W, hipStream_t s);
 int launch_pack_conv_gemm_form(const float* w, float* wp, int Cout, int Cin, int form, int CoutP, hipStream_t s);
+// Input channels of the Winograd kernels.  A workgroup parks the GroupNorm (A, B) coefficients of the channels ITS chunks contract --
+// all of them without a K split, one part's with ConvArgs::ksplit -- in an LDS table of at most WINO_TABLE_CH entries per sample (two per
+// thread of the 512-thread kernels, one per thread of conv_wino.cpp's 1024), so
+//     Cin <= WINO_MAX_CIN   and   CinP / max(ksplit, 1) <= WINO_TABLE_CH:
+// layers of 1040 .. 2048 channels are served by the K-split ids only.
+constexpr int WINO_MAX_CIN = 2048;
+constexpr int WINO_TABLE_CH = 1024;
+inline int wino_part_channels(int CinP, int ksplit) { return CinP / (ksplit >= 2 ? ksplit : 1); }      // PC: the table's entries per sample
 // Winograd F(2x2,3x3) kernel (conv_wino.cpp): tile shape id 4 of the dispatcher
 bool conv_wino_supported(int ks, int H, int W);      // geometry only (decides whether transformed weights are packed at all)
 int conv_wino_cout_tile(int Cout);

@@ -2,6 +2,13 @@
 // what a launch tries after it.  The ids are public (the context options conv_shape / conv_shape1, the committed tuning tables under
 // profiles/, mcvd_last_conv_kernel / mcvd_model_op_kernel): a new variant gets a new number and one line here; numbers are never reused.
 // Plain C++17, no HIP: the static_asserts at the end check the table in every build.
+//
+// Input channels of the Winograd families (common.h: WINO_MAX_CIN = 2048, WINO_TABLE_CH = 1024): a workgroup's GroupNorm coefficient table covers
+// the channels of its own K part, so a launch needs  Cin <= WINO_MAX_CIN  and  CinP / max(kparts, 1) <= WINO_TABLE_CH.  The unsplit ids
+// (4, 10, 12, 24, 16) stop at 1024 channels; layers of 1040 .. 2048 are served by the K-split ids 8 / 11 / 18 / 19 / 13 / 26 / 25 / 27 where the
+// split's own conditions hold.  The persistent kernel (CF_WINO3P: 16 / 17 / 20) was NOT widened: it keeps one table of all Cin channels per run of
+// items, and a per-part table would have to be reloaded inside its item boundary; its fallback lists (17 -> 11, 20 -> 17 -> 16 -> 11) route round it.
+// The SPADE-fused loader of CF_WINO (ConvArgs::gb) stays at 1024 as well.
 #pragma once
 #include <initializer_list>
 

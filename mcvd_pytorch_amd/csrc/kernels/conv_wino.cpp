@@ -82,9 +82,15 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* sV = smem;                           // [2][VSZ]
     float* sP = smem + 2 * VSZ;                 // [2][PBUF]
-    float* sCo = sP + 2 * PBUF;                 // [Cin][2] prologue coefficients (A_c, B_c) of this sample (PRO only)
-    float* sC2 = sCo + (G8 ? 4 : 2) * a.Cin;    // PRO 3: [Cin][2] (s1, b2) of this sample (G8: + the second sample's)
-    float* sGB = sC2 + (G8 ? 4 : 2) * a.Cin;    // PRO 3: [2][MAXP][NT] gamma | beta of the patch elements of ONE chunk, element e = sl*NT + tid
+    // ---- chunk range of this workgroup (a.ksplit == 2: blockIdx.y picks one half of the input channels).  The coefficient tables cover the
+    // PC channels of this range only (PC <= WINO_TABLE_CH: one entry per thread and sample), indexed relative to 16 c_begin.
+    const int nch_all = a.CinP / CK;
+    const int ksp = a.ksplit == 2 ? 2 : 1, kh = ksp == 2 ? (int)blockIdx.y : 0;
+    const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
+    const int PC = (nch_all / ksp) * CK;
+    float* sCo = sP + 2 * PBUF;                 // [PC][2] prologue coefficients (A_c, B_c) of this sample's channels 16 c_begin .. (PRO only)
+    float* sC2 = sCo + (G8 ? 4 : 2) * PC;       // PRO 3: [PC][2] (s1, b2) of this sample (G8: + the second sample's)
+    float* sGB = sC2 + (G8 ? 4 : 2) * PC;       // PRO 3: [2][MAXP][NT] gamma | beta of the patch elements of ONE chunk, element e = sl*NT + tid
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
     const int H = a.H, W = a.W, HW = H * W, Cin = a.Cin;
@@ -205,7 +211,7 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(ConvArgs a) {
         f32x2 cfv[MAXP];                     /* all coefficient reads first: ONE LDS round trip, not MAXP */     \
         if (PRO >= 1) {                                                                                         \
             _Pragma("unroll") for (int sl = 0; sl < MAXP; ++sl) {                                               \
-                const int cch = min((ch) * CK + (p_ci[sl] & (CK - 1)), Cin - 1) + (G8 ? p_img[sl] * Cin : 0);   \
+                const int cch = min(((ch) - c_begin) * CK + (p_ci[sl] & (CK - 1)), PC - 1) + (G8 ? p_img[sl] * PC : 0);   \
                 cfv[sl] = *reinterpret_cast<const f32x2*>(sCo + cch * 2);                                       \
             }                                                                                                   \
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(cfv[0]), "+v"(cfv[1]), "+v"(cfv[MAXP > 2 ? 2 : 0]) :: "memory"); \
@@ -214,7 +220,7 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(ConvArgs a) {
         float gmv[MAXP], btv[MAXP];                                                                             \
         if (PRO == 3) {                                                                                         \
             _Pragma("unroll") for (int sl = 0; sl < MAXP; ++sl) {                                               \
-                const int cch = min((ch) * CK + (p_ci[sl] & (CK - 1)), Cin - 1) + (G8 ? p_img[sl] * Cin : 0);   \
+                const int cch = min(((ch) - c_begin) * CK + (p_ci[sl] & (CK - 1)), PC - 1) + (G8 ? p_img[sl] * PC : 0);   \
                 c2v[sl] = *reinterpret_cast<const f32x2*>(sC2 + cch * 2);                                       \
                 gmv[sl] = sGB[sl * NT + tid];                                                                   \
                 btv[sl] = sGB[(MAXP + sl) * NT + tid];                                                          \
@@ -270,11 +276,6 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(ConvArgs a) {
         tprev = now;                                                                                            \
     }
 
-    // ---- chunk range of this workgroup (a.ksplit == 2: blockIdx.y picks one half of the input channels)
-    const int nch_all = a.CinP / CK;
-    const int ksp = a.ksplit == 2 ? 2 : 1, kh = ksp == 2 ? (int)blockIdx.y : 0;
-    const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
-
     // ---- prologue: every global load of the first chunks + the coefficient table is issued before anything waits
     f32x4 A0[COT], A1[COT];                // A operands of the even / odd weight unit (first / second half of a chunk)
     float pd[MAXP];                        // raw patch registers, loaded one chunk ahead of their activation
@@ -287,22 +288,24 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(ConvArgs a) {
         WR_LOAD_P(c_begin + 1, q1)
         WR_LOAD_P(c_begin + 2, pd)
         WR_LOAD_GB(c_begin)
-        if (PRO && a.coef && tid < Cin) cfl = *reinterpret_cast<const f32x2*>(a.coef + ((long)b * Cin + tid) * 2);
-        if (PRO && tid < Cin) *reinterpret_cast<f32x2*>(sCo + tid * 2) = cfl;
-        if (PRO == 3 && tid < Cin) {           // (s1, b2): the temb pair, (1, 0) where the norm has none (final SPADE norm)
+        // table entry tid = channel 16 c_begin + tid; the clamp to Cin - 1 covers the padded last chunk of the last part (zeroed at the write)
+        const int csrc = min(CK * c_begin + tid, Cin - 1);
+        if (PRO && a.coef && tid < PC) cfl = *reinterpret_cast<const f32x2*>(a.coef + ((long)b * Cin + csrc) * 2);
+        if (PRO && tid < PC) *reinterpret_cast<f32x2*>(sCo + tid * 2) = cfl;
+        if (PRO == 3 && tid < PC) {            // (s1, b2): the temb pair, (1, 0) where the norm has none (final SPADE norm)
             f32x2 c2 = {1.0f, 0.0f};
-            if (a.coef2) c2 = *reinterpret_cast<const f32x2*>(a.coef2 + ((long)b * Cin + tid) * 2);
+            if (a.coef2) c2 = *reinterpret_cast<const f32x2*>(a.coef2 + ((long)b * Cin + csrc) * 2);
             *reinterpret_cast<f32x2*>(sC2 + tid * 2) = c2;
             if (G8) {
-                if (a.coef2 && b + 1 < a.B) c2 = *reinterpret_cast<const f32x2*>(a.coef2 + ((long)(b + 1) * Cin + tid) * 2);
-                *reinterpret_cast<f32x2*>(sC2 + (Cin + tid) * 2) = c2;
+                if (a.coef2 && b + 1 < a.B) c2 = *reinterpret_cast<const f32x2*>(a.coef2 + ((long)(b + 1) * Cin + csrc) * 2);
+                *reinterpret_cast<f32x2*>(sC2 + (PC + tid) * 2) = c2;
             }
         }
         if (G8) {                          // the halo of both patch buffers is zero padding for the whole kernel
             for (int i = tid; i < 2 * PBUF; i += NT) sP[i] = 0.0f;
-            if (PRO && a.coef && tid < Cin && b + 1 < a.B)     // second sample's coefficients: table rows Cin .. 2*Cin-1
-                cfl = *reinterpret_cast<const f32x2*>(a.coef + ((long)(b + 1) * Cin + tid) * 2);
-            if (PRO && tid < Cin) *reinterpret_cast<f32x2*>(sCo + (Cin + tid) * 2) = cfl;
+            if (PRO && a.coef && tid < PC && b + 1 < a.B)      // second sample's coefficients: table rows PC .. 2*PC-1
+                cfl = *reinterpret_cast<const f32x2*>(a.coef + ((long)(b + 1) * Cin + csrc) * 2);
+            if (PRO && tid < PC) *reinterpret_cast<f32x2*>(sCo + (PC + tid) * 2) = cfl;
         }
         if (rec) pt[0] = __builtin_amdgcn_s_memtime() - tk0;           // index setup + load issue
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // ONE memory latency for everything above (the asm loads are
@@ -607,9 +610,10 @@ __global__ __launch_bounds__(256) void wino_ksplit_reduce_stats_kernel(const flo
     }
 }
 
-static size_t wino_lds_bytes(int Cin, bool g8, bool spade = false) {
+// pc: the channels of one part (wino_part_channels): the coefficient tables' entries per sample
+static size_t wino_lds_bytes(int pc, bool g8, bool spade = false) {
     const int maxp = g8 ? 2 : 3;               // MAXP of the kernel
-    const size_t k = (size_t)(2 * WR_CK * 16 * WR_T + 2 * (WR_CK * 10 * WR_PP + 4) + (g8 ? 4 : 2) * Cin * (spade ? 2 : 1) +
+    const size_t k = (size_t)(2 * WR_CK * 16 * WR_T + 2 * (WR_CK * 10 * WR_PP + 4) + (g8 ? 4 : 2) * pc * (spade ? 2 : 1) +
                               (spade ? 2 * maxp * WR_NT : 0)) * sizeof(float);
     const size_t epi = (size_t)16 * 32 * WR_T * sizeof(float);        // sM of the epilogue
     return k > epi ? k : epi;
@@ -688,7 +692,7 @@ int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s) {
 template <int COT, int PRO, bool G8>
 static int wino_launch3(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
-    const size_t lds = wino_lds_bytes(a.Cin, G8, PRO == 3);
+    const size_t lds = wino_lds_bytes(wino_part_channels(a.CinP, a.ksplit == 2 ? 2 : 1), G8, PRO == 3);
     static PerDeviceOnce raised;
     if (raised.first_use()) {
         MCVD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_kernel<COT, PRO, G8>),
@@ -750,17 +754,20 @@ int conv_wino_cout_tile(int Cout) {
 
 // Shape ids 4 / 8 apply to this launch: geometry, channel layout, packed weights present (8: and an even chunk count).
 bool conv_wino_usable(const ConvArgs& a) {
-    return conv_wino_supported(a.ks, a.H, a.W) && a.wpw && a.Cin <= 1024 && a.CinP % WR_CK == 0 &&
+    const int pc = wino_part_channels(a.CinP, a.ksplit == 2 ? 2 : 1);        // (this kernel splits two ways only)
+    return conv_wino_supported(a.ks, a.H, a.W) && a.wpw && a.Cin <= WINO_MAX_CIN && pc <= WINO_TABLE_CH && a.CinP % WR_CK == 0 &&
+           (a.gb == nullptr || a.Cin <= WINO_TABLE_CH) &&                            // the SPADE-fused loader (PRO 3) stays where it was
+
            (a.C1 == 0 || a.C0 % WR_CK == 0) &&                                       // a chunk never straddles the concat seam
            (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) &&      // 32-bit byte offsets of the patch loads
-           wino_lds_bytes(a.Cin, a.H == 8 && a.W == 8, a.gb != nullptr) <= 160 * 1024 &&
+           wino_lds_bytes(pc, a.H == 8 && a.W == 8, a.gb != nullptr) <= 160 * 1024 &&
            (a.ksplit != 2 || ((a.CinP / WR_CK) % 2 == 0 && a.CinP / WR_CK >= 4 && conv_part_fits(a)));
 }
 
 // a.wpw must hold the operand-major layout (launch_pack_wino_weight) packed for conv_wino_cout_tile(Cout).
 int launch_conv_wino(const ConvArgs& a, hipStream_t s) {
-    MCVD_REQUIRE(conv_wino_usable(a), "winograd conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weights %s)", a.ks,
-                 a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpw ? "present" : "missing");
+    MCVD_REQUIRE(conv_wino_usable(a), "winograd conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weights %s; Cin <= %d, %d channels per K part)", a.ks,
+                 a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpw ? "present" : "missing", WINO_MAX_CIN, WINO_TABLE_CH);
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {

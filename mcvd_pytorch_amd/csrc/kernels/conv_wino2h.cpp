@@ -106,8 +106,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned* sV = reinterpret_cast<unsigned*>(smem);           // [2][VW]
     float* sP = smem + 2 * VW;                  // [2][PBUF]
-    float* sCo = sP + 2 * PBUF;                 // [Cin][2] prologue coefficients (A_c, B_c) of this sample (PRO only; G8: [2][Cin][2])
-    unsigned* sOff = reinterpret_cast<unsigned*>(sCo + (G8 ? 4 : 2) * a.Cin);      // [MAXP][NT] byte offsets of the patch-load slots (read by their owner only)
+    float* sCo = sP + 2 * PBUF;                 // [PC][2] prologue coefficients (A_c, B_c) of this sample's channels 16 c_begin .. (PRO only; G8: [2][PC][2])
 
     {   // the kernel descriptor must allocate all 256 registers: the asm statements below name v202-v255 in their text only
         float top;
@@ -118,6 +117,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
                  "s"(a.C1), "s"(a.CoutP), "s"(a.ksplit), "s"(a.dbg), "s"(a.wdma));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
     const int H = a.H, W = a.W, HW = H * W, Cin = a.Cin;
+    // ---- chunk range of this workgroup (a.ksplit == 2 / 4: blockIdx.y picks one part of the input channels).  The coefficient table
+    // covers the PC channels of this range only (PC <= WINO_TABLE_CH: two entries per thread and sample), indexed relative to 16 c_begin.
+    const int nch_all = a.CinP / CK;
+    const int ksp = a.ksplit >= 2 ? a.ksplit : 1, kh = ksp >= 2 ? (int)blockIdx.y : 0;          // 2 or 4 parts of the input channels
+    const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
+    const int PC = (nch_all / ksp) * CK;
+    unsigned* sOff = reinterpret_cast<unsigned*>(sCo + (G8 ? 4 : 2) * PC);      // [MAXP][NT] byte offsets of the patch-load slots (read by their owner only)
     const int rx_n = G8 ? 1 : W >> 4, ry_n = G8 ? 1 : H >> 3;
     const int nreg = G8 ? (a.B + 1) >> 1 : a.B * rx_n * ry_n;
     // block id -> (region, cout tile): the cout tiles of one region run at the same time on the same XCD (conv_wino.cpp)
@@ -132,20 +138,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
     const int co0 = cotile * BCO;
     const int rg = __builtin_amdgcn_readfirstlane(wave >> 2);   // rows 2rg, 2rg+1 of B^T d; phase order of the wave
 
-    // prologue coefficients of this sample: (A_c, B_c) of channel tid + k * 512 (Cin <= 1024: at most two table entries per thread and
-    // sample).  Regions of a plane: asm loads into v202-v205 (the registers of the third patch) IN FRONT of the first patches, parked in
+    // prologue coefficients of this sample: (A_c, B_c) of channel 16 c_begin + tid + k * 512 (PC <= 1024: at most two table entries per thread and
+    // sample; the clamp to Cin - 1 covers the padded last chunk of the last part).  Regions of a plane: asm loads into v202-v205 (the registers of the third patch) IN FRONT of the first patches, parked in
     // the LDS table once they have landed (conv_wino3.cpp).  G8 (two samples, eight values: more than the six patch registers): ordinary
     // loads, waited for before the first patch request.
     f32x2 cpre[2] = {{1.0f, 0.0f}, {1.0f, 0.0f}};
     f32x2 cpre2[2] = {{1.0f, 0.0f}, {1.0f, 0.0f}};              // G8: the region's second sample (clamped to the last one)
     const float* co_src[2];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) co_src[k] = a.coef + ((long)b * Cin + min(tid + k * NT, Cin - 1)) * 2;
+    for (int k = 0; k < 2; ++k) co_src[k] = a.coef + ((long)b * Cin + min(CK * c_begin + tid + k * NT, Cin - 1)) * 2;
     if (PRO && G8) {                                            // unconditional (clamped) loads: the wait belongs at the use
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             cpre[k] = *reinterpret_cast<const f32x2*>(co_src[k]);
-            cpre2[k] = *reinterpret_cast<const f32x2*>(a.coef + ((long)min(b + 1, a.B - 1) * Cin + min(tid + k * NT, Cin - 1)) * 2);
+            cpre2[k] = *reinterpret_cast<const f32x2*>(a.coef + ((long)min(b + 1, a.B - 1) * Cin + min(CK * c_begin + tid + k * NT, Cin - 1)) * 2);
         }
     }
 
@@ -250,7 +256,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         _Pragma("unroll") for (int sl = 0; sl < MAXP; ++sl) {                                                   \
             cfv[sl] = f32x2{1.0f, 0.0f};                                                                        \
             if (PRO >= 1) {                                                                                     \
-                const int cch = min((ch) * CK + (int)((p_pk[sl] >> 12) & (CK - 1)), Cin - 1) + (G8 ? (int)((p_pk[sl] >> 20) & 1u) * Cin : 0); \
+                /* relative to the part's first channel; the clamp keeps the look-ahead past c_end (a patch nobody reads) in the table */ \
+                const int cch = min(((ch) - c_begin) * CK + (int)((p_pk[sl] >> 12) & (CK - 1)), PC - 1) + (G8 ? (int)((p_pk[sl] >> 20) & 1u) * PC : 0); \
                 cfv[sl] = *reinterpret_cast<const f32x2*>(sCo + cch * 2);                                       \
             }                                                                                                   \
         }                                                                                                       \
@@ -379,11 +386,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         tprev = now;                                                                                            \
     }
 
-    // ---- chunk range of this workgroup (a.ksplit == 2 / 4: blockIdx.y picks one part of the input channels)
-    const int nch_all = a.CinP / CK;
-    const int ksp = a.ksplit >= 2 ? a.ksplit : 1, kh = ksp >= 2 ? (int)blockIdx.y : 0;          // 2 or 4 parts of the input channels
-    const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
-
     // ---- prologue.  Issue order = need order: the coefficients of the sample (into the registers of the third patch), the raw patches of
     // the first two chunks (into the registers of weight quads 0-2, which are not needed before the first MFMA phase), then the weight
     // quads 3.. of the first chunk.  Coefficients and patches are consumed as soon as THEY have landed (the weights, 3/4 of the bytes, are
@@ -395,9 +397,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         if (PRO && G8) {                   // (the compiler waits for the coefficient loads here: nothing else is in flight yet)
 #pragma unroll
             for (int k = 0; k < 2; ++k)
-                if (tid + k * NT < Cin) {
+                if (tid + k * NT < PC) {
                     *reinterpret_cast<f32x2*>(sCo + (tid + k * NT) * 2) = cpre[k];
-                    *reinterpret_cast<f32x2*>(sCo + (Cin + tid + k * NT) * 2) = cpre2[k];
+                    *reinterpret_cast<f32x2*>(sCo + (PC + tid + k * NT) * 2) = cpre2[k];
                 }
         }
         if (G8)                            // the halo of both patch buffers is zero padding for the whole kernel
@@ -418,7 +420,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
                          : "=v"(cpre[0].x), "=v"(cpre[0].y), "=v"(cpre[1].x), "=v"(cpre[1].y) : "s"(vtok));
 #pragma unroll
             for (int k = 0; k < 2; ++k)
-                if (tid + k * NT < Cin) *reinterpret_cast<f32x2*>(sCo + (tid + k * NT) * 2) = cpre[k];
+                if (tid + k * NT < PC) *reinterpret_cast<f32x2*>(sCo + (tid + k * NT) * 2) = cpre[k];
             cdep[0] = cdep[1] = cpre[0].x + cpre[0].y;
             cdep[2] = cdep[3] = cpre[1].x + cpre[1].y;
         }
@@ -636,8 +638,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
 #undef H2_VALU_PHASE
 }
 
-static size_t wino2h_lds_bytes(int Cin, bool g8) {
-    return (size_t)(2 * H2_VW + 2 * (H2_CK * 10 * H2_PP + 4) + (g8 ? 4 : 2) * Cin + 6 * H2_NT) * sizeof(float);
+// pc: the channels of one part (wino_part_channels): the coefficient table's entries per sample
+static size_t wino2h_lds_bytes(int pc, bool g8) {
+    return (size_t)(2 * H2_VW + 2 * (H2_CK * 10 * H2_PP + 4) + (g8 ? 4 : 2) * pc + 6 * H2_NT) * sizeof(float);
 }
 
 // the K-split second pass lives in conv_wino.cpp
@@ -658,7 +661,7 @@ static int wino2h_launch_k(const ConvArgs& k, dim3 grid, size_t lds, hipStream_t
 template <int COT, int PRO, bool G8>
 static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
-    const size_t lds = wino2h_lds_bytes(a.Cin, G8);
+    const size_t lds = wino2h_lds_bytes(wino_part_channels(a.CinP, a.ksplit), G8);
     const int nreg = G8 ? (a.B + 1) / 2 : a.B * (a.H / 8) * (a.W / 16);
     const int ksp = a.ksplit >= 2 ? a.ksplit : 1;
     dim3 grid(((nreg + 7) / 8) * 8 * (a.CoutP / BCO), ksp);
@@ -716,17 +719,17 @@ static int wino2h_launch(const ConvArgs& a, hipStream_t s) {
 bool conv_wino2h_usable(const ConvArgs& a) {
     const bool g8 = a.H == 8 && a.W == 8;
     const int nch = a.CinP / H2_CK;
-    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= 1024 &&
+    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= WINO_MAX_CIN && wino_part_channels(a.CinP, a.ksplit) <= WINO_TABLE_CH &&
            a.CinP % H2_CK == 0 && (a.C1 == 0 || a.C0 % H2_CK == 0) && a.H * a.W <= 16384 &&
-           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino2h_lds_bytes(a.Cin, g8) <= 160 * 1024 &&
+           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino2h_lds_bytes(wino_part_channels(a.CinP, a.ksplit), g8) <= 160 * 1024 &&
            (a.ksplit < 2 || ((a.ksplit == 2 || (a.ksplit == 4 && nch / 4 >= H2_MINCH_K4)) && nch % a.ksplit == 0 && nch >= 2 * a.ksplit &&
                              conv_part_fits(a)));
 }
 
 // a.wph: the layout of launch_pack_wino2h_weight, packed for conv_wino_cout_tile(Cout).
 int launch_conv_wino2h(const ConvArgs& a, hipStream_t s) {
-    MCVD_REQUIRE(conv_wino2h_usable(a), "winograd f16x2 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s)",
-                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wph ? "present" : "missing");
+    MCVD_REQUIRE(conv_wino2h_usable(a), "winograd f16x2 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d, %d channels per K part)",
+                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wph ? "present" : "missing", WINO_MAX_CIN, WINO_TABLE_CH);
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd f16x2 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {

@@ -112,8 +112,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned* sV = reinterpret_cast<unsigned*>(smem);           // [2][VW]
     float* sP = smem + 2 * VW;                  // [2][PBUF]
-    float* sCo = sP + 2 * PBUF;                 // [Cin][2] prologue coefficients (A_c, B_c) of this sample (PRO only; G8: [2][Cin][2])
-    unsigned* sOff = reinterpret_cast<unsigned*>(sCo + (G8 ? 4 : 2) * a.Cin);      // [NPL][NT] byte offsets of the patch-load slots (read by their owner only)
+    float* sCo = sP + 2 * PBUF;                 // [PC][2] prologue coefficients (A_c, B_c) of this sample's channels 16 c_begin .. (PRO only; G8: [2][PC][2])
 
     {   // the kernel descriptor must allocate all 256 registers: the asm statements below name v172-v255 in their text only
         float top;
@@ -126,6 +125,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     const unsigned long long t_start = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;     // diagnostics: the phase clock starts here
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
     const int H = a.H, W = a.W, HW = H * W, Cin = a.Cin;
+    // ---- chunk range of this workgroup (a.ksplit == 2 / 4 / 8: blockIdx.y picks one part of the input channels).  The coefficient table
+    // covers the PC channels of this range only (PC <= WINO_TABLE_CH: two entries per thread and sample), indexed relative to 16 c_begin.
+    const int nch_all = a.CinP / CK;
+    const int ksp = a.ksplit >= 2 ? a.ksplit : 1, kh = ksp >= 2 ? (int)blockIdx.y : 0;          // 2, 4 or 8 parts of the input channels
+    const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
+    const int PC = (nch_all / ksp) * CK;
+    unsigned* sOff = reinterpret_cast<unsigned*>(sCo + (G8 ? 4 : 2) * PC);      // [NPL][NT] byte offsets of the patch-load slots (read by their owner only)
     const int rx_n = G8 ? 1 : W >> 4, ry_n = G8 ? 1 : H >> 3;
     const int nreg = G8 ? (a.B + 1) >> 1 : a.B * rx_n * ry_n;
     // block id -> (region, cout tile): the cout tiles of one region run at the same time on the same XCD (conv_wino.cpp)
@@ -140,14 +146,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     const int co0 = cotile * BCO;
     const int rg = __builtin_amdgcn_readfirstlane(wave >> 2);   // rows 2rg, 2rg+1 of B^T d; phase order of the wave
 
-    // prologue coefficients of this sample: (A_c, B_c) of channel tid + k * 512 (Cin <= 1024: at most two table entries per thread and
-    // sample; G8: also the region's second sample, clamped to the last one), fetched by asm loads into v172-v179 IN FRONT of the first
+    // prologue coefficients of this sample: (A_c, B_c) of channel 16 c_begin + tid + k * 512 (PC <= 1024: at most two table entries per thread and
+    // sample; the clamp to Cin - 1 covers the padded last chunk of the last part; G8: also the region's second sample, clamped to the last one), fetched by asm loads into v172-v179 IN FRONT of the first
     // patches (see the prologue below) and parked in the LDS table once they have landed
     const float* co_src[G8 ? 4 : 2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-        co_src[k] = a.coef + ((long)b * Cin + min(tid + k * NT, Cin - 1)) * 2;
-        if (G8) co_src[2 + k] = a.coef + ((long)min(b + 1, a.B - 1) * Cin + min(tid + k * NT, Cin - 1)) * 2;
+        co_src[k] = a.coef + ((long)b * Cin + min(CK * c_begin + tid + k * NT, Cin - 1)) * 2;
+        if (G8) co_src[2 + k] = a.coef + ((long)min(b + 1, a.B - 1) * Cin + min(CK * c_begin + tid + k * NT, Cin - 1)) * 2;
     }
     if (PRO) {                             // unconditional (clamped) loads into the registers of the third patch (requested later); the
                                            // oldest VMEM operations of the wave: their latency passes under the index arithmetic below
@@ -268,7 +274,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
         _Pragma("unroll") for (int sl = 0; sl < NPL; ++sl) {                                                    \
             cfv[sl] = f32x2{1.0f, 0.0f};                                                                        \
             if (PRO >= 1) {                                                                                     \
-                const int cch = min((ch) * CK + (int)((p_pk[sl] >> 12) & (CK - 1)), Cin - 1) + (G8 ? (int)((p_pk[sl] >> 20) & 1u) * Cin : 0); \
+                /* relative to the part's first channel; the clamp keeps the look-ahead past c_end (a patch nobody reads) in the table */ \
+                const int cch = min(((ch) - c_begin) * CK + (int)((p_pk[sl] >> 12) & (CK - 1)), PC - 1) + (G8 ? (int)((p_pk[sl] >> 20) & 1u) * PC : 0); \
                 cfv[sl] = *reinterpret_cast<const f32x2*>(sCo + cch * 2);                                       \
             }                                                                                                   \
         }                                                                                                       \
@@ -439,11 +446,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
 #define W3_TS(i)
 #endif
 
-    // ---- chunk range of this workgroup (a.ksplit == 2: blockIdx.y picks one half of the input channels)
-    const int nch_all = a.CinP / CK;
-    const int ksp = a.ksplit >= 2 ? a.ksplit : 1, kh = ksp >= 2 ? (int)blockIdx.y : 0;          // 2, 4 or 8 parts of the input channels
-    const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
-
     // ---- prologue.  Issue order = need order: the coefficients of the sample (into the registers of the third patch), the raw patches of
     // the first two chunks (into the registers of weight quads 0 .. PQ-1, which are not needed before the first MFMA phase), then the
     // weight quads PQ.. of the first chunk.  Coefficients and patches are consumed as soon as THEY have landed (the weights, most of the
@@ -474,9 +476,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
                              : "=v"(cpre[2].x), "=v"(cpre[2].y), "=v"(cpre[3].x), "=v"(cpre[3].y) : "s"(vtok));
 #pragma unroll
             for (int k = 0; k < 2; ++k)
-                if (tid + k * NT < Cin) {
+                if (tid + k * NT < PC) {
                     *reinterpret_cast<f32x2*>(sCo + (tid + k * NT) * 2) = cpre[k];
-                    if constexpr (G8) *reinterpret_cast<f32x2*>(sCo + (Cin + tid + k * NT) * 2) = cpre[2 + k];
+                    if constexpr (G8) *reinterpret_cast<f32x2*>(sCo + (PC + tid + k * NT) * 2) = cpre[2 + k];
                 }
             cdep = cpre[0].x + cpre[1].x + (G8 ? cpre[2].x + cpre[3].x : 0.0f);
         }
@@ -700,8 +702,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
 #undef W3_VALU_PHASE
 }
 
-static size_t wino3_lds_bytes(int Cin, bool g8) {
-    return (size_t)(2 * W3_VW + 2 * (W3_CK * 10 * W3_PP + 8) + (g8 ? 4 : 2) * Cin + (g8 ? 1 : 3) * W3_NT) * sizeof(float);
+// pc: the channels of one part (wino_part_channels): the coefficient table's entries per sample
+static size_t wino3_lds_bytes(int pc, bool g8) {
+    return (size_t)(2 * W3_VW + 2 * (W3_CK * 10 * W3_PP + 8) + (g8 ? 4 : 2) * pc + (g8 ? 1 : 3) * W3_NT) * sizeof(float);
 }
 
 // the K-split second pass lives in conv_wino.cpp
@@ -722,7 +725,7 @@ static int wino3_launch_k(const ConvArgs& k, dim3 grid, size_t lds, hipStream_t 
 template <int COT, int PRO, bool G8>
 static int wino3_launch2(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
-    const size_t lds = wino3_lds_bytes(a.Cin, G8);
+    const size_t lds = wino3_lds_bytes(wino_part_channels(a.CinP, a.ksplit), G8);
     const int nreg = G8 ? (a.B + 1) / 2 : a.B * (a.H / 8) * (a.W / 16);
     const int ksp = a.ksplit >= 2 ? a.ksplit : 1;
     dim3 grid(((nreg + 7) / 8) * 8 * (a.CoutP / BCO), ksp);
@@ -778,17 +781,17 @@ static int wino3_launch(const ConvArgs& a, hipStream_t s) {
 // pre-split packed weights present (11: and an even chunk count).
 bool conv_wino3_usable(const ConvArgs& a) {
     const bool g8 = a.H == 8 && a.W == 8;
-    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wpb && !a.gb && a.Cin <= 1024 &&
+    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wpb && !a.gb && a.Cin <= WINO_MAX_CIN && wino_part_channels(a.CinP, a.ksplit) <= WINO_TABLE_CH &&
            a.CinP % W3_CK == 0 && (a.C1 == 0 || a.C0 % W3_CK == 0) && a.H * a.W <= 16384 &&
-           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino3_lds_bytes(a.Cin, g8) <= 160 * 1024 &&
+           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino3_lds_bytes(wino_part_channels(a.CinP, a.ksplit), g8) <= 160 * 1024 &&
            (a.ksplit < 2 || ((a.ksplit == 2 || a.ksplit == 4 || a.ksplit == 8) && (a.CinP / W3_CK) % a.ksplit == 0 &&
                              a.CinP / W3_CK >= 2 * a.ksplit && conv_part_fits(a)));        // every part at least two chunks
 }
 
 // a.wpb: the layout of launch_pack_wino3_weight, packed for conv_wino_cout_tile(Cout).
 int launch_conv_wino3(const ConvArgs& a, hipStream_t s) {
-    MCVD_REQUIRE(conv_wino3_usable(a), "winograd bf16x3 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s)",
-                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpb ? "present" : "missing");
+    MCVD_REQUIRE(conv_wino3_usable(a), "winograd bf16x3 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d, %d channels per K part)",
+                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpb ? "present" : "missing", WINO_MAX_CIN, WINO_TABLE_CH);
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd bf16x3 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {

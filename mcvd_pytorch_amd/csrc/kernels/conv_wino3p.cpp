@@ -664,9 +664,11 @@ static int wino3p_launch1(const ConvArgs& a, hipStream_t s) {
 
 // Shape ids 16 / 17 apply to this launch: regions of 8 x 16 output pixels (not the 8x8 images), no SPADE prologue, no consumer-side
 // GroupNorm reduction, pre-split packed weights present, at least WP_MINCH chunks per item (17: per K half, and an even chunk count).
+// Cin <= WINO_TABLE_CH with or without a K split: a persistent workgroup keeps ONE table of all Cin channels per run of items of a sample
+// (an item of another part would need its table reloaded inside the item boundary); wider layers take the one-shot kernel (ids 11 / 18 / 19).
 bool conv_wino3p_usable(const ConvArgs& a) {
     const int nchunks = a.CinP / WP_CK;
-    return a.ks == 3 && a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16 && a.wpb && !a.gb && a.Cin <= 1024 &&
+    return a.ks == 3 && a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16 && a.wpb && !a.gb && a.Cin <= WINO_TABLE_CH &&
            a.CinP % WP_CK == 0 && (a.C1 == 0 || a.C0 % WP_CK == 0) && a.H * a.W <= 16384 &&
            (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino3p_lds_bytes(a.Cin) <= 160 * 1024 &&
            (long)a.B * (a.H / 8) * (a.W / 16) * (a.CoutP / 32) * 8 < (1L << 31) &&
@@ -676,8 +678,8 @@ bool conv_wino3p_usable(const ConvArgs& a) {
 }
 
 int launch_conv_wino3p(const ConvArgs& a, hipStream_t s) {
-    MCVD_REQUIRE(conv_wino3p_usable(a), "persistent winograd bf16x3 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s)",
-                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpb ? "present" : "missing");
+    MCVD_REQUIRE(conv_wino3p_usable(a), "persistent winograd bf16x3 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d)",
+                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpb ? "present" : "missing", WINO_TABLE_CH);
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "persistent winograd bf16x3 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {
