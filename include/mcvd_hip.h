@@ -73,7 +73,7 @@ typedef struct mcvd_unet_desc {
     int32_t channels;          /* data.channels */
     int32_t num_frames;        /* data.num_frames (frames predicted per block) */
     int32_t num_frames_cond;   /* data.num_frames_cond + data.num_frames_future (ncsnpp_more.py:47) */
-    int32_t ngf;               /* model.ngf */
+    int32_t ngf;               /* model.ngf: 8 .. 288, a multiple of 4 (288: the ngf-288 UCF-101 models; T = 4 ngf, + ngf / 2 with cond_emb, <= 1296) */
     int32_t n_levels;          /* len(model.ch_mult) */
     int32_t ch_mult[MCVD_MAX_LEVELS];
     int32_t num_res_blocks;    /* model.num_res_blocks */

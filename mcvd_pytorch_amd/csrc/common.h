@@ -152,9 +152,12 @@ int launch_pack_conv_gemm_form(const float* w, float* wp, int Cout, int Cin, int
 // Input channels of the Winograd kernels.  A workgroup parks the GroupNorm (A, B) coefficients of the channels ITS chunks contract --
 // all of them without a K split, one part's with ConvArgs::ksplit -- in an LDS table of at most WINO_TABLE_CH entries per sample (two per
 // thread of the 512-thread kernels, one per thread of conv_wino.cpp's 1024), so
-//     Cin <= WINO_MAX_CIN   and   CinP / max(ksplit, 1) <= WINO_TABLE_CH:
-// layers of 1040 .. 2048 channels are served by the K-split ids only.
+//     Cin <= WINO_MAX_CIN (ksplit >= 4: WINO_MAX_CIN_K4)   and   CinP / max(ksplit, 1) <= WINO_TABLE_CH:
+// layers of 1040 .. 2048 channels are served by the K-split ids only.  A split of four or more parts takes WINO_MAX_CIN_K4 channels
+// (144 chunks: 576 per part at 4 parts, 288 at 8); the 2-way and unsplit launches stop at WINO_MAX_CIN by the table rule alone.
 constexpr int WINO_MAX_CIN = 2048;
+constexpr int WINO_MAX_CIN_K4 = 2304;          // a split of four or more parts takes this many
+inline int wino_max_cin(int ksplit) { return ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN; }
 constexpr int WINO_TABLE_CH = 1024;
 inline int wino_part_channels(int CinP, int ksplit) { return CinP / (ksplit >= 2 ? ksplit : 1); }      // PC: the table's entries per sample
 // Winograd F(2x2,3x3) kernel (conv_wino.cpp): tile shape id 4 of the dispatcher

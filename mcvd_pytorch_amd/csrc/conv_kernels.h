@@ -9,6 +9,9 @@
 // split's own conditions hold.  The persistent kernel (CF_WINO3P: 16 / 17 / 20) was NOT widened: it keeps one table of all Cin channels per run of
 // items, and a per-part table would have to be reloaded inside its item boundary; its fallback lists (17 -> 11, 20 -> 17 -> 16 -> 11) route round it.
 // The SPADE-fused loader of CF_WINO (ConvArgs::gb) stays at 1024 as well.
+// A split of four or more parts takes WINO_MAX_CIN_K4 = 2304 channels: layers of 2049 .. 2304 (the 2304-channel concats of the ngf-288 UCF-101 nets)
+// are served by ids 18 / 19 (bf16x3), 26 (f16x2) and 27 (f16x1) only.  The 2-way ids 8 / 11 / 13 / 25 refuse them by the table rule (1152 channels per
+// part), and CF_WINO has no 4-way split: with bf16x3 off such a layer runs the direct tile kernel.
 #pragma once
 #include <initializer_list>
 

@@ -70,9 +70,21 @@ __global__ __launch_bounds__(256, 2) void conv1x1_h2_kernel(ConvArgs a, int ptil
     float* sC = sX + (IM ? 0 : NB * XSZ);     // [nimg][Cin][2] prologue coefficients of the images this pixel tile spans (PRO only)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
-    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-    const int ptile = (slot / nct) * 8 + xcd, ctile = slot - (slot / nct) * nct;
-    if (ptile >= ptiles) return;
+    // block id -> (pixel tile, cout tile).  Eight pixel tiles or more: the cout tiles of one pixel tile run on the same XCD (block ids go round
+    // the eight XCDs) and share its L2 copy of the pixels.  FEWER than eight (an 8 x 8 level at B < 16): that map leaves 8 - ptiles XCDs idle --
+    // at ptiles = 1 every working workgroup of a launch sat on the 32 CUs of XCD 0, and the q|k|v projection 1152 -> 3456 at B = 2 (54 workgroups at
+    // cout tile 64) lost to the direct tile kernel, which spreads (62 against 46 us) -- so consecutive block ids take consecutive pixel tiles of
+    // the same cout tile and the launch covers all XCDs; the pixels of so few tiles (<= 7 x 128 x Cin floats) fit every L2.  Same arithmetic.
+    int ptile, ctile;
+    if (ptiles < 8) {
+        ptile = blockIdx.x % ptiles;
+        ctile = blockIdx.x / ptiles;
+    } else {
+        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+        ptile = (slot / nct) * 8 + xcd;
+        ctile = slot - (slot / nct) * nct;
+    }
+    if (ptile >= ptiles || ctile >= nct) return;
     const int co0 = ctile * BCO;
     const int HW = a.H * a.W, Cin = a.Cin;
     const long NPX = (long)a.B * HW;
@@ -487,9 +499,12 @@ __global__ __launch_bounds__(256, 2) void conv1x1_h2_kernel(ConvArgs a, int ptil
 }
 
 // im_cc > 0: the im2col form (ConvArgs::im2col) -- no pixel ring; the raw patch [im_cc + 1][PT / W + 2][W + 8] and the offset table [Cin] instead
-static size_t q1_lds_bytes(int np, int cot, int Cin, int HW, int im_cc = 0, int W = 0) {
+// table: the launch has a prologue (ConvArgs::coef, PRO != 0) and parks [nimg][Cin][2] coefficients behind the pixel ring.  A raw-input launch
+// (PRO 0: the shortcuts Conv_2, NIN_3) neither writes nor reads that table and does not pay for it: at 2304 channels and 8 x 8 planes (two
+// images per pixel tile) it is 36 KB, and counting it left such a shortcut with cout tile 1 only.
+static size_t q1_lds_bytes(int np, int cot, int Cin, int HW, bool table, int im_cc = 0, int W = 0) {
     const int nimg = HW >= Q1_PT ? 1 : Q1_PT / HW;
-    const size_t pix = im_cc > 0 ? (size_t)((im_cc + 1) * (Q1_PT / W + 2) * (W + 8) + Cin) : (size_t)Q1_NB * Q1_CK * Q1_PT + (size_t)nimg * Cin * 2;
+    const size_t pix = im_cc > 0 ? (size_t)((im_cc + 1) * (Q1_PT / W + 2) * (W + 8) + Cin) : (size_t)Q1_NB * Q1_CK * Q1_PT + (table ? (size_t)nimg * Cin * 2 : 0);
     const size_t loop = ((size_t)Q1_NB * (cot * np * 256) + pix) * sizeof(float);
     const size_t epi = (size_t)(32 * cot) * (Q1_PT + 4) * sizeof(float);      // the transposed output tile (row pitch PT + 4) overlays the chunk buffers
     return loop > epi ? loop : epi;
@@ -503,14 +518,14 @@ bool conv1x1_h2_supported(const ConvArgs& a, int cot, int np) {
     if (a.im2col) {          // the stem as a GEMM over an im2col the kernel stages itself: whole image rows per pixel tile, raw input, three pieces
         return np == 3 && !a.coef && !a.act && !a.kv_img && a.W >= 8 && a.W <= Q1_PT && (a.W & (a.W - 1)) == 0 && HW % Q1_PT == 0 && a.Cin % Q1_CK == 0 &&
                a.Cin == a.CinP && a.Cin >= 9 * (a.C0 + a.C1) && (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * HW < (1L << 31) &&
-               q1_lds_bytes(np, cot, a.Cin, HW, a.C0 + a.C1, a.W) <= 80 * 1024;
+               q1_lds_bytes(np, cot, a.Cin, HW, false, a.C0 + a.C1, a.W) <= 80 * 1024;
     }
     if (!(HW % Q1_PT == 0 || (HW < Q1_PT && Q1_PT % HW == 0 && Q1_PT / HW <= Q1_MAXIMG))) return false;
     if (a.Cin % Q1_CK != 0 || a.CinP % Q1_CK != 0) return false;            // no partial chunk: every staged row is real data
     if (a.C1 > 0 && a.C0 % Q1_CK != 0) return false;                        // a chunk never straddles the concat seam
     if ((long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * HW >= (1L << 31)) return false;   // 32-bit lane offsets
     if (a.act && !a.coef) return false;
-    return q1_lds_bytes(np, cot, a.Cin, HW) <= 80 * 1024;                   // two workgroups per CU
+    return q1_lds_bytes(np, cot, a.Cin, HW, a.coef != nullptr) <= 80 * 1024;                   // two workgroups per CU
 }
 
 template <int NP, int COT>
@@ -519,8 +534,8 @@ static int q1_launch(const ConvArgs& a, hipStream_t s) {
     const long NPX = (long)a.B * HW;
     const int ptiles = (int)((NPX + Q1_PT - 1) / Q1_PT);
     const int nct = a.CoutP / (32 * COT);
-    const size_t lds = q1_lds_bytes(NP, COT, a.Cin, HW, a.im2col ? a.C0 + a.C1 : 0, a.W);
-    const dim3 grid(((ptiles + 7) / 8) * 8 * nct);
+    const size_t lds = q1_lds_bytes(NP, COT, a.Cin, HW, a.coef != nullptr, a.im2col ? a.C0 + a.C1 : 0, a.W);
+    const dim3 grid(ptiles < 8 ? ptiles * nct : ((ptiles + 7) / 8) * 8 * nct);          // (the kernel's two block maps)
     if constexpr (NP == 3) {
         if (a.im2col) {
             static PerDeviceOnce raised_im;

@@ -754,7 +754,9 @@ int conv_wino_cout_tile(int Cout) {
 
 // Shape ids 4 / 8 apply to this launch: geometry, channel layout, packed weights present (8: and an even chunk count).
 bool conv_wino_usable(const ConvArgs& a) {
-    const int pc = wino_part_channels(a.CinP, a.ksplit == 2 ? 2 : 1);        // (this kernel splits two ways only)
+    // (this kernel splits two ways only: WINO_MAX_CIN_K4, the bound of the splits of four or more parts, never applies to it)
+    const int pc = wino_part_channels(a.CinP, a.ksplit == 2 ? 2 : 1);
+    static_assert(WINO_MAX_CIN_K4 > 2 * WINO_TABLE_CH && WINO_MAX_CIN <= 2 * WINO_TABLE_CH, "above WINO_MAX_CIN a 2-way part overflows the table");
     return conv_wino_supported(a.ks, a.H, a.W) && a.wpw && a.Cin <= WINO_MAX_CIN && pc <= WINO_TABLE_CH && a.CinP % WR_CK == 0 &&
            (a.gb == nullptr || a.Cin <= WINO_TABLE_CH) &&                            // the SPADE-fused loader (PRO 3) stays where it was
 

@@ -719,7 +719,7 @@ static int wino2h_launch(const ConvArgs& a, hipStream_t s) {
 bool conv_wino2h_usable(const ConvArgs& a) {
     const bool g8 = a.H == 8 && a.W == 8;
     const int nch = a.CinP / H2_CK;
-    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= WINO_MAX_CIN && wino_part_channels(a.CinP, a.ksplit) <= WINO_TABLE_CH &&
+    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) && wino_part_channels(a.CinP, a.ksplit) <= WINO_TABLE_CH &&
            a.CinP % H2_CK == 0 && (a.C1 == 0 || a.C0 % H2_CK == 0) && a.H * a.W <= 16384 &&
            (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino2h_lds_bytes(wino_part_channels(a.CinP, a.ksplit), g8) <= 160 * 1024 &&
            (a.ksplit < 2 || ((a.ksplit == 2 || (a.ksplit == 4 && nch / 4 >= H2_MINCH_K4)) && nch % a.ksplit == 0 && nch >= 2 * a.ksplit &&
@@ -729,7 +729,7 @@ bool conv_wino2h_usable(const ConvArgs& a) {
 // a.wph: the layout of launch_pack_wino2h_weight, packed for conv_wino_cout_tile(Cout).
 int launch_conv_wino2h(const ConvArgs& a, hipStream_t s) {
     MCVD_REQUIRE(conv_wino2h_usable(a), "winograd f16x2 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d, %d channels per K part)",
-                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wph ? "present" : "missing", WINO_MAX_CIN, WINO_TABLE_CH);
+                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wph ? "present" : "missing", wino_max_cin(a.ksplit), WINO_TABLE_CH);
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd f16x2 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {

@@ -18,7 +18,7 @@ constexpr int TEMB_NW = 8;       // waves per workgroup (256 registers per lane:
 // ds_bpermute per output); the rest is 12 passes of one L2 round trip each, the large-argument sinf / cosf and the cold first touch.
 // The sum of one output is formed in the same order whatever the number of rows.
 //
-// out[o] = silu( sum_k in[k] * w[o * K + k] + bias[o] ), o < N; `in` in LDS (16-byte aligned), K <= 1152
+// out[o] = silu( sum_k in[k] * w[o * K + k] + bias[o] ), o < N; `in` in LDS (16-byte aligned), K <= 1152 (= 4 * 288, the widest ngf)
 __device__ __forceinline__ void temb_linear(const float* in, const float* w, const float* bias, float* out, float* red, int K, int N, int wave, int lane) {
     typedef float f32x4 __attribute__((ext_vector_type(4)));
     constexpr int NO = 8;
@@ -89,8 +89,8 @@ __global__ __launch_bounds__(64 * TEMB_NW) void temb_mlp_kernel(const void* labe
                                                          const float* b0, const float* w1, const float* b1,
                                                          float* silu_temb, int nf, int out_stride, const float* emb_table,
                                                          const int32_t* mask) {
-    __shared__ __attribute__((aligned(16))) float emb[256];
-    __shared__ __attribute__((aligned(16))) float hid[1024];
+    __shared__ __attribute__((aligned(16))) float emb[288];            // nf <= 288
+    __shared__ __attribute__((aligned(16))) float hid[1152];           // 4 nf
     __shared__ __attribute__((aligned(16))) float red[TEMB_NW * 512];      // [wave][8 outputs][64 lanes]
     const int b = blockIdx.x;
     const int T = 4 * nf;
@@ -132,7 +132,7 @@ __global__ __launch_bounds__(64 * TEMB_NW) void temb_mlp_kernel(const void* labe
 int launch_temb_mlp(const void* labels, int labels_f32, const float* freqs, const float* w0, const float* b0, const float* w1,
                     const float* b1, float* silu_temb, int B, int nf, int out_stride, const float* emb_table, const int32_t* mask,
                     hipStream_t s) {
-    MCVD_REQUIRE(nf <= 256 && nf >= 4, "temb: ngf=%d out of range [4,256]", nf);
+    MCVD_REQUIRE(nf <= 288 && nf >= 4, "temb: ngf=%d out of range [4,288]", nf);
     hipLaunchKernelGGL(temb_mlp_kernel, dim3(B), dim3(64 * TEMB_NW), 0, s, labels, labels_f32, freqs, w0, b0, w1, b1, silu_temb, nf,
                        out_stride, emb_table, mask);
     MCVD_HIP_CHECK(hipGetLastError());
@@ -141,7 +141,7 @@ int launch_temb_mlp(const void* labels, int labels_f32, const float* freqs, cons
 
 // out[b][n] = bias[n] + sum_k act[b][k] * wt[k][n]: a GEMV per row (ONE row in the device loops), 11 k outputs x K = 384..576 for a
 // 4-level net: 17-25 MB of weights per forward.  Block = 64 outputs (16 lanes x float4) x 16 slices of K; every slice keeps its whole
-// share of weight rows in flight (K / 16 <= 72 float4 loads per thread, unrolled by 8), the slices are summed in index order through
+// share of weight rows in flight (K / 16 <= 81 float4 loads per thread, unrolled by 8: K = 4 ngf, + ngf / 2 with cond_emb, ngf <= 288), the slices are summed in index order through
 // the LDS -- the order of a row's sum does not depend on the number of rows.  R rows share one pass over the weights.  (Until round 4:
 // 256 outputs per block, one thread per output walking all of K: 44 blocks, 53-71 us.)
 template <int R>
@@ -184,7 +184,7 @@ int launch_dense_all(const float* act, const float* wt, const float* bias, float
     // N = NE = sum over the Dense_0 entries of 2 * channels, channels = ngf * ch_mult (+ a skip's): build_plan admits ngf % 4 == 0 only
     // (model.cpp), so every entry starts at a multiple of 8 floats and N % 4 == 0 holds for every model the plan accepts (ADVICE r4 asked
     // whether the float4 rows narrowed the supported widths: they did not -- the same plan check predates them).
-    MCVD_REQUIRE(K <= 1152 && N % 4 == 0 && N >= 4, "dense_all: K=%d N=%d (N is a sum of 2 * channels with ngf %% 4 == 0)", K, N);
+    MCVD_REQUIRE(K <= 1296 && N % 4 == 0 && N >= 4, "dense_all: K=%d N=%d (N is a sum of 2 * channels with ngf %% 4 == 0)", K, N);
     const int nb = (N / 4 + 15) / 16;
     if (B == 1)
         hipLaunchKernelGGL(dense_all_kernel<1>, dim3(nb, 1), dim3(256), 0, s, act, wt, bias, out, B, K, N);

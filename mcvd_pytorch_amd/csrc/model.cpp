@@ -415,7 +415,7 @@ int mcvd_model::build_plan() {
     MCVD_REQUIRE(c.n_levels >= 1 && c.n_levels <= MCVD_MAX_LEVELS, "desc: n_levels=%d", c.n_levels);
     MCVD_REQUIRE(c.image_size >= 8 && (c.image_size & (c.image_size - 1)) == 0, "desc: image_size=%d must be a power of two", c.image_size);
     MCVD_REQUIRE((c.image_size >> (c.n_levels - 1)) >= 8, "desc: lowest resolution %d < 8", c.image_size >> (c.n_levels - 1));
-    MCVD_REQUIRE(c.ngf >= 8 && c.ngf % 4 == 0 && c.ngf <= 256, "desc: ngf=%d", c.ngf);
+    MCVD_REQUIRE(c.ngf >= 8 && c.ngf % 4 == 0 && c.ngf <= 288, "desc: ngf=%d out of range [8,288] (a multiple of 4)", c.ngf);
     MCVD_REQUIRE(c.channels > 0 && c.num_frames > 0 && c.num_frames_cond >= 0, "desc: frames/channels");
     MCVD_REQUIRE(!c.spade || (c.num_frames_cond > 0 && c.spade_dim > 0), "desc: spade needs conditioning frames and spade_dim");
     MCVD_REQUIRE(c.num_classes >= 2, "desc: num_classes=%d", c.num_classes);
@@ -1107,7 +1107,9 @@ int mcvd_model::autotune(int B) {
             // (region, cout tile) pairs of a Winograd launch: few of them leave CUs idle, and the deeper K splits are offered
             const bool g8 = op.H == 8 && op.W == 8;
             const long pairs = op.ks == 3 ? (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout))) : 0;
-            const bool few_pairs = op.ks == 3 && 2 * pairs < 1024;
+            // (a layer of more than WINO_MAX_CIN channels has no 2-way split to fall back on -- 4 parts are the shallowest Winograd launch that takes
+            // it -- so it is offered the 4-way ids at every batch; the 8-way one on the terms of every other layer)
+            const bool few_pairs = op.ks == 3 && (2 * pairs < 1024 || cin > WINO_MAX_CIN);
             if (op.ks == 3 && ctx->winograd && ctx->bf16x3 && !spade_fused) {     // Winograd on the bf16 pipe, three exact pieces per operand
                 for (int id : {CK_WINO3, CK_WINO3_K2, CK_WINO3P, CK_WINO3P_K2})    // (persistent: the staging pipeline runs on across the items of a CU)
                     if (int rc = offer(id, op.cot)) return rc;
@@ -1226,7 +1228,8 @@ int mcvd_model::ensure_ksplit(int B) {
         int parts = 2;
         const bool g8 = op.H == 8 && op.W == 8;
         const long pairs = (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout)));
-        if (ctx->autotune && !table && tuned_B != B && 2 * pairs < 1024) parts = 4 * pairs < 1024 ? 8 : 4;    // the candidates autotune() is about to time
+        const bool wide = op.src0.C + (op.src1.kind == REF_NONE ? 0 : op.src1.C) > WINO_MAX_CIN;             // no 2-way split takes it: autotune() offers 4 parts at every batch
+        if (ctx->autotune && !table && tuned_B != B && (2 * pairs < 1024 || wide)) parts = 4 * pairs < 1024 ? 8 : 4;    // the candidates autotune() is about to time
         auto deepen = [&](int shape) { parts = std::max(parts, k_parts(shape)); };
         deepen(ctx->conv_shape);
         if (table) deepen((*table)[i]);
