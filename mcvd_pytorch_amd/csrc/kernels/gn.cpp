@@ -1,6 +1,6 @@
 // GroupNorm statistics -> per-(sample, channel) affine coefficients (A, B) with y = A*x + B, so the consumer
 // conv applies normalisation + temb scale/shift (+ SiLU) while it stages its input tile: the normalised tensor is
-// never written to HBM.  One workgroup per (sample, group), ONE pass over the group's data (pilot-shifted moments).
+// never written to HBM.  One workgroup per (sample, group), ONE pass over the group's data (merged per-stream moments).
 // Input may be a virtual channel concat of two tensors (UNet up path: cat([h, skip])).
 #include "../common.h"
 
@@ -31,34 +31,46 @@ __global__ __launch_bounds__(256) void gn_coef_kernel(GnArgs a) {
         return (c < a.C0) ? a.x0 + ((long)b * a.C0 + c) * HW : a.x1 + ((long)b * a.C1 + (c - a.C0)) * HW;
     };
 
-    // Single pass over the group: sums of (x - p) and (x - p)^2 around a pilot value p (the group's first element), which
-    // keeps the fp32 variance free of the E[x^2] - mean^2 cancellation while reading the tensor from HBM exactly once.
-    const float pilot = chan_ptr(c0)[0];
-    float s0 = 0.f, s1 = 0.f, q0 = 0.f, q1 = 0.f;
+    // Single pass over the group, no pilot value: every float4 contributes its own mean and M2 (four values about their own mean), a stream
+    // folds them into a running (count, mean, M2) with the exact pairwise update
+    //     mean += (m - mean) / (k + 1),   M2 += q + 4 k / (k + 1) * (m - mean)^2        (k float4s so far),
+    // and the block folds its 512 streams with gn_finalize_kernel's identities.  Every term is non-negative and no term is larger than
+    // the group's own M2, so neither a large mean nor an outlier anywhere in the group (the [0, 0] corner of a zero-padded conv output
+    // is the group's first element) costs the variance anything.  The order of the sums depends on the group's shape only.
+    float mu0 = 0.f, mu1 = 0.f, m20 = 0.f, m21 = 0.f;      // the two streams' running mean and M2
+    // r = 1 / (k + 1): the hardware reciprocal (1 ulp) will do -- a mean that is off by an ulp of (m - mean) moves M2 by that much of
+    // (m - mean)^2, the size of the update's own rounding
+    auto fold4 = [](const float4 v, float r, float& mu, float& m2) {
+        const float m = 0.25f * ((v.x + v.y) + (v.z + v.w));
+        const float dx = v.x - m, dy = v.y - m, dz = v.z - m, dw = v.w - m;
+        const float q = (dx * dx + dy * dy) + (dz * dz + dw * dw);
+        const float d = m - mu;
+        mu += d * r;
+        m2 += q + (4.0f - 4.0f * r) * (d * d);            // 4 k / (k + 1)
+    };
     int i = threadIdx.x;
-    for (; i + 256 < n4; i += 512) {                      // two independent float4 streams per thread
+    int k = 0;                                            // float4s each stream has folded: the same for both inside the loop
+    for (; i + 256 < n4; i += 512, ++k) {                 // two independent float4 streams per thread
         const int cla = i / HW4, clb = (i + 256) / HW4;
         const float4 va = *reinterpret_cast<const float4*>(chan_ptr(c0 + cla) + (i - cla * HW4) * 4);
         const float4 vb = *reinterpret_cast<const float4*>(chan_ptr(c0 + clb) + (i + 256 - clb * HW4) * 4);
-        const float ax = va.x - pilot, ay = va.y - pilot, az = va.z - pilot, aw = va.w - pilot;
-        const float bx = vb.x - pilot, by = vb.y - pilot, bz = vb.z - pilot, bw = vb.w - pilot;
-        s0 += (ax + ay) + (az + aw);
-        s1 += (bx + by) + (bz + bw);
-        q0 += (ax * ax + ay * ay) + (az * az + aw * aw);
-        q1 += (bx * bx + by * by) + (bz * bz + bw * bw);
+        const float r = __builtin_amdgcn_rcpf((float)(k + 1));
+        fold4(va, r, mu0, m20);
+        fold4(vb, r, mu1, m21);
     }
+    float k0 = (float)k;
+    const float k1 = (float)k;
     if (i < n4) {
         const int cl = i / HW4;
         const float4 v = *reinterpret_cast<const float4*>(chan_ptr(c0 + cl) + (i - cl * HW4) * 4);
-        const float ax = v.x - pilot, ay = v.y - pilot, az = v.z - pilot, aw = v.w - pilot;
-        s0 += (ax + ay) + (az + aw);
-        q0 += (ax * ax + ay * ay) + (az * az + aw * aw);
+        fold4(v, __builtin_amdgcn_rcpf(k0 + 1.0f), mu0, m20);
+        k0 += 1.0f;
     }
     const float inv_n = 1.0f / (float)(gs * HW);
-    const float ds = block_sum_256(s0 + s1, red) * inv_n;            // E[x - p]
-    const float dq = block_sum_256(q0 + q1, red) * inv_n;            // E[(x - p)^2]
-    const float mean = pilot + ds;
-    const float var = fmaxf(dq - ds * ds, 0.0f);
+    const float na = 4.0f * k0, nb = 4.0f * k1;                      // (0 for a stream, or a thread, that read nothing)
+    const float mean = block_sum_256(na * mu0 + nb * mu1, red) * inv_n;
+    const float da = mu0 - mean, db = mu1 - mean;
+    const float var = block_sum_256((m20 + na * (da * da)) + (m21 + nb * (db * db)), red) * inv_n;
     const float rstd = 1.0f / sqrtf(var + a.eps);
 
     for (int cl = threadIdx.x; cl < gs; cl += 256) {
@@ -161,7 +173,7 @@ __global__ __launch_bounds__(64) void gn_finalize_kernel(GnArgs a, const float* 
     if (lane < gs) {
         reinterpret_cast<float2*>(a.coef)[(long)b * C + cpar] = make_float2(rstd * par0, par1 - mean * rstd * par0);
     }
-    for (int cl = lane + 64; cl < gs; cl += 64) {       // (groups of more than 64 channels: not a shape of the reference's configs)
+    for (int cl = lane + 64; cl < gs; cl += 64) {       // (groups of more than 64 channels: the 2304-channel concats of the ngf-288 nets, 72 per group)
         const int c = c0 + cl;
         float A, Bc;
         if (a.mode == 1) {

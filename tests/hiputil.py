@@ -42,6 +42,21 @@ class Ctx:
         st = buf[:B * Cout * np_ * 2].view(B, Cout, np_, 2) if np_ > 0 else None
         return y, st, np_
 
+    def conv2d_stats_full(self, x0, w, bias, slack=4096, **kw):
+        """conv2d_stats that also returns the whole NaN-prefilled buffer: (y, stats [B, Cout, np, 2], np, buf).  Everything behind the
+        B * Cout * np pairs must still be NaN after the launch; `slack` floats beyond the largest np any kernel uses are there to be
+        looked at as well."""
+        B, Cout, H, W = x0.shape[0], w.shape[0], x0.shape[2], x0.shape[3]
+        buf = torch.full((B * Cout * (H * W // 32) * 2 + slack,), float("nan"), device=x0.device)
+        _lib.check(_lib.lib.mcvd_ctx_set_stats_buffer(self.h, P(buf)))
+        try:
+            y = self.conv2d(x0, w, bias, **kw)
+            np_ = _lib.lib.mcvd_last_conv_stats_np()
+        finally:
+            _lib.check(_lib.lib.mcvd_ctx_set_stats_buffer(self.h, None))
+        st = buf[:B * Cout * np_ * 2].view(B, Cout, np_, 2) if np_ > 0 else None
+        return y, st, np_, buf
+
     def gn_finalize(self, st0, np0, groups, eps, mode, HW, st1=None, np1=1, p0=None, p1=None, emb_stride=0, emb_off=0):
         B, C0 = st0.shape[:2]
         C1 = st1.shape[1] if st1 is not None else 0
