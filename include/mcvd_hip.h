@@ -145,7 +145,7 @@ int mcvd_ctx_set_stream(mcvd_ctx* ctx, void* hip_stream);
  *     "conv_shape" (-1 auto): force a kernel family for every conv (tests): 0/1/2/3 the 256/128/64-pixel / split-K direct tiles, 4 fp32
  *         Winograd F(2x2,3x3) (8: with its 2-way split of the input channels), 5 / 6 / 9 the fp32 all-DMA 1x1 GEMM (16 / 32 channels per
  *         chunk / 64 pixels per wave), 10 / 11 three-piece bf16 Winograd (11: K split), 12 / 13 two-piece fp16 Winograd (13: K split),
- *         24 / 25 one-piece fp16 Winograd (25: K split; the draft arithmetic of "f16x1": kernels/conv_wino1h.cpp), 26 / 27 the two-piece /
+ *         24 / 25 one-piece fp16 Winograd (25: K split; the draft arithmetic of "f16x1": kernels/conv_wino2h.cpp with one piece), 26 / 27 the two-piece /
  *         one-piece fp16 Winograd kernels with the input channels in 4 parts (a chunk count that divides by 4, at least three 16-channel
  *         chunks per part; else 13 / 25, then 12 / 24; with their option off they are 18),
  *         14 / 15 the split-operand 1x1 GEMM with two fp16 / three bf16 pieces, 16 / 17 the three-piece bf16 Winograd kernel as PERSISTENT

@@ -18,7 +18,7 @@ LIB = os.path.join(PKG, "libmcvd_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(ROOT, "include")]
-WINO_OBJS = ("conv_wino.o", "conv_wino3.o", "conv_wino2h.o", "conv_wino3p.o", "conv_wino1h.o")
+WINO_OBJS = ("conv_wino.o", "conv_wino3.o", "conv_wino2h.o", "conv_wino3p.o")
 HOST_ONLY_FLAGS = {"model.cpp": ["-ffp-contract=off"], "api.cpp": ["-ffp-contract=off"],
                    "sampler.cpp": ["-ffp-contract=off"],      # sampler update kernels: one rounding per operation
                    "dsm.cpp": ["-ffp-contract=off"],          # the loss's perturbation: the reference's separate roundings, same Philox bits

@@ -177,15 +177,13 @@ bool conv_wino3p_usable(const ConvArgs& a);
 int launch_conv_wino3p(const ConvArgs& a, hipStream_t s);
 int launch_pack_wino3_weight(const float* w, float* wb, int Cout, int Cin, int CinP, int CoutP, hipStream_t s);    // wb zero-filled
 // the same convolution on the fp16 matrix pipe, operands split into two fp16 pieces (22-bit operands, three piece products; weights
-// pre-split at pack time; conv_wino2h.cpp): tile shape ids 12 / 13 (13: 2-way K split); needs ConvArgs::wph
+// pre-split at pack time; conv_wino2h.cpp): tile shape ids 12 / 13 (13: 2-way K split); needs ConvArgs::wph.
+// np = 1: the same kernel with ONE fp16 piece per operand (a draft arithmetic: 11-bit operands, fp32 accumulate): shape ids 24 / 25 (25: 2-way
+// K split); reads the first piece of the same ConvArgs::wph.  One usable() rule serves both piece counts.
 bool conv_wino2h_usable(const ConvArgs& a);
-int launch_conv_wino2h(const ConvArgs& a, hipStream_t s);
+int launch_conv_wino2h(const ConvArgs& a, int np, hipStream_t s);
 long conv_wino2h_weight_floats(int CinP, int CoutP);          // size of the wph buffer (header + pieces), in floats
 int launch_pack_wino2h_weight(const float* w, float* wh, int Cout, int Cin, int CinP, int CoutP, hipStream_t s);   // wh zero-filled
-// ... with ONE fp16 piece per operand (a draft arithmetic: 11-bit operands, fp32 accumulate; conv_wino1h.cpp): shape ids 24 / 25 (25: 2-way
-// K split); reads the first piece of the same ConvArgs::wph
-bool conv_wino1h_usable(const ConvArgs& a);
-int launch_conv_wino1h(const ConvArgs& a, hipStream_t s);
 // 1x1 GEMM on the 16-bit matrix pipes with split operands (conv1x1_h2.cpp), cout tile a.cot = 1..4: np = 3 three bf16 pieces
 // (fp32-equivalent; tile shape id 15; needs ConvArgs::wpb), np = 2 two fp16 pieces (tile shape id 14; needs ConvArgs::wph); the
 // pieces come from the packed fp32 matrix wp (launch_pack_conv1x1_h2)

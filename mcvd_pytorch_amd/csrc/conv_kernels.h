@@ -39,7 +39,7 @@ enum ConvFamily : int {
     CF_WINO2H,      // ... on the fp16 pipe, two-piece operands (conv_wino2h.cpp)
     CF_WINO3,       // ... on the bf16 pipe, three-piece operands (conv_wino3.cpp)
     CF_WINO3P,      // ... the same as persistent workgroups (conv_wino3p.cpp)
-    CF_WINO1H       // ... on the fp16 pipe, ONE-piece operands: a draft arithmetic (conv_wino1h.cpp)
+    CF_WINO1H       // ... on the fp16 pipe, ONE-piece operands: a draft arithmetic (conv_wino2h.cpp, NP = 1)
 };
 
 enum ConvWeights : int { CW_WP, CW_WPW, CW_WPH, CW_WPB };      // the ConvArgs weight image the kernel reads

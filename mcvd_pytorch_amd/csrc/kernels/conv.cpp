@@ -53,8 +53,8 @@ bool conv_kernel_usable(int id, const ConvArgs& a) {
     const ConvKernelDesc& k = conv_kernel(id);
     switch (k.family) {
         case CF_WINO: return conv_wino_usable(with_k_parts(k, a));
-        case CF_WINO2H: return conv_wino2h_usable(with_k_parts(k, a));
-        case CF_WINO1H: return conv_wino1h_usable(with_k_parts(k, a));
+        case CF_WINO2H:
+        case CF_WINO1H: return conv_wino2h_usable(with_k_parts(k, a));
         case CF_WINO3: return conv_wino3_usable(with_k_parts(k, a));
         case CF_WINO3P: return conv_wino3p_usable(with_k_parts(k, a));
         case CF_SPLIT1: return conv1x1_h2_supported(a, a.cot, k.pieces);
@@ -67,8 +67,8 @@ int conv_kernel_launch(int id, const ConvArgs& a, hipStream_t s) {
     const ConvKernelDesc& k = conv_kernel(id);
     switch (k.family) {
         case CF_WINO: return launch_conv_wino(with_k_parts(k, a), s);
-        case CF_WINO2H: return launch_conv_wino2h(with_k_parts(k, a), s);
-        case CF_WINO1H: return launch_conv_wino1h(with_k_parts(k, a), s);
+        case CF_WINO2H:
+        case CF_WINO1H: return launch_conv_wino2h(with_k_parts(k, a), k.pieces, s);
         case CF_WINO3: return launch_conv_wino3(with_k_parts(k, a), s);
         case CF_WINO3P: return launch_conv_wino3p(with_k_parts(k, a), s);
         case CF_SPLIT1: return launch_conv1x1_h2(a, a.cot, s, k.pieces);

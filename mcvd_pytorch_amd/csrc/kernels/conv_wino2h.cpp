@@ -31,6 +31,29 @@
 //     consecutive MFMAs target different accumulators.
 // VMEM of the K loop is hand-counted (inline asm loads + s_waitcnt vmcnt(N)) exactly as in conv_wino3.cpp; tools/check_wino_isa.py
 // checks the generated code of this file too.
+//
+// ONE PIECE (template parameter NP = 1; shape ids 24 / 25 / 27, context option "f16x1", off by default): the same kernel with the second
+// piece of both operands dropped, each MFMA operand rounded to ONE fp16 value (11 significant bits, round to nearest even):
+//     u * v  ~=  fp16(u * scale) * fp16(16 v)                  |error| <= (2^-10 + 2^-22) |u v| per product, exact in the accumulator
+// A DRAFT arithmetic: it does not meet the fp32 parity gates and is not meant to -- the rounding of the operands, random in sign,
+// leaves ~2^-11 / sqrt(terms) of the summed magnitude in an output.  tests/f16x1_ref.py restates the arithmetic and derives the bound
+// the kernel is held to (tests/test_gpu_f16x1.py).  What one piece changes:
+//   * weights: the kernel reads the FIRST piece of the pack above (launch_pack_wino2h_weight: u1 = fp16(U * scale) is the one-piece
+//     operand; same header, same per-layer power-of-two scale, 1 / scale folded into the epilogue).  The pieces lie in separate
+//     1 KB quads [..][cout sub-tile][piece][64 lanes][4 dwords], so a wave fetches whole, aligned quads and skips every other one
+//     (QS in the kernel): 2 B per weight from L2, no second weight image in memory (a pack of its own would be half the size and contiguous;
+//     the quads are eight full cache lines each, so the skipped ones cost no traffic).
+//   * one MFMA per position and cout sub-tile (two pieces: three); 2 * COT weight quads per wave and chunk in v208-v231.  v232-v255
+//     stay idle: the freed registers are NOT spent on a deeper prefetch or a larger cout tile (nothing measured says it pays).
+//   * activations: the transformed values are rounded with one v_cvt_pk_f16_f32 per channel pair and position and parked in ONE
+//     fp16 plane [position][k half][k pair][tile]: 16 KB per chunk (h2_vw), 74 KiB of LDS + the tables where two pieces take 125 KiB --
+//     two workgroups per CU.  The word index inside the plane is the two-piece one (the piece is the outermost index, 4096 words =
+//     a multiple of the 64 banks), so the bank pattern of its stores and reads is unchanged.
+//   * a value beyond the fp16 range becomes Inf, the accumulator NaN: the library keeps raw tensors away (model.cpp: range guard)
+//     and its non-finite scan reports the normalised ones that get there all the same (behind a SPADE norm: H2_ACT_SCALE below).
+// Everything else -- regions, chunks, phase order, the XCD block-id map, the K split, the epilogue with its GroupNorm partials, the
+// named registers and the hand-counted vmcnt -- is one text.  The per-phase clock recording and the EXP ablations are the two-piece
+// instantiations' only (DIAG in the kernel).
 #include <stdlib.h>
 
 #include "../common.h"
@@ -50,12 +73,12 @@ constexpr int H2_CK = 16;        // input channels per chunk = K of one fp16 MFM
 constexpr int H2_T = 32;         // tiles per workgroup (4 x 8 tiles = 8 x 16 output pixels)
 constexpr int H2_NT = 512;
 constexpr int H2_PP = 24;        // LDS patch row pitch (conv_wino.cpp: WR_PP)
-constexpr int H2_VW = 2 * 16 * 2 * 4 * H2_T;      // 32-bit words of one V chunk: [piece][position][half][pair][tile]
+constexpr int h2_vw(int np) { return np * 16 * 2 * 4 * H2_T; }      // 32-bit words of one V chunk: [piece np][position][half][pair][tile]
 constexpr int H2_MINCH_K4 = 3;  // chunks per part of the 4-way K split, at least: the prologue requests the raw patches of THREE chunks (c_begin,
                                  // c_begin + 1, c_begin + 2) before the first MFMA, and the loop keeps that distance.  In a shorter part the third
                                  // request (clamped, in bounds) fetches and activates a chunk of the NEXT part -- work another workgroup does
                                  // already, on the critical path of a part that has one or two chunks of its own to hide it behind: four such
-                                 // parts pay the prologue four times for nothing.  (Id 13, the 2-way form, keeps the rule it was tuned under: two chunks.)
+                                 // parts pay the prologue four times for nothing.  (Ids 13 and 25, the 2-way forms, keep the rule they were tuned under: two chunks.)
 constexpr int H2_HDR = 4;        // header floats in front of the packed weight pieces: |w|max, scale, 1 / scale, -
 constexpr float H2_ACT_SCALE = 16.0f;             // activations enter the patch times 2^4 (exact): transformed values of the
                                                   // order 10..1e3, second pieces clear of the fp16 denormal range.  |B^T d B| must
@@ -86,23 +109,29 @@ __device__ __forceinline__ void h2_split2(f32x2 v, unsigned& w1, unsigned& w2) {
 // PRO: 0 raw input, 1 affine, 2 affine + SiLU (the GroupNorm / temb prologue of conv_wino.cpp)
 // a.ksplit == 2 / 4 (grid.y = that many): one part of the input channels per workgroup, raw partial result to a.part[part]; the reduce
 //     pass of conv_wino.cpp sums the parts in a fixed order.
-// EXP != 0 (built with -DMCVD_DIAG only): timing-only ablations of the K loop (wrong results; env MCVD_WINO2H_EXP, tests/gpu_diag.py w3exp): bit 0 no tile
+// NP: fp16 pieces per operand, 2 or 1 (the file's header has what one piece changes).
+// EXP != 0 (NP = 2, built with -DMCVD_DIAG only): timing-only ablations of the K loop (wrong results; env MCVD_WINO2H_EXP, tests/gpu_diag.py w3exp): bit 0 no tile
 //     transform, bit 1 no patch activation/park, bit 2 no VMEM in the loop, bit 3 no B-operand reads, bit 4 no MFMA.
 // G8: 8x8 images -- the 32 tiles of a workgroup are TWO whole images (16 tiles each, image i at patch columns 10 i .. 10 i + 9); every
 //     halo element is zero padding, so only the 2 x 64 interior pixels per channel are loaded (slots 0-3 of the six; the other two
 //     fetch a dummy) and the halo of both patch buffers is zeroed once.  The coefficient table holds both samples.
-template <int COT, int PRO, bool G8, int EXP = 0>
+template <int NP, int COT, int PRO, bool G8, int EXP = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void conv_wino2h_kernel(ConvArgs a) {
     // amdgpu_num_vgpr(202): registers the compiler may allocate; v202-v255 hold the in-flight loads and the A operands (H2_LOAD_A)
-    constexpr int NT = H2_NT, CK = H2_CK, T = H2_T, BCO = 32 * COT, PP = H2_PP, VW = H2_VW;
+    constexpr int NT = H2_NT, CK = H2_CK, T = H2_T, BCO = 32 * COT, PP = H2_PP, VW = h2_vw(NP);
+    // The clock recording (rec, sp[], H2_STAMP, the final d[] store) and the EXP ablations belong to the two-piece instantiations: with
+    // DIAG false they are dead code, and the one-piece instantiations neither fetch a.dbg / a.wdma nor carry an instruction of it.
+    constexpr bool DIAG = NP == 2;
+    static_assert((NP == 1 || NP == 2) && (DIAG || EXP == 0), "one or two pieces; ablations of the two-piece kernel only");
     constexpr int PSZ = CK * 10 * PP;           // activated input patch of one chunk: [CK][10 rows][PP]
     constexpr int PBUF = PSZ + 4;               // + dump space for unused patch slots
     constexpr int PCOUNT = G8 ? CK * 2 * 64 : CK * 10 * 18;     // patch elements loaded per chunk
     constexpr int MAXP = 6;                                     // load slots per thread and chunk (G8 uses four of them)
-    constexpr int NQ = 2 * COT;                                 // weight quads per position: COT cout sub-tiles x 2 pieces
+    constexpr int NQ = NP * COT;                                // weight quads per position: COT cout sub-tiles x NP pieces
+    constexpr int QS = 512 / NP;                                // dwords from one quad this kernel reads to the next: one piece skips every other quad of the image
     constexpr int NA = 2 * NQ;                                  // weight loads per wave and chunk
     constexpr int VM_A = NQ + MAXP;                             // see H2_MFMA_PHASE
-    static_assert(MAXP == 6 && NA <= 12, "named-register map below: v202-v207 patch, v208-v255 twelve weight quads");
+    static_assert(MAXP == 6 && NA <= 6 * NP, "named-register map below: v202-v207 patch; weight quads: two pieces v208-v255 (twelve), one piece v208-v231 (six)");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned* sV = reinterpret_cast<unsigned*>(smem);           // [2][VW]
     float* sP = smem + 2 * VW;                  // [2][PBUF]
@@ -113,8 +142,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         asm volatile("" : "={v255}"(top));
     }
     // every kernel argument the prologue needs, fetched NOW (one batch of scalar loads, one wait; conv_wino3.cpp)
-    asm volatile("" :: "s"(a.x0), "s"(a.x1), "s"(a.coef), "s"(a.wph), "s"(a.B), "s"(a.H), "s"(a.W), "s"(a.Cin), "s"(a.CinP), "s"(a.C0),
-                 "s"(a.C1), "s"(a.CoutP), "s"(a.ksplit), "s"(a.dbg), "s"(a.wdma));
+    if constexpr (DIAG)
+        asm volatile("" :: "s"(a.x0), "s"(a.x1), "s"(a.coef), "s"(a.wph), "s"(a.B), "s"(a.H), "s"(a.W), "s"(a.Cin), "s"(a.CinP), "s"(a.C0),
+                     "s"(a.C1), "s"(a.CoutP), "s"(a.ksplit), "s"(a.dbg), "s"(a.wdma));
+    else
+        asm volatile("" :: "s"(a.x0), "s"(a.x1), "s"(a.coef), "s"(a.wph), "s"(a.B), "s"(a.H), "s"(a.W), "s"(a.Cin), "s"(a.CinP), "s"(a.C0),
+                     "s"(a.C1), "s"(a.CoutP), "s"(a.ksplit));
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
     const int H = a.H, W = a.W, HW = H * W, Cin = a.Cin;
     // ---- chunk range of this workgroup (a.ksplit == 2 / 4: blockIdx.y picks one part of the input channels).  The coefficient table
@@ -161,7 +194,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
     const int s_ty = G8 ? (s_tile >> 2) & 3 : s_tile >> 3, s_tx = G8 ? (s_tile & 3) + 5 * (s_tile >> 4) : s_tile & 7;
     // LDS patch: [pair 8][10 rows][PP columns][2 channels] floats.  Rows rg, rg+1, rg+2 of the tile's 4x4 window:
     const int p_rd = ((s_cp * 10 + 2 * s_ty + rg) * PP + 2 * s_tx) * 2;
-    // word of (piece 0, position 8*rg, half, pair, tile); one position further = 256 words, one piece = 4096
+    // word of (piece 0, position 8*rg, half, pair, tile); one position further = 256 words, one piece (NP = 2) = 4096
     const int v_wr = ((8 * rg * 2 + (s_cp & 1)) * 4 + (s_cp >> 1)) * T + s_tile;
 
     // ---- patch-load slots (chunk invariant): p_pk = LDS float index of the element (12 bits) | channel code << 12, code = channel
@@ -197,15 +230,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         }
     }
 
-    // ---- weight fetch: the NA quads of a wave per chunk are contiguous: quad q = (i * COT + ct) * 2 + piece of positions 2w + i at
-    //      wr_base + chunk * (16*COT*512) + q * 256 + lane * 4   dwords
+    // ---- weight fetch: the NA quads of a wave per chunk: quad q = (i * COT + ct) * NP + piece of positions 2w + i at
+    //      wr_base + chunk * (16*COT*512) + q * QS + lane * 4   dwords
+    //      (two pieces: contiguous, QS = 256; one piece: quad q is the piece-0 quad 2q of the same image, QS = 512)
     const int wave_u = __builtin_amdgcn_readfirstlane(wave);
     const unsigned* wr_base = reinterpret_cast<const unsigned*>(a.wph) + H2_HDR + ((long)cotile * (a.CinP / CK) * 16 + 2 * wave_u) * (COT * 512);
     const unsigned wr_voff = (unsigned)lane * 16u;
 
     /* IN-FLIGHT DATA LIVES IN REGISTERS THE COMPILER DOES NOT ALLOCATE (conv_wino3.cpp has the story).  The kernel is compiled with
        amdgpu_num_vgpr(202): v202-v255 are never touched by generated code.  The asm loads write them (weight quad q: v[208 + 4q :
-       211 + 4q]; patch slots: v202-v207), the waits are bare s_waitcnt, the MFMAs name their A operand in the instruction text.
+       211 + 4q], q < NA -- `if ((q) == K)` below drops the entries of H2_QUADS an instantiation does not use; patch slots: v202-v207),
+       the waits are bare s_waitcnt, the MFMAs name their A operand in the instruction text.
        Every statement that touches a named register is `asm volatile` (program order among them is kept) except the patch FMAs, which
        take the wait's token (an SGPR) as an operand. */
 #define H2_QUADS(X, q, A1, A2) X(0, "v[208:211]", q, A1, A2) X(1, "v[212:215]", q, A1, A2) X(2, "v[216:219]", q, A1, A2) X(3, "v[220:223]", q, A1, A2) X(4, "v[224:227]", q, A1, A2) X(5, "v[228:231]", q, A1, A2) X(6, "v[232:235]", q, A1, A2) X(7, "v[236:239]", q, A1, A2) X(8, "v[240:243]", q, A1, A2) X(9, "v[244:247]", q, A1, A2) X(10, "v[248:251]", q, A1, A2) X(11, "v[252:255]", q, A1, A2)
@@ -214,21 +249,21 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
     /* the NQ weight quads of position 2w + i of chunk `ch` */
 #define H2_LOAD_A(ch, i)                                                                                        \
     {                                                                                                           \
-        const unsigned* ua = wr_base + (long)(ch) * (16 * COT * 512) + (i) * (NQ * 256);                        \
-        _Pragma("unroll") for (int qq = 0; qq < NQ; ++qq) { H2_QUADS(H2_LD1, (i) * NQ + qq, ua + qq * 256, 0) } \
+        const unsigned* ua = wr_base + (long)(ch) * (16 * COT * 512) + (i) * (NQ * QS);                         \
+        _Pragma("unroll") for (int qq = 0; qq < NQ; ++qq) { H2_QUADS(H2_LD1, (i) * NQ + qq, ua + qq * QS, 0) }  \
     }
-    /* weight piece `pc` of every cout sub-tile of position 2w + i of chunk `ch` (quads 2 * (i * COT + ct) + pc) */
+    /* weight piece `pc` of every cout sub-tile of position 2w + i of chunk `ch` (quads NP * (i * COT + ct) + pc; one piece: H2_LOAD_A) */
 #define H2_LOAD_A_PIECE(ch, i, pc)                                                                              \
     {                                                                                                           \
-        const unsigned* ua = wr_base + (long)(ch) * (16 * COT * 512) + (i) * (NQ * 256);                        \
-        _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { H2_QUADS(H2_LD1, (i) * NQ + 2 * ct + (pc), ua + (2 * ct + (pc)) * 256, 0) } \
+        const unsigned* ua = wr_base + (long)(ch) * (16 * COT * 512) + (i) * (NQ * QS);                         \
+        _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { H2_QUADS(H2_LD1, (i) * NQ + NP * ct + (pc), ua + (NP * ct + (pc)) * QS, 0) } \
     }
     /* prologue: quads Q0 .. Q1-1 of chunk `ch`, issued behind the instructions that produced DEP (which read the registers) */
 #define H2_LD1D(K, R, q, P, DEP) if ((q) == K) asm volatile("global_load_dwordx4 " R ", %0, %1" :: "v"(wr_voff), "s"(P), "v"(DEP[0]), "v"(DEP[1]), "v"(DEP[2]), "v"(DEP[3]), "v"(DEP[4]), "v"(DEP[5]) : "memory");
 #define H2_LOAD_A_RANGE(ch, Q0, Q1, DEP)                                                                        \
     {                                                                                                           \
         const unsigned* ua = wr_base + (long)(ch) * (16 * COT * 512);                                           \
-        _Pragma("unroll") for (int qq = (Q0); qq < (Q1); ++qq) { H2_QUADS(H2_LD1D, qq, ua + qq * 256, DEP) }    \
+        _Pragma("unroll") for (int qq = (Q0); qq < (Q1); ++qq) { H2_QUADS(H2_LD1D, qq, ua + qq * QS, DEP) }     \
     }
 #define H2_WAIT(N) asm volatile("s_waitcnt vmcnt(%1)\n\ts_mov_b32 %0, 0" : "=s"(vtok) : "n"(N) : "memory");
     /* unconditional, clamped raw loads of the patch of chunk `ch` (conv_wino.cpp: WR_LOAD_P) */
@@ -283,7 +318,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         }                                                                                                       \
     }
     /* rows 2rg and 2rg+1 of B^T d for the two channels of the pair (packed fp32: .x = channel s_ca, .y = s_ca + 2), (.) B,      \
-       two-way fp16 split, 16 stores:                                                                                        \
+       two-way fp16 split, 16 stores (one piece: one fp16 rounding, 8 stores):                                               \
        row 0: d0 - d2   row 1: d1 + d2   row 2: d2 - d1   row 3: d1 - d3;   (.) B: m0 - m2, m1 + m2, m2 - m1, m1 - m3 */      \
 #define H2_READ_R(ch, RW)                                                                                       \
     {                                                                                                           \
@@ -303,10 +338,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
             const f32x2 m0 = row ? my[0] : mx[0], m1 = row ? my[1] : mx[1], m2 = row ? my[2] : mx[2], m3 = row ? my[3] : mx[3]; \
             const f32x2 v0 = m0 - m2, v1 = m1 + m2, v2 = m2 - m1, v3 = m1 - m3;                                 \
             _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                     \
-                unsigned w1, w2;                                                                                \
-                h2_split2(q == 0 ? v0 : q == 1 ? v1 : q == 2 ? v2 : v3, w1, w2);                                \
-                vdst[(row * 4 + q) * 256] = w1;                                                                 \
-                vdst[(row * 4 + q) * 256 + 4096] = w2;                                                          \
+                const f32x2 vv = q == 0 ? v0 : q == 1 ? v1 : q == 2 ? v2 : v3;                                  \
+                if constexpr (NP == 2) {                                                                        \
+                    unsigned w1, w2;                                                                            \
+                    h2_split2(vv, w1, w2);                                                                      \
+                    vdst[(row * 4 + q) * 256] = w1;                                                             \
+                    vdst[(row * 4 + q) * 256 + 4096] = w2;                                                      \
+                } else {                                                                                        \
+                    /* no clamp either: beyond the fp16 range the value becomes Inf and the accumulator NaN -- loud (h2_split2) */ \
+                    vdst[(row * 4 + q) * 256] = h2_cvt_pk(vv.x, vv.y);                                          \
+                }                                                                                               \
             }                                                                                                   \
         }                                                                                                       \
     }
@@ -315,33 +356,37 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
     {                                                                                                           \
         const unsigned* q = sVc + (((2 * wave + (i)) * 2 + half) * 4) * T + l31;                                \
         _Pragma("unroll") for (int jp = 0; jp < 4; ++jp) {                                                      \
-            BQ[0][jp] = q[jp * T]; BQ[1][jp] = q[4096 + jp * T];                                                \
+            BQ[0][jp] = q[jp * T];                                                                              \
+            if constexpr (NP == 2) BQ[1][jp] = q[4096 + jp * T];                                                \
         }                                                                                                       \
     }
     /* all MFMAs of chunk `ch` (V(ch) in LDS, weights(ch) in the named registers).  Per position 2w + i: wait for its NQ quads, 3*COT  \
        MFMAs ordered piece-major (u2 v1, u1 v2, u1 v1: smallest class first; consecutive MFMAs write different accumulators), and -- NEXT \
        -- the same NQ quads are reloaded for chunk ch+1 (the matrix pipe has read its A operands by the time the wave gets past the   \
-       MFMA: it issues in order).  In-order VMEM bookkeeping: when the quads of a position are needed, the loads issued after them    \
-       are the other position's NQ quads and one patch group: vmcnt(NQ + MAXP), in both phase orders. */                              \
+       MFMA: it issues in order).  One piece: u1 v1 alone, COT MFMAs, one per cout sub-tile.  In-order VMEM bookkeeping: when the     \
+       quads of a position are needed, the loads issued after them are the other position's NQ quads and one patch group:            \
+       vmcnt(NQ + MAXP), in both phase orders. */                                                                                    \
 #define H2_MFMA_PHASE(ch, NEXT)                                                                                 \
     {                                                                                                           \
         const unsigned* sVc = sV + (((ch) & 1) ? VW : 0);                                                       \
-        u32x4 bq[2][2];                                                                                         \
+        u32x4 bq[2][NP];                                                                                        \
         if (!(EXP & 8)) { H2_LOAD_B(0, bq[0]) H2_LOAD_B(1, bq[1]) }                                             \
-        else { _Pragma("unroll") for (int p = 0; p < 2; ++p) { bq[0][p] = u32x4{1, 2, 3, 4}; bq[1][p] = u32x4{5, 6, 7, 8}; } } \
+        else { _Pragma("unroll") for (int p = 0; p < NP; ++p) { bq[0][p] = u32x4{1, 2, 3, 4}; bq[1][p] = u32x4{5, 6, 7, 8}; } } \
         _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
             if (NEXT && !(EXP & 4)) H2_WAIT(VM_A)                                                               \
             if (!(EXP & 16)) {                                                                                  \
                 /* u2 v1 first: the second weight piece is re-requested for chunk ch+1 right behind its only product, the first     \
                    piece behind the last one (conv_wino3.cpp: all quads in one burst stall the wave in the issue) */                 \
-                _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { H2_QUADS(H2_MF1, 2 * (i * COT + ct) + 1, acc[i][ct], bq[i][0]) }  \
-                if (NEXT && !(EXP & 4)) H2_LOAD_A_PIECE((ch) + 1, i, 1)                                         \
-                _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { H2_QUADS(H2_MF1, 2 * (i * COT + ct), acc[i][ct], bq[i][1]) }      \
-                _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { H2_QUADS(H2_MF1, 2 * (i * COT + ct), acc[i][ct], bq[i][0]) }      \
+                if constexpr (NP == 2) {                                                                        \
+                    _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { H2_QUADS(H2_MF1, 2 * (i * COT + ct) + 1, acc[i][ct], bq[i][0]) }  \
+                    if (NEXT && !(EXP & 4)) H2_LOAD_A_PIECE((ch) + 1, i, 1)                                     \
+                    _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { H2_QUADS(H2_MF1, 2 * (i * COT + ct), acc[i][ct], bq[i][1]) }     \
+                }                                                                                               \
+                _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { H2_QUADS(H2_MF1, NP * (i * COT + ct), acc[i][ct], bq[i][0]) }     \
                 if (NEXT && !(EXP & 4)) H2_LOAD_A_PIECE((ch) + 1, i, 0)                                         \
             } else {                                                                                            \
                 _Pragma("unroll") for (int ct = 0; ct < COT; ++ct)                                              \
-                    acc[i][ct][0] += __builtin_bit_cast(float, bq[i][0][0] ^ bq[i][1][1] ^ bq[i][0][2] ^ bq[i][1][3]); \
+                    acc[i][ct][0] += __builtin_bit_cast(float, bq[i][0][0] ^ bq[i][NP - 1][1] ^ bq[i][0][2] ^ bq[i][NP - 1][3]); \
                 if (NEXT && !(EXP & 4)) H2_LOAD_A((ch) + 1, i)                                                  \
             }                                                                                                   \
         }                                                                                                       \
@@ -371,8 +416,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
             for (int r = 0; r < 16; ++r) acc[i][ct][r] = 0.0f;
 
     // diagnostics (mcvd_ctx_set_debug_buffer): shader-clock time the wave a.wdma spends per phase
-    const bool rec = a.dbg != nullptr && wave == (a.wdma & 63);
-    const bool sub = (a.wdma & 64) != 0;           // record prologue / epilogue sub-phase stamps instead of the wall clock
+    const bool rec = DIAG && a.dbg != nullptr && wave == (a.wdma & 63);
+    const bool sub = DIAG && (a.wdma & 64) != 0;          // record prologue / epilogue sub-phase stamps instead of the wall clock
     unsigned long long sp[3] = {0, 0, 0};
     unsigned long long tk0 = 0, tprev = 0, dt[2] = {0, 0}, rt0 = 0;
     if (rec) {
@@ -496,7 +541,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         asm volatile("s_nop 15\n\ts_nop 15" : "+v"(acc[0][0]), "+v"(acc[1][0]) :: "memory");
 
     // ---------------- inverse transform + epilogue, one 32-cout sub-tile at a time ----------------
-    float* sM = smem;                      // [16 positions][32 couts][32 tiles] = 64 KiB
+    float* sM = smem;                      // [16 positions][32 couts][32 tiles] = 64 KiB (one piece: over both V planes, the patches and the head
+                                           // of the coefficient / offset tables -- all dead; the allocation is 74 KiB + the coefficients)
     const int e_tile = tid & 31, e_col0 = tid >> 5;            // two (cout, tile) tasks per thread: couts e_col0 and e_col0 + 16
     const int e_ty = G8 ? (e_tile >> 2) & 3 : e_tile >> 3, e_tx = G8 ? e_tile & 3 : e_tile & 7;
     const int e_b = min(b + (G8 ? e_tile >> 4 : 0), a.B - 1);          // G8: the tile's sample (clamped for the loads)
@@ -638,61 +684,70 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
 #undef H2_VALU_PHASE
 }
 
-// pc: the channels of one part (wino_part_channels): the coefficient table's entries per sample
-static size_t wino2h_lds_bytes(int pc, bool g8) {
-    return (size_t)(2 * H2_VW + 2 * (H2_CK * 10 * H2_PP + 4) + (g8 ? 4 : 2) * pc + 6 * H2_NT) * sizeof(float);
+// np: pieces; pc: the channels of one part (wino_part_channels): the coefficient table's entries per sample.  One piece asks for its one
+// V plane only (74 KiB + the tables; two pieces: 125 KiB): two of its workgroups share a CU's LDS.
+static constexpr size_t wino2h_lds_bytes(int np, int pc, bool g8) {
+    return (size_t)(2 * h2_vw(np) + 2 * (H2_CK * 10 * H2_PP + 4) + (g8 ? 4 : 2) * pc + 6 * H2_NT) * sizeof(float);
 }
+// conv_wino2h_usable() serves both piece counts with the two-piece size in its LDS bound: the size grows with np, pc and g8, usable() holds pc
+// to WINO_TABLE_CH, and the largest request fits -- the bound never decides, for either count
+static_assert(wino2h_lds_bytes(2, WINO_TABLE_CH, true) == 124960 && wino2h_lds_bytes(2, WINO_TABLE_CH, true) <= 160 * 1024,
+              "two pieces, a full coefficient table for two samples: the most LDS a usable launch asks for");
 
 // the K-split second pass lives in conv_wino.cpp
 int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s);
 
-template <int COT, int PRO, bool G8, int EXP>
+template <int NP, int COT, int PRO, bool G8, int EXP>
 static int wino2h_launch_k(const ConvArgs& k, dim3 grid, size_t lds, hipStream_t s) {
     static PerDeviceOnce raised;
     if (raised.first_use()) {
-        MCVD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino2h_kernel<COT, PRO, G8, EXP>),
+        MCVD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino2h_kernel<NP, COT, PRO, G8, EXP>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         raised.done();
     }
-    hipLaunchKernelGGL((conv_wino2h_kernel<COT, PRO, G8, EXP>), grid, dim3(H2_NT), lds, s, k);
+    hipLaunchKernelGGL((conv_wino2h_kernel<NP, COT, PRO, G8, EXP>), grid, dim3(H2_NT), lds, s, k);
     return 0;
 }
 
-template <int COT, int PRO, bool G8>
+template <int NP, int COT, int PRO, bool G8>
 static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
-    const size_t lds = wino2h_lds_bytes(wino_part_channels(a.CinP, a.ksplit), G8);
+    const size_t lds = wino2h_lds_bytes(NP, wino_part_channels(a.CinP, a.ksplit), G8);
     const int nreg = G8 ? (a.B + 1) / 2 : a.B * (a.H / 8) * (a.W / 16);
     const int ksp = a.ksplit >= 2 ? a.ksplit : 1;
     dim3 grid(((nreg + 7) / 8) * 8 * (a.CoutP / BCO), ksp);
-    ConvArgs k = a;
     int rc = 0;
-    if (k.dbg) k.wdma = 0;                 // wave 0 records its phase times
+    if constexpr (NP == 1) {               // no recording, no ablations (DIAG in the kernel): the caller's arguments as they come
+        rc = wino2h_launch_k<1, COT, PRO, G8, 0>(a, grid, lds, s);
+    } else {
+        ConvArgs k = a;
+        if (k.dbg) k.wdma = 0;             // wave 0 records its phase times
 #ifdef MCVD_DIAG
-    // diagnostics build only (build.py --diag): which wave records, and the timing-only ablations of the K loop (WRONG RESULTS; the
-    // production library has neither the env hooks nor the ablation kernels)
-    if (k.dbg) {
-        const char* w = getenv("MCVD_DBG_WAVE");
-        k.wdma = w ? atoi(w) : 0;
-    }
-    const char* exp_s = getenv("MCVD_WINO2H_EXP");
-    const int e = exp_s ? atoi(exp_s) : 0;
-    if (COT == 3 && PRO == 2 && !G8 && e != 0) {           // tests/gpu_diag.py w3exp
-        switch (e) {
-            case 1: rc = wino2h_launch_k<3, 2, false, 1>(k, grid, lds, s); break;        // no transform
-            case 2: rc = wino2h_launch_k<3, 2, false, 2>(k, grid, lds, s); break;        // no patch activation / park
-            case 3: rc = wino2h_launch_k<3, 2, false, 3>(k, grid, lds, s); break;        // neither
-            case 4: rc = wino2h_launch_k<3, 2, false, 4>(k, grid, lds, s); break;        // no VMEM in the loop
-            case 16: rc = wino2h_launch_k<3, 2, false, 16>(k, grid, lds, s); break;      // everything but the MFMAs
-            case 15: rc = wino2h_launch_k<3, 2, false, 15>(k, grid, lds, s); break;      // MFMA only
-            case 27: rc = wino2h_launch_k<3, 2, false, 27>(k, grid, lds, s); break;      // VMEM only
-            case 11: rc = wino2h_launch_k<3, 2, false, 11>(k, grid, lds, s); break;      // VMEM + MFMA only
-            default: mcvd::set_error("MCVD_WINO2H_EXP=%d is not a built ablation", e); return -1;
+        // diagnostics build only (build.py --diag): which wave records, and the timing-only ablations of the K loop (WRONG RESULTS; the
+        // production library has neither the env hooks nor the ablation kernels)
+        if (k.dbg) {
+            const char* w = getenv("MCVD_DBG_WAVE");
+            k.wdma = w ? atoi(w) : 0;
         }
-    } else
+        const char* exp_s = getenv("MCVD_WINO2H_EXP");
+        const int e = exp_s ? atoi(exp_s) : 0;
+        if (COT == 3 && PRO == 2 && !G8 && e != 0) {           // tests/gpu_diag.py w3exp
+            switch (e) {
+                case 1: rc = wino2h_launch_k<2, 3, 2, false, 1>(k, grid, lds, s); break;        // no transform
+                case 2: rc = wino2h_launch_k<2, 3, 2, false, 2>(k, grid, lds, s); break;        // no patch activation / park
+                case 3: rc = wino2h_launch_k<2, 3, 2, false, 3>(k, grid, lds, s); break;        // neither
+                case 4: rc = wino2h_launch_k<2, 3, 2, false, 4>(k, grid, lds, s); break;        // no VMEM in the loop
+                case 16: rc = wino2h_launch_k<2, 3, 2, false, 16>(k, grid, lds, s); break;      // everything but the MFMAs
+                case 15: rc = wino2h_launch_k<2, 3, 2, false, 15>(k, grid, lds, s); break;      // MFMA only
+                case 27: rc = wino2h_launch_k<2, 3, 2, false, 27>(k, grid, lds, s); break;      // VMEM only
+                case 11: rc = wino2h_launch_k<2, 3, 2, false, 11>(k, grid, lds, s); break;      // VMEM + MFMA only
+                default: mcvd::set_error("MCVD_WINO2H_EXP=%d is not a built ablation", e); return -1;
+            }
+        } else
 #endif
-    {
-        rc = wino2h_launch_k<COT, PRO, G8, 0>(k, grid, lds, s);
+        {
+            rc = wino2h_launch_k<2, COT, PRO, G8, 0>(k, grid, lds, s);
+        }
     }
     if (rc) return rc;
     MCVD_HIP_CHECK(hipGetLastError());
@@ -701,42 +756,48 @@ static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
     return 0;
 }
 
-template <int COT, bool G8>
+template <int NP, int COT, bool G8>
 static int wino2h_launch1(const ConvArgs& a, hipStream_t s) {
-    if (!a.coef && !a.act) return wino2h_launch2<COT, 0, G8>(a, s);
-    if (!a.act) return wino2h_launch2<COT, 1, G8>(a, s);
-    return wino2h_launch2<COT, 2, G8>(a, s);
+    if (!a.coef && !a.act) return wino2h_launch2<NP, COT, 0, G8>(a, s);
+    if (!a.act) return wino2h_launch2<NP, COT, 1, G8>(a, s);
+    return wino2h_launch2<NP, COT, 2, G8>(a, s);
 }
 
-template <int COT>
+template <int NP, int COT>
 static int wino2h_launch(const ConvArgs& a, hipStream_t s) {
-    return (a.H == 8 && a.W == 8) ? wino2h_launch1<COT, true>(a, s) : wino2h_launch1<COT, false>(a, s);
+    return (a.H == 8 && a.W == 8) ? wino2h_launch1<NP, COT, true>(a, s) : wino2h_launch1<NP, COT, false>(a, s);
 }
 
-// Shape ids 12 / 13 / 26 apply to this launch: regions of 8 x 16 output pixels or 8 x 8 images (two per workgroup), no SPADE prologue,
-// pre-split packed weights present (13: and an even chunk count, two chunks per part at least; 26: a chunk count that divides by 4,
-// H2_MINCH_K4 chunks per part at least; both: room for the parts in a.part).
+// Shape ids 12 / 13 / 26 (two pieces) and 24 / 25 / 27 (one piece) apply to this launch: regions of 8 x 16 output pixels or 8 x 8 images (two per
+// workgroup), no SPADE prologue, pre-split packed weights present (13 / 25: and an even chunk count, two chunks per part at least; 26 / 27: a
+// chunk count that divides by 4, H2_MINCH_K4 chunks per part at least; all four: room for the parts in a.part).  One rule for both piece counts.
 bool conv_wino2h_usable(const ConvArgs& a) {
     const bool g8 = a.H == 8 && a.W == 8;
     const int nch = a.CinP / H2_CK;
     return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) && wino_part_channels(a.CinP, a.ksplit) <= WINO_TABLE_CH &&
            a.CinP % H2_CK == 0 && (a.C1 == 0 || a.C0 % H2_CK == 0) && a.H * a.W <= 16384 &&
-           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino2h_lds_bytes(wino_part_channels(a.CinP, a.ksplit), g8) <= 160 * 1024 &&
+           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino2h_lds_bytes(2, wino_part_channels(a.CinP, a.ksplit), g8) <= 160 * 1024 &&
            (a.ksplit < 2 || ((a.ksplit == 2 || (a.ksplit == 4 && nch / 4 >= H2_MINCH_K4)) && nch % a.ksplit == 0 && nch >= 2 * a.ksplit &&
                              conv_part_fits(a)));
 }
 
-// a.wph: the layout of launch_pack_wino2h_weight, packed for conv_wino_cout_tile(Cout).
-int launch_conv_wino2h(const ConvArgs& a, hipStream_t s) {
-    MCVD_REQUIRE(conv_wino2h_usable(a), "winograd f16x2 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d, %d channels per K part)",
-                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wph ? "present" : "missing", wino_max_cin(a.ksplit), WINO_TABLE_CH);
+template <int NP>
+static int wino2h_launch_np(const ConvArgs& a, hipStream_t s) {
+    MCVD_REQUIRE(conv_wino2h_usable(a), "winograd f16x%d conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d, %d channels per K part)",
+                 NP, a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wph ? "present" : "missing", wino_max_cin(a.ksplit), WINO_TABLE_CH);
     const int cot = conv_wino_cout_tile(a.Cout);
-    MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd f16x2 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
+    MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd f16x%d conv: CoutP=%d vs tile %d", NP, a.CoutP, 32 * cot);
     switch (cot) {
-        case 1: return wino2h_launch<1>(a, s);
-        case 2: return wino2h_launch<2>(a, s);
-        default: return wino2h_launch<3>(a, s);
+        case 1: return wino2h_launch<NP, 1>(a, s);
+        case 2: return wino2h_launch<NP, 2>(a, s);
+        default: return wino2h_launch<NP, 3>(a, s);
     }
+}
+
+// a.wph: the layout of launch_pack_wino2h_weight, packed for conv_wino_cout_tile(Cout).  np: operand pieces, 2 or 1 (one: the first piece is read).
+int launch_conv_wino2h(const ConvArgs& a, int np, hipStream_t s) {
+    MCVD_REQUIRE(np == 1 || np == 2, "winograd fp16 conv: %d operand pieces", np);
+    return np == 1 ? wino2h_launch_np<1>(a, s) : wino2h_launch_np<2>(a, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

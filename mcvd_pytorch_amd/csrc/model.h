@@ -39,7 +39,7 @@ struct mcvd_ctx {
     int f16x2 = 0;                 // offer the two-piece fp16 kernels (conv_wino2h.cpp, conv1x1_h2.cpp, attention_h2.cpp with NP = 2: 22-bit operands,
                                    //    fp16 exponent range, fp32 accumulate) as well.  OFF by default: narrower arithmetic than the reference's.
                                    //    Convs with a raw (not normalised) input never take them; see model.cpp "f16x2 range guard"
-    int f16x1 = 0;                 // offer the ONE-piece fp16 Winograd kernel (conv_wino1h.cpp: operands rounded to 11 bits, fp16 exponent range, fp32
+    int f16x1 = 0;                 // offer the ONE-piece fp16 Winograd kernel (conv_wino2h.cpp with NP = 1: operands rounded to 11 bits, fp16 exponent range, fp32
                                    //    accumulate) for the 3x3 convs f16x2 may take.  A DRAFT arithmetic, OFF by default: it does not meet the parity
                                    //    tolerances.  1x1 GEMMs and attention stay where f16x2 / bf16x3 put them.  Same range guard as f16x2
     int conv_dma1 = 1;             // offer the all-DMA 1x1 GEMM kernel (conv1x1_dma.cpp) to the autotuner

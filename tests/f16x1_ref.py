@@ -1,4 +1,4 @@
-"""The one-piece fp16 Winograd conv (conv_wino1h.cpp, context option "f16x1", shape ids 24 / 25) restated in fp64, rounding where the
+"""The one-piece fp16 Winograd conv (conv_wino2h.cpp with NP = 1, context option "f16x1", shape ids 24 / 25) restated in fp64, rounding where the
 kernel rounds, with the error bound the kernel is held to.  A helper of tests/test_f16x1_arithmetic_cpu.py, tests/test_gpu_f16x1.py and
 tools/gen_f16x1_golden.py; no GPU.
 

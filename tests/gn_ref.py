@@ -121,7 +121,7 @@ def expected_np(kid, H, W, B=1):
             # hw4 == 16 || hw4 == 64 (8x8 and 16x16 planes: the fused reduce + finalize or the reduce pass with statistics),
             # else `if (a.stats) set_last_conv_stats_np(0)`.
             return 1 if HW in (64, 256) else 0
-        # conv_wino.cpp launch_conv_wino / conv_wino2h.cpp / conv_wino3.cpp / conv_wino1h.cpp:
+        # conv_wino.cpp launch_conv_wino / conv_wino2h.cpp (both piece counts) / conv_wino3.cpp:
         #   `set_last_conv_stats_np(G8 ? 1 : (a.H / 8) * (a.W / 16))`; conv_wino3p.cpp (no 8x8 form): `(a.H / 8) * (a.W / 16)`.
         return 1 if (H == 8 and W == 8) else (H // 8) * (W // 16)
     if fam == "DMA1":

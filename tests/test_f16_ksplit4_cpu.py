@@ -1,4 +1,4 @@
-"""CPU: the 4-way K split of the two fp16 Winograd kernels (shape ids 26 / 27; conv_wino2h.cpp, conv_wino1h.cpp) -- the partition of the
+"""CPU: the 4-way K split of the two fp16 Winograd kernels (shape ids 26 / 27; conv_wino2h.cpp with two pieces and with one) -- the partition of the
 16-channel chunks into parts and the rule that admits a layer, restated here and walked over every layer shape up to 1024 channels.
 
 The kernels: `nch = CinP / 16` chunks; workgroup (.., blockIdx.y = part) contracts chunks [part * nch / 4, (part + 1) * nch / 4) and writes its raw
@@ -33,11 +33,12 @@ def chunk_source(c, Cin, C0):
 
 
 def test_the_restated_minimum_is_the_kernels():
-    for f, name in (("conv_wino1h.cpp", "H1_MINCH_K4"), ("conv_wino2h.cpp", "H2_MINCH_K4")):
-        src = open(os.path.join(CSRC, "kernels", f)).read()
-        m = re.search(r"constexpr int %s = (\d+);" % name, src)
-        assert m and int(m.group(1)) == MINCH_K4, (f, m and m.group(0))
-        assert re.search(r"a\.ksplit == 4 && nch / 4 >= %s" % name, src), f"{f}: usable() does not state the minimum"
+    f, name = "conv_wino2h.cpp", "H2_MINCH_K4"               # one kernel source, one constant, one usable() for both piece counts
+    src = open(os.path.join(CSRC, "kernels", f)).read()
+    m = re.findall(r"constexpr int \w*MINCH_K4 = (\d+);", src)
+    assert m == [str(MINCH_K4)] and re.search(r"constexpr int %s = (\d+);" % name, src), (f, m)
+    assert re.search(r"a\.ksplit == 4 && nch / 4 >= %s" % name, src), f"{f}: usable() does not state the minimum"
+    assert len(re.findall(r"\nbool conv_wino\w+_usable\(", src)) == 1
     table = open(os.path.join(CSRC, "conv_kernels.h")).read()
     assert "CK_WINO2H_K4 = 26" in table and "CK_WINO1H_K4 = 27" in table
 

@@ -1,4 +1,4 @@
-"""CPU: the one-piece fp16 Winograd arithmetic (conv_wino1h.cpp, option "f16x1") -- its fp64 restatement (tests/f16x1_ref.py) against
+"""CPU: the one-piece fp16 Winograd arithmetic (conv_wino2h.cpp with NP = 1, option "f16x1") -- its fp64 restatement (tests/f16x1_ref.py) against
 the bound derived there, and the addresses the kernel forms into the two-piece weight image it shares with conv_wino2h.cpp."""
 import numpy as np
 import pytest
@@ -68,11 +68,11 @@ def test_weight_scale_rule():
 # ------------------------------------------------------------------------------------------------ addresses into the shared weight image
 @pytest.mark.parametrize("COT,Cout,Cin,CinP", [(3, 192, 40, 48), (2, 128, 32, 32), (1, 64, 16, 16)])
 def test_one_piece_loop_reads_exactly_the_first_pieces(COT, Cout, Cin, CinP):
-    """conv_wino1h.cpp reads conv_wino2h.cpp's weight image [cout tile][chunk][position][cout sub-tile][piece][64 lanes][4 dwords]
-    (pack_wino2h_weight_kernel, restated here halfword by halfword).  The addresses of H1_LOAD_A -- per (cout tile, chunk, wave, position
+    """conv_wino2h.cpp's one-piece form (NP = 1) reads the two-piece weight image [cout tile][chunk][position][cout sub-tile][piece][64 lanes][4 dwords]
+    (pack_wino2h_weight_kernel, restated here halfword by halfword).  The addresses of H2_LOAD_A (QS = 512) -- per (cout tile, chunk, wave, position
     of the wave, cout sub-tile): 64 lanes x 4 dwords -- must hit every dword of every piece-0 quad exactly once and no dword of a piece-1
-    quad; and what lands in the A-operand registers, contracted by the MFMA's K-slot convention with the ONE plane H1_WRITE_V parks
-    (read back by H1_LOAD_B), must be the plain contraction over the chunk's channels."""
+    quad; and what lands in the A-operand registers, contracted by the MFMA's K-slot convention with the ONE plane H2_WRITE_V parks
+    (read back by H2_LOAD_B), must be the plain contraction over the chunk's channels."""
     rng = np.random.default_rng(0)
     BCO, CoutP, nch = 32 * COT, Cout, CinP // 16
     U = rng.standard_normal((Cout, CinP, 16))
@@ -94,7 +94,7 @@ def test_one_piece_loop_reads_exactly_the_first_pieces(COT, Cout, Cin, CinP):
     assert (piece_of >= 0).all()
     hits = np.zeros(ndw, dtype=int)
     V = rng.standard_normal((16, 16, 32))                       # [channel in chunk][position][tile]
-    sV = np.zeros((16 * 2 * 4 * 32, 2))                         # H1_WRITE_V: words [position][half][pair][tile] = (lo, hi)
+    sV = np.zeros((16 * 2 * 4 * 32, 2))                         # H2_WRITE_V, NP = 1: words [position][half][pair][tile] = (lo, hi)
     for tid in range(512):
         rg, s_tile, s_cp = (tid >> 6) >> 2, tid & 31, (tid & 255) >> 5
         s_ca = 4 * (s_cp >> 1) + (s_cp & 1)
@@ -112,11 +112,11 @@ def test_one_piece_loop_reads_exactly_the_first_pieces(COT, Cout, Cin, CinP):
                         A, Bm = np.zeros((32, 2, 8)), np.zeros((32, 2, 8))
                         for lane in range(64):
                             half, l31 = lane >> 5, lane & 31
-                            q = i * COT + ct                                            # H1_LOAD_A / H1_MF1: quad of (position, sub-tile)
+                            q = i * COT + ct                                            # H2_LOAD_A / H2_MF1, NP = 1: quad of (position, sub-tile)
                             dw0 = (cotile * nch * 16 + 2 * wave) * (COT * 512) + chunk * (16 * COT * 512) + q * 512 + lane * 4
                             hits[dw0:dw0 + 4] += 1
                             A[l31, half] = [mem[(dw0 + j) * 2 + k] for j in range(4) for k in range(2)]
-                            qb = (((2 * wave + i) * 2 + half) * 4) * 32 + l31           # H1_LOAD_B
+                            qb = (((2 * wave + i) * 2 + half) * 4) * 32 + l31           # H2_LOAD_B, NP = 1
                             Bm[l31, half] = [sV[qb + jp * 32][k] for jp in range(4) for k in range(2)]
                         if chunk == nch - 1:
                             co0 = cotile * BCO + ct * 32

@@ -1,5 +1,5 @@
 """GPU: the 4-way K split of the two fp16 Winograd kernels -- shape ids 26 (wino2h_k4, two-piece operands, conv_wino2h.cpp) and 27
-(wino1h_k4, one-piece operands, conv_wino1h.cpp) -- forced through the stand-alone conv.
+(wino1h_k4, one-piece operands, the same file with NP = 1) -- forced through the stand-alone conv.
 
 blockIdx.y picks one of four parts of the 16-channel chunks, every part writes its raw partial result, launch_wino_ksplit_reduce sums
 them in a fixed order: the split only reorders the fp32 accumulation, so each id is held to what its 2-way form is held to --
@@ -18,7 +18,7 @@ from tests import f16x1_ref as R
 
 pytestmark = pytest.mark.gpu
 
-MINCH_K4 = 3                     # conv_wino1h.cpp / conv_wino2h.cpp: chunks per part, at least (tests/test_f16_ksplit4_cpu.py checks the source)
+MINCH_K4 = 3                     # conv_wino2h.cpp, both piece counts: chunks per part, at least (tests/test_f16_ksplit4_cpu.py checks the source)
 SHAPES = [
     # (B, C0, C1, Cout, H, chunks divide by 4)
     (2, 16 * 4 * MINCH_K4, 0, 32, 8, True),     # G8, the shortest admissible parts, COT 1

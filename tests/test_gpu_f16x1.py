@@ -1,4 +1,4 @@
-"""GPU: the one-piece fp16 Winograd arithmetic -- context option "f16x1", shape ids 24 / 25 (conv_wino1h.cpp).
+"""GPU: the one-piece fp16 Winograd arithmetic -- context option "f16x1", shape ids 24 / 25 (conv_wino2h.cpp with NP = 1).
 
 A DRAFT arithmetic: operands of 11 significant bits.  It is not held to the parity tolerances of tests/test_gpu_parity.py but to
   * per conv, the bound tests/f16x1_ref.py derives (worst case over the signs of the roundings), per element, against an fp64 convolution;

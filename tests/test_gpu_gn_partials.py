@@ -72,7 +72,7 @@ CASES += [_c(17, 1, 128, 0, 5, 32, pgrid=7), _c(20, 1, 256, 0, 5, 32, pgrid=7)] 
 # ---- K split: 8x8 with an odd batch and 16x16, each at the smallest Cin the id's usable() admits
 #   8 / 11 / 13 / 25: an even number of 16-channel chunks, at least 4                      -> 64
 #   18: chunks a multiple of 4, at least 8 -> 128;   19: a multiple of 8, at least 16       -> 256
-#   26 / 27: a multiple of 4 with H2_MINCH_K4 = H1_MINCH_K4 = 3 chunks per part            -> 192
+#   26 / 27: a multiple of 4 with H2_MINCH_K4 = 3 chunks per part (both piece counts)   -> 192
 for kid, cin in ((8, 64), (11, 64), (13, 64), (25, 64), (18, 128), (19, 256), (26, 192), (27, 192)):
     CASES += [_c(kid, 3, cin, 0, 40, 8), _c(kid, 2, cin, 0, 40, 16)]
 CASES += [_c(18, 2, 160, 96, 96, 16), _c(26, 2, 160, 96, 96, 16)]      # a concat, the seam (chunk 10 of 16) inside part 2

@@ -1,5 +1,5 @@
 """GPU: 3x3 convs with 1040 .. 2048 input channels on the K-split Winograd kernels (conv_wino3.cpp ids 11 / 18 / 19, conv_wino2h.cpp 13 / 26,
-conv_wino1h.cpp 25 / 27, conv_wino.cpp 8), whose GroupNorm coefficient table covers the channels of the workgroup's own K part.
+its one-piece form 25 / 27, conv_wino.cpp 8), whose GroupNorm coefficient table covers the channels of the workgroup's own K part.
 
 Every forced case goes through the stand-alone conv and must RUN the id it names (before the per-part table these launches fell through
 every fallback list to a direct tile kernel), with the prologues raw / affine / affine + SiLU over a per-(sample, channel) random table: a

@@ -147,6 +147,19 @@ def test_winograd_isa_checker_flags_violations():
     assert any("LDS-DMA" in p for p in c.check(head + spade_loop + others) if "ILi1ELi0ELb0" in p)   # ... and rejected elsewhere
 
 
+def test_profile_summaries_count_the_two_piece_launches_as_f16x2():
+    """tools/summarize_prof.py: conv_wino2h_kernel serves f16x2 (NP = 2) and f16x1 (NP = 1); the f16x2 family's traffic counts the
+    two-piece launches only, in new traces (five template arguments, NP first) and in the committed old ones (four, no NP)."""
+    from tools import summarize_prof as p
+    old = "void mcvd::conv_wino2h_kernel<1, 2, false, 0>(mcvd::ConvArgs)"          # profiles/r02_rocprofv3_summary_f16x2.txt: COT = 1, two pieces
+    new2 = "void mcvd::conv_wino2h_kernel<2, 3, 2, false, 0>(mcvd::ConvArgs)"
+    new1 = "void mcvd::conv_wino2h_kernel<1, 3, 2, false, 0>(mcvd::ConvArgs)"
+    assert [p.short(n) for n in (old, new2, new1)] == ["conv_wino2h_kernel<1, 2, false, 0>", "conv_wino2h_kernel<2, 3, 2, false, 0>",
+                                                       "conv_wino2h_kernel<1, 3, 2, false, 0>"]
+    assert [p.is_wino_f16x2(p.short(n)) for n in (old, new2, new1)] == [True, True, False]
+    assert not p.is_wino_f16x2("conv_wino3_kernel<3, 2, false, 0>") and not p.is_wino_f16x2("wino_ksplit_reduce_kernel")
+
+
 def test_no_kernel_of_the_library_holds_the_gfx950_coresidency_erratum_form():
     """tools/check_vop3p_dual_read.py (run by every build after the link): a packed-fp32 instruction that reads ONE VGPR pair as src1 and src2
     loses its low addend on gfx950 beside another kernel's 128-bit-operand MFMA (profiles/r06_coresident_cause.txt).  The scanner flags exactly

@@ -23,7 +23,7 @@ CK = T.CK
 
 
 def admitted(Cin, CinP, P):
-    """conv_wino3_usable's channel conditions (conv_wino2h / conv_wino1h: the same, 4 parts at most; conv_wino: 2 parts at most)."""
+    """conv_wino3_usable's channel conditions (conv_wino2h, either piece count: the same, 4 parts at most; conv_wino: 2 parts at most)."""
     nch = CinP // CK
     return (Cin <= (WINO_MAX_CIN_K4 if P >= 4 else T.WINO_MAX_CIN) and CinP % CK == 0 and CinP // max(P, 1) <= T.WINO_TABLE_CH
             and (P < 2 or (P in (2, 4, 8) and nch % P == 0 and nch >= 2 * P)))
@@ -86,7 +86,8 @@ def test_common_h_holds_both_constants_and_the_predicates_name_the_new_one():
         assert m, (f, fn)
         body = m.group(1)
         assert "WINO_MAX_CIN_K4" in body and re.search(r"WINO_MAX_CIN\b(?!_)", body) and "WINO_TABLE_CH" in body, f"{fn} does not name both bounds"
-    for f, fn in T.FAMILIES[:3]:          # the families with a 4-way split take the new bound from ksplit >= 4 on
+    assert [f for f, _ in T.FAMILIES[:2]] == ["conv_wino3.cpp", "conv_wino2h.cpp"]
+    for f, fn in T.FAMILIES[:2]:          # the families with a 4-way split (conv_wino2h.cpp: both piece counts) take the new bound from ksplit >= 4 on
         assert "a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN)" in T._src(os.path.join("kernels", f)), f
     # conv_wino.cpp splits two ways only: its bound stays WINO_MAX_CIN
     assert "a.Cin <= WINO_MAX_CIN &&" in T._src(os.path.join("kernels", "conv_wino.cpp"))

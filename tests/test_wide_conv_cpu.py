@@ -1,4 +1,4 @@
-"""CPU: the per-part GroupNorm coefficient table of the Winograd 3x3 kernels (conv_wino3.cpp, conv_wino2h.cpp, conv_wino1h.cpp; conv_wino.cpp
+"""CPU: the per-part GroupNorm coefficient table of the Winograd 3x3 kernels (conv_wino3.cpp, conv_wino2h.cpp with two pieces or one; conv_wino.cpp
 with one entry per thread) and the rule that admits a layer, restated here and walked over every layer shape up to 2048 channels.
 
 The kernels: `nch = CinP / 16` chunks; workgroup (.., blockIdx.y = kh) of a P-way K split contracts chunks [kh * nch / P, (kh + 1) * nch / P) and
@@ -24,7 +24,7 @@ WINO_MAX_CIN = 2048
 WINO_TABLE_CH = 1024
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcvd_pytorch_amd", "csrc")
-FAMILIES = (("conv_wino3.cpp", "conv_wino3_usable"), ("conv_wino2h.cpp", "conv_wino2h_usable"), ("conv_wino1h.cpp", "conv_wino1h_usable"),
+FAMILIES = (("conv_wino3.cpp", "conv_wino3_usable"), ("conv_wino2h.cpp", "conv_wino2h_usable"),       # the first two: the families with a 4-way split
             ("conv_wino.cpp", "conv_wino_usable"))
 
 
@@ -62,12 +62,12 @@ def lds_wino3(pc, g8):
     return (2 * vw + 2 * (CK * 10 * 24 + 8) + (4 if g8 else 2) * pc + (1 if g8 else 3) * NT) * 4
 
 
-def lds_wino2h(pc, g8):
+def lds_wino2h(pc, g8):          # wino2h_lds_bytes(2, pc, g8)
     vw = 2 * 16 * 2 * 4 * 32
     return (2 * vw + 2 * (CK * 10 * 24 + 4) + (4 if g8 else 2) * pc + 6 * NT) * 4
 
 
-def lds_wino1h(pc, g8):
+def lds_wino1h(pc, g8):          # wino2h_lds_bytes(1, pc, g8): the one-piece instantiations of conv_wino2h.cpp, one V plane
     vw = 16 * 2 * 4 * 32
     return (2 * vw + 2 * (CK * 10 * 24 + 4) + (4 if g8 else 2) * pc + 6 * NT) * 4
 
@@ -92,12 +92,17 @@ def test_the_constants_and_the_predicates_name_one_rule():
         assert "WINO_MAX_CIN" in body and "WINO_TABLE_CH" in body and "wino_part_channels(a.CinP" in body, f"{fn} does not name the rule"
         assert not re.search(r"a\.Cin <= 1024", src), f"{f}: a bare 1024"
         assert "lds_bytes(a.Cin" not in src, f"{f}: the LDS size still takes all Cin channels"
-    for f in ("conv_wino3.cpp", "conv_wino2h.cpp", "conv_wino1h.cpp"):        # the expressions restated above, as the kernels write them
+    for f in ("conv_wino3.cpp", "conv_wino2h.cpp"):        # the expressions restated above, as the kernels write them
         src = _src(os.path.join("kernels", f))
         assert "min(CK * c_begin + tid + k * NT, Cin - 1)" in src, f
         assert re.search(r"min\(\(\(ch\) - c_begin\) \* CK \+ \(int\)\(\(p_pk\[sl\] >> 12\) & \(CK - 1\)\), PC - 1\) \+ "
                          r"\(G8 \? \(int\)\(\(p_pk\[sl\] >> 20\) & 1u\) \* PC : 0\)", src), f
         assert "const int PC = (nch_all / ksp) * CK;" in src and "if (tid + k * NT < PC)" in src, f
+    # the fp16 kernel serves two piece counts: its V-plane word count, and with it the LDS request (lds_wino2h / lds_wino1h above), carries NP
+    src = _src(os.path.join("kernels", "conv_wino2h.cpp"))
+    assert "constexpr int h2_vw(int np) { return np * 16 * 2 * 4 * H2_T; }" in src and "VW = h2_vw(NP);" in src
+    assert "return (size_t)(2 * h2_vw(np) + 2 * (H2_CK * 10 * H2_PP + 4) + (g8 ? 4 : 2) * pc + 6 * H2_NT) * sizeof(float);" in src
+    assert "const size_t lds = wino2h_lds_bytes(NP, wino_part_channels(a.CinP, a.ksplit), G8);" in src
     src = _src(os.path.join("kernels", "conv_wino.cpp"))
     assert "min(CK * c_begin + tid, Cin - 1)" in src and "const int PC = (nch_all / ksp) * CK;" in src
     assert "min(((ch) - c_begin) * CK + (p_ci[sl] & (CK - 1)), PC - 1) + (G8 ? p_img[sl] * PC : 0)" in src

@@ -11,8 +11,8 @@ the destination registers of those loads are pending.  That is only sound if, in
 This script compiles the file to gfx950 assembly and verifies 1-3 for every instantiation of conv_wino_kernel.
 
 conv_wino2h.cpp (two fp16 pieces per operand, pre-split weights) and conv_wino3.cpp (three bf16 pieces, pre-split weights) count
-their VMEM the same way (conv_wino1h.cpp, one fp16 piece read out of conv_wino2h.cpp's weight image, likewise: 2*COT weight loads and
-2*COT MFMAs per K loop): their K loops (two per kernel, one per phase order) must hold exactly 4*COT (6*COT) weight loads + 6 patch
+their VMEM the same way (conv_wino2h.cpp's NP = 1 instantiations, one fp16 piece read out of the same weight image, likewise: 2*COT weight
+loads and 2*COT MFMAs per K loop): their K loops (two per kernel, one per phase order) must hold exactly 4*COT (6*COT) weight loads + 6 patch
 loads, no scratch traffic, and keep the load destinations untouched up to a vmcnt wait that covers them.  Their MFMAs are inline
 asm that read their A operand straight out of the load destinations, so in addition nothing but MFMAs may touch an accumulator
 register inside a K loop (the compiler does not know they are MFMA results and would not insert the wait states).
@@ -28,7 +28,6 @@ SRC = os.path.join(ROOT, "mcvd_pytorch_amd", "csrc", "kernels", "conv_wino.cpp")
 SRC3 = os.path.join(ROOT, "mcvd_pytorch_amd", "csrc", "kernels", "conv_wino3.cpp")
 SRC2H = os.path.join(ROOT, "mcvd_pytorch_amd", "csrc", "kernels", "conv_wino2h.cpp")
 SRC3P = os.path.join(ROOT, "mcvd_pytorch_amd", "csrc", "kernels", "conv_wino3p.cpp")
-SRC1H = os.path.join(ROOT, "mcvd_pytorch_amd", "csrc", "kernels", "conv_wino1h.cpp")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 DIAG = "--diag" in sys.argv[1:]          # check the diagnostics library's code (-DMCVD_DIAG)
 
@@ -155,7 +154,7 @@ def _inner_loop_spans(raw):
 
 def check3(asm_text, kernel="17conv_wino3_kernel", asm_mfma=True, expect=18, wl_per_cot=6, nloops=2, npatch=(3, 1), wreg0=184, named0=172,
            targs=r"ILi(\d)ELi(\d)E(?:Lb([01])E)?Li0EEE", nested=False, mfma_per_cot=None, wreg_end=256):
-    """conv_wino3_kernel<COT, PRO, G8, 0> / conv_wino2h_kernel<COT, PRO, G8, 0>: every loop that holds MFMAs is a K loop; a K loop
+    """conv_wino3_kernel<COT, PRO, G8, 0> / conv_wino2h_kernel<NP, COT, PRO, G8, 0>: every loop that holds MFMAs is a K loop; a K loop
     holds wl_per_cot * COT weight loads (NP pieces x 2 positions; destinations from register `wreg0` up) + npatch[G8] patch loads
     (destinations below `wreg0`).  mfma_per_cot: the K loop holds exactly that many MFMAs per cout sub-tile; wreg_end: the weight loads'
     destinations end below it."""
@@ -299,19 +298,23 @@ def check3p(asm_text):
 
 
 def check2h(asm_text):
-    return check3(asm_text, kernel="18conv_wino2h_kernel", asm_mfma=True, expect=18, wl_per_cot=4, nloops=2, npatch=(6, 6), wreg0=208, named0=202)      # x {8x16 regions, 8x8 images}; one loop per phase order
+    """conv_wino2h_kernel<NP = 2, COT, PRO, G8, 0>: 18 instantiations (x {8x16 regions, 8x8 images}), one K loop per phase order; per chunk
+    2 positions x 2 pieces x COT weight quads and 2 x 3 MFMAs (the three piece products) per cout sub-tile."""
+    return check3(asm_text, kernel="18conv_wino2h_kernel", asm_mfma=True, expect=18, wl_per_cot=4, nloops=2, npatch=(6, 6), wreg0=208, named0=202,
+                  targs=r"ILi2ELi(\d)ELi(\d)ELb([01])ELi0EEE", mfma_per_cot=6)
 
 
 def check1h(asm_text):
-    """conv_wino1h_kernel<COT, PRO, G8>: one piece -- 2 positions x COT weight quads (v208-v231) and as many MFMAs per chunk."""
-    return check3(asm_text, kernel="18conv_wino1h_kernel", asm_mfma=True, expect=18, wl_per_cot=2, nloops=2, npatch=(6, 6), wreg0=208, named0=202,
-                  targs=r"ILi(\d)ELi(\d)ELb([01])EEE", mfma_per_cot=2, wreg_end=232)
+    """conv_wino2h_kernel<NP = 1, COT, PRO, G8, 0>, out of the same assembly: one piece -- 2 positions x COT weight quads (v208-v231) and as
+    many MFMAs per chunk."""
+    return check3(asm_text, kernel="18conv_wino2h_kernel", asm_mfma=True, expect=18, wl_per_cot=2, nloops=2, npatch=(6, 6), wreg0=208, named0=202,
+                  targs=r"ILi1ELi(\d)ELi(\d)ELb([01])ELi0EEE", mfma_per_cot=2, wreg_end=232)
 
 
 def main():
     problems = []
     with tempfile.TemporaryDirectory() as td:
-        for src, fn in ((SRC, check), (SRC3, check3), (SRC2H, check2h), (SRC3P, check3p), (SRC1H, check1h)):
+        for src, fn in ((SRC, check), (SRC3, check3), (SRC2H, lambda t: check2h(t) + check1h(t)), (SRC3P, check3p)):
             out = os.path.join(td, os.path.basename(src)[:-4] + ".s")
             cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-S", "--cuda-device-only",
                    src, "-o", out] + (["-DMCVD_DIAG"] if DIAG else [])

@@ -4,7 +4,7 @@
 
 BASELINE config 2 (smmnist_big5_ngf96), B = 2, through the CPU oracle (oracle/unet_ref.py, oracle/sampler_ref.py) with the synthetic
 weights, inputs and injected noise of tests/golden/smmnist_big5_ngf96_b2.pt, every 3x3 conv with Cin >= 32 -- the GroupNorm-ed ones, the
-convs the option may move -- replaced by tests/f16x1_ref.py's restatement of conv_wino1h.cpp (operands rounded where the kernel rounds
+convs the option may move -- replaced by tests/f16x1_ref.py's restatement of conv_wino2h.cpp's one-piece form (operands rounded where the kernel rounds
 them, products accumulated in fp64).  Stored:
     config_name, batch, convs_per_forward
     result                         the emulated final frames of DDPM-100 + denoise                       [B, C, H, W] fp32

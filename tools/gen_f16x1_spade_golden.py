@@ -5,7 +5,7 @@
 BASELINE config 4 (bair_big_spade), B = 2, through the CPU oracle (oracle/unet_ref.py, oracle/sampler_ref.py) with the synthetic weights,
 inputs and injected noise of tests/golden/bair_big_spade_b2_fwd.pt / _ddpm100.pt.  The convs the option may move -- the 3x3 convs with a
 SPADE norm directly in front: Conv_0 of a ResBlock that does not resample (behind a FIR the conv reads a raw tensor and stays exact),
-Conv_1 of every ResBlock, the last conv -- are replaced by tests/f16x1_ref.py's restatement of conv_wino1h.cpp (operands rounded where
+Conv_1 of every ResBlock, the last conv -- are replaced by tests/f16x1_ref.py's restatement of conv_wino2h.cpp's one-piece form (operands rounded where
 the kernel rounds them, products accumulated in fp64).  They are selected by the KEY of their weight, not by its shape: MySPADE's
 mlp_gamma / mlp_beta are 3x3 convs over spade_dim = 128 channels too, read a ReLU-ed tensor no norm bounds, and stay exact -- as do
 mlp_shared, the stem and the shortcuts.  Stored:

@@ -22,6 +22,18 @@ def short(name):
     return name[:70]
 
 
+def is_wino_f16x2(k):
+    """short(name) is a launch of the f16x2 family: a TWO-piece instantiation of conv_wino2h_kernel.  The kernel serves both fp16 arithmetics
+    since the one-piece kernel was folded into it -- conv_wino2h_kernel<NP, COT, PRO, G8, EXP>, five template arguments, the pieces first:
+    NP = 2 is f16x2, NP = 1 is f16x1 and counts for another family.  Older traces (profiles/) name four arguments, <COT, PRO, G8, EXP>: the
+    two-piece kernel, whatever the first one says (<1, 2, false, 0> is its 32-cout tile)."""
+    m = re.match(r"conv_wino2h_kernel<([^>]*)>", k)
+    if not m:
+        return False
+    args = [a.strip() for a in m.group(1).split(",")]
+    return len(args) == 4 or (len(args) == 5 and args[0] == "2")
+
+
 def stats():
     for f in glob.glob(os.path.join(OUT, "prof", "**", "*kernel_stats.csv"), recursive=True):
         rows = list(csv.DictReader(open(f)))
@@ -133,7 +145,7 @@ def family_traffic(fetch_dir, write_dir, dom_kernel_name):
     directories): (2 x FETCH + WRITE) / launches -- `bench.py --pmc-traffic` measures `roofline.traffic` with this in the run it
     describes.  The x2 on FETCH_SIZE is the gfx950 correction of MI355X_MICROARCH.md (HBM section)."""
     if dom_kernel_name.startswith("conv_wino2h_kernel"):
-        fam = lambda k: k.startswith("conv_wino2h_kernel")
+        fam = is_wino_f16x2
     elif dom_kernel_name.startswith("conv_wino3_kernel"):
         fam = lambda k: k.startswith("conv_wino3_kernel") or k.startswith("conv_wino3p_kernel")
     else:
@@ -166,9 +178,9 @@ def traffic(out_json):
     except Exception:
         pass
     if dom.startswith("conv_wino2h_kernel"):
-        res = {"family": "wino_f16x2", "kernel_family": "conv_wino2h_kernel<*> (the reduce passes of its 3 K-split ops per forward share a kernel "
+        res = {"family": "wino_f16x2", "kernel_family": "conv_wino2h_kernel<*>, two-piece instantiations (the reduce passes of its 3 K-split ops per forward share a kernel "
                "with the fp32 Winograd K-split ops and are left out: 3 x 8 us of 41 ops)", "per_instantiation": {}}
-        fam = lambda k: k.startswith("conv_wino2h_kernel")
+        fam = is_wino_f16x2
     elif dom.startswith("conv_wino3_kernel"):
         res = {"family": "wino_bf16x3", "kernel_family": "conv_wino3_kernel<*> + conv_wino3p_kernel<*> (the same kernel as persistent workgroups)", "per_instantiation": {}}
         fam = lambda k: k.startswith("conv_wino3_kernel") or k.startswith("conv_wino3p_kernel")
