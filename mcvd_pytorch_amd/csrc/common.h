@@ -150,15 +150,22 @@ int launch_im2col3x3(const float* x0, int C0, const float* x1, int C1, float* co
 int launch_taps_shift_add(const float* z, const float* bias, const float* res, float scale, float* y, int B, int Cout, int H, int W, hipStream_t s);
 int launch_pack_conv_gemm_form(const float* w, float* wp, int Cout, int Cin, int form, int CoutP, hipStream_t s);
 // Input channels of the Winograd kernels.  A workgroup parks the GroupNorm (A, B) coefficients of the channels ITS chunks contract --
-// all of them without a K split, one part's with ConvArgs::ksplit -- in an LDS table of at most WINO_TABLE_CH entries per sample (two per
-// thread of the 512-thread kernels, one per thread of conv_wino.cpp's 1024), so
-//     Cin <= WINO_MAX_CIN (ksplit >= 4: WINO_MAX_CIN_K4)   and   CinP / max(ksplit, 1) <= WINO_TABLE_CH:
-// layers of 1040 .. 2048 channels are served by the K-split ids only.  A split of four or more parts takes WINO_MAX_CIN_K4 channels
-// (144 chunks: 576 per part at 4 parts, 288 at 8); the 2-way and unsplit launches stop at WINO_MAX_CIN by the table rule alone.
+// all of them without a K split, one part's with ConvArgs::ksplit -- in an LDS table.  A workgroup of 8 x 16-pixel regions (every plane but
+// 8 x 8) serves ONE sample and parks up to WINO_TABLE_CH_PLANE entries (four per thread of the 512-thread kernels, two per thread of
+// conv_wino.cpp's 1024); an 8 x 8 launch (G8) serves TWO samples per workgroup and parks up to WINO_TABLE_CH entries for each (two per
+// thread and sample, one in conv_wino.cpp): four entries for two samples do not fit the LDS.  So
+//     Cin <= WINO_MAX_CIN (ksplit >= 4: WINO_MAX_CIN_K4)   and   CinP / max(ksplit, 1) <= wino_table_ch(8 x 8 ?):
+// on planes of 16 x 16 and larger the unsplit ids take every layer up to WINO_MAX_CIN channels; at 8 x 8 layers of 1040 .. 2048 channels
+// are served by the K-split ids only.  A split of four or more parts takes WINO_MAX_CIN_K4 channels (144 chunks: 576 per part at 4 parts,
+// 288 at 8); the 2-way and unsplit launches stop at WINO_MAX_CIN (the 2-way split by this constant alone on a plane, where a part of 1152
+// channels would fit the table: its part buffers and the tuner's candidate rules are sized for WINO_MAX_CIN).
 constexpr int WINO_MAX_CIN = 2048;
 constexpr int WINO_MAX_CIN_K4 = 2304;          // a split of four or more parts takes this many
 inline int wino_max_cin(int ksplit) { return ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN; }
-constexpr int WINO_TABLE_CH = 1024;
+constexpr int WINO_TABLE_CH = 1024;            // table entries per sample, 8 x 8 launches (two samples per workgroup); the persistent kernel; the SPADE-fused loader
+constexpr int WINO_TABLE_CH_PLANE = 2048;      // ... launches of 8 x 16-pixel regions (one sample per workgroup)
+inline int wino_table_ch(bool g8) { return g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE; }
+static_assert(WINO_TABLE_CH_PLANE == 2 * WINO_TABLE_CH && WINO_MAX_CIN <= WINO_TABLE_CH_PLANE, "an unsplit plane launch parks every channel up to WINO_MAX_CIN");
 inline int wino_part_channels(int CinP, int ksplit) { return CinP / (ksplit >= 2 ? ksplit : 1); }      // PC: the table's entries per sample
 // Winograd F(2x2,3x3) kernel (conv_wino.cpp): tile shape id 4 of the dispatcher
 bool conv_wino_supported(int ks, int H, int W);      // geometry only (decides whether transformed weights are packed at all)

@@ -3,15 +3,17 @@
 // profiles/, mcvd_last_conv_kernel / mcvd_model_op_kernel): a new variant gets a new number and one line here; numbers are never reused.
 // Plain C++17, no HIP: the static_asserts at the end check the table in every build.
 //
-// Input channels of the Winograd families (common.h: WINO_MAX_CIN = 2048, WINO_TABLE_CH = 1024): a workgroup's GroupNorm coefficient table covers
-// the channels of its own K part, so a launch needs  Cin <= WINO_MAX_CIN  and  CinP / max(kparts, 1) <= WINO_TABLE_CH.  The unsplit ids
-// (4, 10, 12, 24, 16) stop at 1024 channels; layers of 1040 .. 2048 are served by the K-split ids 8 / 11 / 18 / 19 / 13 / 26 / 25 / 27 where the
+// Input channels of the Winograd families (common.h: WINO_MAX_CIN = 2048, WINO_TABLE_CH = 1024, WINO_TABLE_CH_PLANE = 2048): a workgroup's GroupNorm
+// coefficient table covers the channels of its own K part, so a launch needs  Cin <= WINO_MAX_CIN  and  CinP / max(kparts, 1) <= WINO_TABLE_CH at
+// 8 x 8 (two samples per workgroup), <= WINO_TABLE_CH_PLANE on every other plane (one sample per workgroup, twice the entries per thread).  On planes
+// of 16 x 16 and larger the unsplit ids 4 / 10 / 12 / 24 take every layer up to 2048 channels -- no K-split scratch, so also the 32 x 32 layers of a model
+// above 1024 channels; at 8 x 8 they stop at 1024 and layers of 1040 .. 2048 are served by the K-split ids 8 / 11 / 18 / 19 / 13 / 26 / 25 / 27 where the
 // split's own conditions hold.  The persistent kernel (CF_WINO3P: 16 / 17 / 20) was NOT widened: it keeps one table of all Cin channels per run of
 // items, and a per-part table would have to be reloaded inside its item boundary; its fallback lists (17 -> 11, 20 -> 17 -> 16 -> 11) route round it.
 // The SPADE-fused loader of CF_WINO (ConvArgs::gb) stays at 1024 as well.
 // A split of four or more parts takes WINO_MAX_CIN_K4 = 2304 channels: layers of 2049 .. 2304 (the 2304-channel concats of the ngf-288 UCF-101 nets)
-// are served by ids 18 / 19 (bf16x3), 26 (f16x2) and 27 (f16x1) only.  The 2-way ids 8 / 11 / 13 / 25 refuse them by the table rule (1152 channels per
-// part), and CF_WINO has no 4-way split: with bf16x3 off such a layer runs the direct tile kernel.
+// are served by ids 18 / 19 (bf16x3), 26 (f16x2) and 27 (f16x1) only.  The 2-way ids 8 / 11 / 13 / 25 refuse them (Cin <= WINO_MAX_CIN; at 8 x 8 also by the
+// table rule, 1152 channels per part), and CF_WINO has no 4-way split: with bf16x3 off such a layer runs the direct tile kernel.
 #pragma once
 #include <initializer_list>
 

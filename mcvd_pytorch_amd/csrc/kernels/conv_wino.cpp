@@ -83,7 +83,7 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(ConvArgs a) {
     float* sV = smem;                           // [2][VSZ]
     float* sP = smem + 2 * VSZ;                 // [2][PBUF]
     // ---- chunk range of this workgroup (a.ksplit == 2: blockIdx.y picks one half of the input channels).  The coefficient tables cover the
-    // PC channels of this range only (PC <= WINO_TABLE_CH: one entry per thread and sample), indexed relative to 16 c_begin.
+    // PC channels of this range only (G8: PC <= WINO_TABLE_CH, one entry per thread and sample; else PC <= WINO_TABLE_CH_PLANE, two per thread), indexed relative to 16 c_begin.
     const int nch_all = a.CinP / CK;
     const int ksp = a.ksplit == 2 ? 2 : 1, kh = ksp == 2 ? (int)blockIdx.y : 0;
     const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
@@ -291,7 +291,14 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(ConvArgs a) {
         // table entry tid = channel 16 c_begin + tid; the clamp to Cin - 1 covers the padded last chunk of the last part (zeroed at the write)
         const int csrc = min(CK * c_begin + tid, Cin - 1);
         if (PRO && a.coef && tid < PC) cfl = *reinterpret_cast<const f32x2*>(a.coef + ((long)b * Cin + csrc) * 2);
+        // regions of a plane, a table of more than 1024 channels (PC <= WINO_TABLE_CH_PLANE; `wide` is uniform over the workgroup, and never
+        // set with the SPADE tables of PRO 3): the thread's second entry, tid + NT, requested before the first is parked.  Narrower launches
+        // issue the one load they always did.
+        const bool wide = PRO && PRO != 3 && !G8 && PC > NT;
+        f32x2 cfw = {1.0f, 0.0f};
+        if (wide && a.coef && tid + NT < PC) cfw = *reinterpret_cast<const f32x2*>(a.coef + ((long)b * Cin + min(CK * c_begin + tid + NT, Cin - 1)) * 2);
         if (PRO && tid < PC) *reinterpret_cast<f32x2*>(sCo + tid * 2) = cfl;
+        if (wide && tid + NT < PC) *reinterpret_cast<f32x2*>(sCo + (tid + NT) * 2) = cfw;
         if (PRO == 3 && tid < PC) {            // (s1, b2): the temb pair, (1, 0) where the norm has none (final SPADE norm)
             f32x2 c2 = {1.0f, 0.0f};
             if (a.coef2) c2 = *reinterpret_cast<const f32x2*>(a.coef2 + ((long)b * Cin + csrc) * 2);
@@ -611,13 +618,16 @@ __global__ __launch_bounds__(256) void wino_ksplit_reduce_stats_kernel(const flo
 }
 
 // pc: the channels of one part (wino_part_channels): the coefficient tables' entries per sample
-static size_t wino_lds_bytes(int pc, bool g8, bool spade = false) {
+static constexpr size_t wino_lds_bytes(int pc, bool g8, bool spade = false) {
     const int maxp = g8 ? 2 : 3;               // MAXP of the kernel
     const size_t k = (size_t)(2 * WR_CK * 16 * WR_T + 2 * (WR_CK * 10 * WR_PP + 4) + (g8 ? 4 : 2) * pc * (spade ? 2 : 1) +
                               (spade ? 2 * maxp * WR_NT : 0)) * sizeof(float);
     const size_t epi = (size_t)16 * 32 * WR_T * sizeof(float);        // sM of the epilogue
     return k > epi ? k : epi;
 }
+static_assert(WR_PP != 24 || wino_lds_bytes(WINO_TABLE_CH_PLANE, false) == 112672, "a plane's table of WINO_TABLE_CH_PLANE channels");
+static_assert(wino_lds_bytes(WINO_TABLE_CH_PLANE, false) <= 160 * 1024 && wino_lds_bytes(WINO_TABLE_CH, true, true) <= 160 * 1024,
+              "the widest coefficient tables fit the LDS: a plane's, and the SPADE loader's two tables for two 8 x 8 samples");
 
 #ifdef MCVD_DIAG
 template <int EXP>
@@ -756,8 +766,9 @@ int conv_wino_cout_tile(int Cout) {
 bool conv_wino_usable(const ConvArgs& a) {
     // (this kernel splits two ways only: WINO_MAX_CIN_K4, the bound of the splits of four or more parts, never applies to it)
     const int pc = wino_part_channels(a.CinP, a.ksplit == 2 ? 2 : 1);
-    static_assert(WINO_MAX_CIN_K4 > 2 * WINO_TABLE_CH && WINO_MAX_CIN <= 2 * WINO_TABLE_CH, "above WINO_MAX_CIN a 2-way part overflows the table");
-    return conv_wino_supported(a.ks, a.H, a.W) && a.wpw && a.Cin <= WINO_MAX_CIN && pc <= WINO_TABLE_CH && a.CinP % WR_CK == 0 &&
+    static_assert(WINO_MAX_CIN_K4 > 2 * WINO_TABLE_CH && WINO_MAX_CIN <= 2 * WINO_TABLE_CH, "above WINO_MAX_CIN a 2-way part overflows the 8 x 8 table");
+    const bool g8 = a.H == 8 && a.W == 8;
+    return conv_wino_supported(a.ks, a.H, a.W) && a.wpw && a.Cin <= WINO_MAX_CIN && pc <= (g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE) && a.CinP % WR_CK == 0 &&
            (a.gb == nullptr || a.Cin <= WINO_TABLE_CH) &&                            // the SPADE-fused loader (PRO 3) stays where it was
 
            (a.C1 == 0 || a.C0 % WR_CK == 0) &&                                       // a chunk never straddles the concat seam
@@ -769,7 +780,7 @@ bool conv_wino_usable(const ConvArgs& a) {
 // a.wpw must hold the operand-major layout (launch_pack_wino_weight) packed for conv_wino_cout_tile(Cout).
 int launch_conv_wino(const ConvArgs& a, hipStream_t s) {
     MCVD_REQUIRE(conv_wino_usable(a), "winograd conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weights %s; Cin <= %d, %d channels per K part)", a.ks,
-                 a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpw ? "present" : "missing", WINO_MAX_CIN, WINO_TABLE_CH);
+                 a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpw ? "present" : "missing", WINO_MAX_CIN, wino_table_ch(a.H == 8 && a.W == 8));
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {

@@ -151,7 +151,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
     const int H = a.H, W = a.W, HW = H * W, Cin = a.Cin;
     // ---- chunk range of this workgroup (a.ksplit == 2 / 4: blockIdx.y picks one part of the input channels).  The coefficient table
-    // covers the PC channels of this range only (PC <= WINO_TABLE_CH: two entries per thread and sample), indexed relative to 16 c_begin.
+    // covers the PC channels of this range only (G8: PC <= WINO_TABLE_CH, two entries per thread and sample; else PC <= WINO_TABLE_CH_PLANE, four per thread), indexed relative to 16 c_begin.
     const int nch_all = a.CinP / CK;
     const int ksp = a.ksplit >= 2 ? a.ksplit : 1, kh = ksp >= 2 ? (int)blockIdx.y : 0;          // 2 or 4 parts of the input channels
     const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
@@ -171,15 +171,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
     const int co0 = cotile * BCO;
     const int rg = __builtin_amdgcn_readfirstlane(wave >> 2);   // rows 2rg, 2rg+1 of B^T d; phase order of the wave
 
-    // prologue coefficients of this sample: (A_c, B_c) of channel 16 c_begin + tid + k * 512 (PC <= 1024: at most two table entries per thread and
-    // sample; the clamp to Cin - 1 covers the padded last chunk of the last part).  Regions of a plane: asm loads into v202-v205 (the registers of the third patch) IN FRONT of the first patches, parked in
-    // the LDS table once they have landed (conv_wino3.cpp).  G8 (two samples, eight values: more than the six patch registers): ordinary
-    // loads, waited for before the first patch request.
-    f32x2 cpre[2] = {{1.0f, 0.0f}, {1.0f, 0.0f}};
+    // prologue coefficients of this sample: (A_c, B_c) of channel 16 c_begin + tid + k * 512 (the clamp to Cin - 1 covers the padded last
+    // chunk of the last part).  Regions of a plane (PC <= WINO_TABLE_CH_PLANE: up to four table entries per thread): asm loads into v202-v205
+    // (the registers of the third patch) IN FRONT of the first patches, parked in the LDS table once they have landed (conv_wino3.cpp);
+    // entries 2 and 3, which only a table of more than 1024 channels has (`wide`, uniform over the workgroup), into v220-v223: weight quad 3,
+    // which nothing requests before the coefficients have been read back.  G8 (PC <= WINO_TABLE_CH, two entries for each of two samples,
+    // eight values: more than the six patch registers): ordinary loads, waited for before the first patch request.
+    constexpr int NE = G8 ? 2 : 4;                               // table entries per thread and sample
+    const bool wide = !G8 && PC > 2 * NT;
+    f32x2 cpre[4] = {{1.0f, 0.0f}, {1.0f, 0.0f}, {1.0f, 0.0f}, {1.0f, 0.0f}};
     f32x2 cpre2[2] = {{1.0f, 0.0f}, {1.0f, 0.0f}};              // G8: the region's second sample (clamped to the last one)
-    const float* co_src[2];
+    const float* co_src[NE];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) co_src[k] = a.coef + ((long)b * Cin + min(CK * c_begin + tid + k * NT, Cin - 1)) * 2;
+    for (int k = 0; k < NE; ++k) co_src[k] = a.coef + ((long)b * Cin + min(CK * c_begin + tid + k * NT, Cin - 1)) * 2;
     if (PRO && G8) {                                            // unconditional (clamped) loads: the wait belongs at the use
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
@@ -451,9 +455,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
             for (int i = tid; i < 2 * PBUF; i += NT) sP[i] = 0.0f;
         unsigned ofs[MAXP];
         H2_READ_OFF(ofs)
-        if (PRO && !G8)
+        if (PRO && !G8) {
             asm volatile("global_load_dwordx2 v[202:203], %0, off\n\tglobal_load_dwordx2 v[204:205], %1, off"
                          :: "v"(co_src[0]), "v"(co_src[1]) : "memory");
+            if (wide)
+                asm volatile("global_load_dwordx2 v[220:221], %0, off\n\tglobal_load_dwordx2 v[222:223], %1, off"
+                             :: "v"(co_src[NE - 2]), "v"(co_src[NE - 1]) : "memory");
+        }
         H2_LOAD_PR(c_begin, nodep, ofs, "v208", "v209", "v210", "v211", "v212", "v213")
         H2_LOAD_PR(c_begin + 1, nodep, ofs, "v214", "v215", "v216", "v217", "v218", "v219")
         if (rec) sp[0] = __builtin_amdgcn_s_memtime() - tk0;      // loads issued
@@ -463,11 +471,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         if (PRO && !G8) {
             asm volatile("v_mov_b32 %0, v202\n\tv_mov_b32 %1, v203\n\tv_mov_b32 %2, v204\n\tv_mov_b32 %3, v205"
                          : "=v"(cpre[0].x), "=v"(cpre[0].y), "=v"(cpre[1].x), "=v"(cpre[1].y) : "s"(vtok));
+            if (wide)
+                asm volatile("v_mov_b32 %0, v220\n\tv_mov_b32 %1, v221\n\tv_mov_b32 %2, v222\n\tv_mov_b32 %3, v223"
+                             : "=v"(cpre[2].x), "=v"(cpre[2].y), "=v"(cpre[3].x), "=v"(cpre[3].y) : "s"(vtok));
 #pragma unroll
-            for (int k = 0; k < 2; ++k)
+            for (int k = 0; k < NE; ++k)               // (k >= 2: never below PC unless `wide`)
                 if (tid + k * NT < PC) *reinterpret_cast<f32x2*>(sCo + (tid + k * NT) * 2) = cpre[k];
             cdep[0] = cdep[1] = cpre[0].x + cpre[0].y;
             cdep[2] = cdep[3] = cpre[1].x + cpre[1].y;
+            cdep[4] = cpre[2].x + cpre[2].y;           // (behind the reads of v220-v223 as well: the hooks below request weight quad 3)
+            cdep[5] = cpre[3].x + cpre[3].y;
         }
         H2_LOAD_P(c_begin + 2, cdep, ofs)  // (behind the reads of v202-v205)
         if (PRO || G8) __syncthreads();    // coefficient table (and the zeroed halo) visible
@@ -690,9 +703,13 @@ static constexpr size_t wino2h_lds_bytes(int np, int pc, bool g8) {
     return (size_t)(2 * h2_vw(np) + 2 * (H2_CK * 10 * H2_PP + 4) + (g8 ? 4 : 2) * pc + 6 * H2_NT) * sizeof(float);
 }
 // conv_wino2h_usable() serves both piece counts with the two-piece size in its LDS bound: the size grows with np, pc and g8, usable() holds pc
-// to WINO_TABLE_CH, and the largest request fits -- the bound never decides, for either count
+// to WINO_TABLE_CH (8 x 8) or WINO_TABLE_CH_PLANE (regions of a plane, half the entries per channel), and the largest request fits -- the bound never decides, for either count
 static_assert(wino2h_lds_bytes(2, WINO_TABLE_CH, true) == 124960 && wino2h_lds_bytes(2, WINO_TABLE_CH, true) <= 160 * 1024,
               "two pieces, a full coefficient table for two samples: the most LDS a usable launch asks for");
+// regions of a plane park one sample's table of up to WINO_TABLE_CH_PLANE = 2 * WINO_TABLE_CH channels: the same words.  One piece with that
+// table asks for more than half a CU's LDS -- one workgroup per CU where the narrower launches run two; the tuner times it
+static_assert(wino2h_lds_bytes(2, WINO_TABLE_CH_PLANE, false) == 124960 && wino2h_lds_bytes(1, WINO_TABLE_CH_PLANE, false) == 92192,
+              "a plane's table of WINO_TABLE_CH_PLANE channels, two pieces and one");
 
 // the K-split second pass lives in conv_wino.cpp
 int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s);
@@ -774,7 +791,7 @@ static int wino2h_launch(const ConvArgs& a, hipStream_t s) {
 bool conv_wino2h_usable(const ConvArgs& a) {
     const bool g8 = a.H == 8 && a.W == 8;
     const int nch = a.CinP / H2_CK;
-    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) && wino_part_channels(a.CinP, a.ksplit) <= WINO_TABLE_CH &&
+    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) && wino_part_channels(a.CinP, a.ksplit) <= (g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE) &&
            a.CinP % H2_CK == 0 && (a.C1 == 0 || a.C0 % H2_CK == 0) && a.H * a.W <= 16384 &&
            (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino2h_lds_bytes(2, wino_part_channels(a.CinP, a.ksplit), g8) <= 160 * 1024 &&
            (a.ksplit < 2 || ((a.ksplit == 2 || (a.ksplit == 4 && nch / 4 >= H2_MINCH_K4)) && nch % a.ksplit == 0 && nch >= 2 * a.ksplit &&
@@ -784,7 +801,7 @@ bool conv_wino2h_usable(const ConvArgs& a) {
 template <int NP>
 static int wino2h_launch_np(const ConvArgs& a, hipStream_t s) {
     MCVD_REQUIRE(conv_wino2h_usable(a), "winograd f16x%d conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d, %d channels per K part)",
-                 NP, a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wph ? "present" : "missing", wino_max_cin(a.ksplit), WINO_TABLE_CH);
+                 NP, a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wph ? "present" : "missing", wino_max_cin(a.ksplit), wino_table_ch(a.H == 8 && a.W == 8));
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd f16x%d conv: CoutP=%d vs tile %d", NP, a.CoutP, 32 * cot);
     switch (cot) {

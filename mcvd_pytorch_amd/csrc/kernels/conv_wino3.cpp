@@ -126,7 +126,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, half = lane >> 5;
     const int H = a.H, W = a.W, HW = H * W, Cin = a.Cin;
     // ---- chunk range of this workgroup (a.ksplit == 2 / 4 / 8: blockIdx.y picks one part of the input channels).  The coefficient table
-    // covers the PC channels of this range only (PC <= WINO_TABLE_CH: two entries per thread and sample), indexed relative to 16 c_begin.
+    // covers the PC channels of this range only (G8: PC <= WINO_TABLE_CH, two entries per thread and sample; else PC <= WINO_TABLE_CH_PLANE, four per thread), indexed relative to 16 c_begin.
     const int nch_all = a.CinP / CK;
     const int ksp = a.ksplit >= 2 ? a.ksplit : 1, kh = ksp >= 2 ? (int)blockIdx.y : 0;          // 2, 4 or 8 parts of the input channels
     const int c_begin = kh * (nch_all / ksp), c_end = c_begin + nch_all / ksp;
@@ -146,12 +146,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     const int co0 = cotile * BCO;
     const int rg = __builtin_amdgcn_readfirstlane(wave >> 2);   // rows 2rg, 2rg+1 of B^T d; phase order of the wave
 
-    // prologue coefficients of this sample: (A_c, B_c) of channel 16 c_begin + tid + k * 512 (PC <= 1024: at most two table entries per thread and
-    // sample; the clamp to Cin - 1 covers the padded last chunk of the last part; G8: also the region's second sample, clamped to the last one), fetched by asm loads into v172-v179 IN FRONT of the first
-    // patches (see the prologue below) and parked in the LDS table once they have landed
-    const float* co_src[G8 ? 4 : 2];
+    // prologue coefficients of this sample: (A_c, B_c) of channel 16 c_begin + tid + k * 512 (the clamp to Cin - 1 covers the padded last
+    // chunk of the last part), fetched by asm loads into v172-v179 IN FRONT of the first patches (see the prologue below) and parked in the
+    // LDS table once they have landed.  G8: PC <= WINO_TABLE_CH, two entries per thread for each of the region's two samples (the second
+    // clamped to the last one), pairs [2 + k].  Regions of a plane: PC <= WINO_TABLE_CH_PLANE, up to four entries per thread of the one sample,
+    // pairs [k]; entries 2 and 3 are requested (and read back) only where the table has them -- `wide`, uniform over the workgroup -- so a
+    // launch of PC <= 1024 issues the two loads it always did.
+    constexpr int NE = G8 ? 2 : 4;                               // table entries per thread and sample
+    const bool wide = !G8 && PC > 2 * NT;
+    const float* co_src[4];
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < NE; ++k) {
         co_src[k] = a.coef + ((long)b * Cin + min(CK * c_begin + tid + k * NT, Cin - 1)) * 2;
         if (G8) co_src[2 + k] = a.coef + ((long)min(b + 1, a.B - 1) * Cin + min(CK * c_begin + tid + k * NT, Cin - 1)) * 2;
     }
@@ -159,7 +164,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
                                            // oldest VMEM operations of the wave: their latency passes under the index arithmetic below
         asm volatile("global_load_dwordx2 v[172:173], %0, off\n\tglobal_load_dwordx2 v[174:175], %1, off"
                      :: "v"(co_src[0]), "v"(co_src[1]) : "memory");
-        if constexpr (G8)
+        if (G8 || wide)
             asm volatile("global_load_dwordx2 v[176:177], %0, off\n\tglobal_load_dwordx2 v[178:179], %1, off"
                          :: "v"(co_src[2]), "v"(co_src[3]) : "memory");
     }
@@ -468,19 +473,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
         if (rec) sp[1] = __builtin_amdgcn_s_memtime() - tk0;      // first patches landed
         float cdep = 0.0f;
         if (PRO) {
-            f32x2 cpre[G8 ? 4 : 2];
+            f32x2 cpre[4] = {{1.0f, 0.0f}, {1.0f, 0.0f}, {1.0f, 0.0f}, {1.0f, 0.0f}};
             asm volatile("v_mov_b32 %0, v172\n\tv_mov_b32 %1, v173\n\tv_mov_b32 %2, v174\n\tv_mov_b32 %3, v175"
                          : "=v"(cpre[0].x), "=v"(cpre[0].y), "=v"(cpre[1].x), "=v"(cpre[1].y) : "s"(vtok));
-            if constexpr (G8)
+            if (G8 || wide)
                 asm volatile("v_mov_b32 %0, v176\n\tv_mov_b32 %1, v177\n\tv_mov_b32 %2, v178\n\tv_mov_b32 %3, v179"
                              : "=v"(cpre[2].x), "=v"(cpre[2].y), "=v"(cpre[3].x), "=v"(cpre[3].y) : "s"(vtok));
 #pragma unroll
-            for (int k = 0; k < 2; ++k)
+            for (int k = 0; k < NE; ++k)               // (k >= 2: never below PC unless `wide`)
                 if (tid + k * NT < PC) {
                     *reinterpret_cast<f32x2*>(sCo + (tid + k * NT) * 2) = cpre[k];
                     if constexpr (G8) *reinterpret_cast<f32x2*>(sCo + (PC + tid + k * NT) * 2) = cpre[2 + k];
                 }
-            cdep = cpre[0].x + cpre[1].x + (G8 ? cpre[2].x + cpre[3].x : 0.0f);
+            cdep = cpre[0].x + cpre[1].x + cpre[2].x + cpre[3].x;
         }
         W3_LOAD_P(c_begin + 2, cdep, ofs)  // (behind the reads of v172-v179)
         if (PRO || G8) __syncthreads();    // coefficient table (and the zeroed halo) visible
@@ -703,9 +708,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
 }
 
 // pc: the channels of one part (wino_part_channels): the coefficient table's entries per sample
-static size_t wino3_lds_bytes(int pc, bool g8) {
+static constexpr size_t wino3_lds_bytes(int pc, bool g8) {
     return (size_t)(2 * W3_VW + 2 * (W3_CK * 10 * W3_PP + 8) + (g8 ? 4 : 2) * pc + (g8 ? 1 : 3) * W3_NT) * sizeof(float);
 }
+// the widest tables either geometry parks fit a CU's LDS (the pitch is a build-time variant: the figure holds for the committed one)
+static_assert(W3_PP != 24 || wino3_lds_bytes(WINO_TABLE_CH_PLANE, false) == 151616, "a plane's table of WINO_TABLE_CH_PLANE channels");
+static_assert(wino3_lds_bytes(WINO_TABLE_CH_PLANE, false) <= 160 * 1024 && wino3_lds_bytes(WINO_TABLE_CH, true) <= 160 * 1024,
+              "the widest coefficient table, regions of a plane and 8 x 8, fits the LDS");
 
 // the K-split second pass lives in conv_wino.cpp
 int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s);
@@ -781,7 +790,7 @@ static int wino3_launch(const ConvArgs& a, hipStream_t s) {
 // pre-split packed weights present (11: and an even chunk count).
 bool conv_wino3_usable(const ConvArgs& a) {
     const bool g8 = a.H == 8 && a.W == 8;
-    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wpb && !a.gb && a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) && wino_part_channels(a.CinP, a.ksplit) <= WINO_TABLE_CH &&
+    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wpb && !a.gb && a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) && wino_part_channels(a.CinP, a.ksplit) <= (g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE) &&
            a.CinP % W3_CK == 0 && (a.C1 == 0 || a.C0 % W3_CK == 0) && a.H * a.W <= 16384 &&
            (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino3_lds_bytes(wino_part_channels(a.CinP, a.ksplit), g8) <= 160 * 1024 &&
            (a.ksplit < 2 || ((a.ksplit == 2 || a.ksplit == 4 || a.ksplit == 8) && (a.CinP / W3_CK) % a.ksplit == 0 &&
@@ -791,7 +800,7 @@ bool conv_wino3_usable(const ConvArgs& a) {
 // a.wpb: the layout of launch_pack_wino3_weight, packed for conv_wino_cout_tile(Cout).
 int launch_conv_wino3(const ConvArgs& a, hipStream_t s) {
     MCVD_REQUIRE(conv_wino3_usable(a), "winograd bf16x3 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d, %d channels per K part)",
-                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpb ? "present" : "missing", wino_max_cin(a.ksplit), WINO_TABLE_CH);
+                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpb ? "present" : "missing", wino_max_cin(a.ksplit), wino_table_ch(a.H == 8 && a.W == 8));
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd bf16x3 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {
