@@ -1529,7 +1529,7 @@ int mcvd_op_conv2d(mcvd_ctx* ctx, const float* x0, int C0, const float* x1, int 
         a.coef2 = ctx->spade_coef2;
         ConvArgs t = a;
         t.ksplit = k.family == CF_WINO ? k.kparts : 0;
-        MCVD_REQUIRE(conv_wino_usable(t) || (t.ksplit = 0, conv_wino_usable(t)), "op_conv2d: shape not served by the Winograd kernel");
+        MCVD_REQUIRE(conv_kernel_usable(CK_WINO, t) || (t.ksplit = 0, conv_kernel_usable(CK_WINO, t)), "op_conv2d: shape not served by the Winograd kernel");
     }
     return ctx->naive_conv ? launch_conv_naive(a, ctx->stream) : launch_conv_mfma(a, ctx->stream);
     API_CATCH

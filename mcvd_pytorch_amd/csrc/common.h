@@ -5,6 +5,8 @@
 #include <atomic>
 #include <string>
 
+#include "conv_kernels.h"
+
 
 namespace mcvd {
 
@@ -101,7 +103,7 @@ struct ConvArgs {
     int ksplit;           // Winograd kernel only: 2 = two workgroups per tile contract half the input channels each into
                           // `part`, a second pass sums the halves; 0/1 = off
     float* part;          // ksplit >= 2: scratch for the partial results, ksplit * B*Cout*H*W floats
-    size_t part_floats;   // capacity of `part` in floats: a K split that needs more is not usable (the *_usable tests refuse it)
+    size_t part_floats;   // capacity of `part` in floats: a K split that needs more is not usable (wino_admits refuses it)
     int wdma;             // 1: stage weight chunks by LDS-DMA (default), 0: through registers
     int pgrid;            // persistent Winograd kernel (conv_wino3p.cpp) only: > 0 = number of workgroups (context option "persist_grid": tests
                           // drive long item ranges and sample changes with a few workgroups); 0 = one per CU
@@ -129,10 +131,6 @@ struct ConvArgs {
 };
 int last_conv_gn_fused();
 void set_last_conv_gn_fused(int v);
-// the K-split partials of this launch fit the scratch the caller handed over
-inline bool conv_part_fits(const ConvArgs& a) {
-    return a.part != nullptr && (size_t)(a.ksplit < 2 ? 2 : a.ksplit) * a.B * a.Cout * a.H * a.W <= a.part_floats;
-}
 bool ksplit_reduce_gn_usable(const ConvArgs& a);
 int launch_ksplit_reduce_gn(const ConvArgs& a, hipStream_t s);
 bool conv1x1_h2_kv_supported(const ConvArgs& a, int cot);
@@ -149,45 +147,29 @@ int conv_kernel_launch(int id, const ConvArgs& a, hipStream_t s);
 int launch_im2col3x3(const float* x0, int C0, const float* x1, int C1, float* col, int B, int H, int W, int K, hipStream_t s);
 int launch_taps_shift_add(const float* z, const float* bias, const float* res, float scale, float* y, int B, int Cout, int H, int W, hipStream_t s);
 int launch_pack_conv_gemm_form(const float* w, float* wp, int Cout, int Cin, int form, int CoutP, hipStream_t s);
-// Input channels of the Winograd kernels.  A workgroup parks the GroupNorm (A, B) coefficients of the channels ITS chunks contract --
-// all of them without a K split, one part's with ConvArgs::ksplit -- in an LDS table.  A workgroup of 8 x 16-pixel regions (every plane but
-// 8 x 8) serves ONE sample and parks up to WINO_TABLE_CH_PLANE entries (four per thread of the 512-thread kernels, two per thread of
-// conv_wino.cpp's 1024); an 8 x 8 launch (G8) serves TWO samples per workgroup and parks up to WINO_TABLE_CH entries for each (two per
-// thread and sample, one in conv_wino.cpp): four entries for two samples do not fit the LDS.  So
-//     Cin <= WINO_MAX_CIN (ksplit >= 4: WINO_MAX_CIN_K4)   and   CinP / max(ksplit, 1) <= wino_table_ch(8 x 8 ?):
-// on planes of 16 x 16 and larger the unsplit ids take every layer up to WINO_MAX_CIN channels; at 8 x 8 layers of 1040 .. 2048 channels
-// are served by the K-split ids only.  A split of four or more parts takes WINO_MAX_CIN_K4 channels (144 chunks: 576 per part at 4 parts,
-// 288 at 8); the 2-way and unsplit launches stop at WINO_MAX_CIN (the 2-way split by this constant alone on a plane, where a part of 1152
-// channels would fit the table: its part buffers and the tuner's candidate rules are sized for WINO_MAX_CIN).
-constexpr int WINO_MAX_CIN = 2048;
-constexpr int WINO_MAX_CIN_K4 = 2304;          // a split of four or more parts takes this many
-inline int wino_max_cin(int ksplit) { return ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN; }
-constexpr int WINO_TABLE_CH = 1024;            // table entries per sample, 8 x 8 launches (two samples per workgroup); the persistent kernel; the SPADE-fused loader
-constexpr int WINO_TABLE_CH_PLANE = 2048;      // ... launches of 8 x 16-pixel regions (one sample per workgroup)
-inline int wino_table_ch(bool g8) { return g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE; }
-static_assert(WINO_TABLE_CH_PLANE == 2 * WINO_TABLE_CH && WINO_MAX_CIN <= WINO_TABLE_CH_PLANE, "an unsplit plane launch parks every channel up to WINO_MAX_CIN");
-inline int wino_part_channels(int CinP, int ksplit) { return CinP / (ksplit >= 2 ? ksplit : 1); }      // PC: the table's entries per sample
+// Which launches the Winograd kernels take (input channels, K parts, geometry): conv_kernels.h, kWinoRules / wino_admits; conv_kernel_usable
+// evaluates it.  A launcher checks its own launch with conv_wino_require (conv.cpp: the family's rule over `a` as it stands, a.ksplit = its
+// K parts) and ends with wino_launch_done; the one-shot kernels share wino_grid (conv_wino.cpp).
+int conv_wino_require(ConvFamily family, const ConvArgs& a, const char* what);
+dim3 wino_grid(const ConvArgs& a, bool g8, int bco, int parts);      // 8-aligned (region, cout tile) workgroups x K parts
+int wino_launch_done(const ConvArgs& a, bool g8, int parts, hipStream_t s);      // the K split's reduce pass, else the statistics partials the epilogue wrote
 // Winograd F(2x2,3x3) kernel (conv_wino.cpp): tile shape id 4 of the dispatcher
 bool conv_wino_supported(int ks, int H, int W);      // geometry only (decides whether transformed weights are packed at all)
 int conv_wino_cout_tile(int Cout);
-bool conv_wino_usable(const ConvArgs& a);            // shape id 4 applies to this launch
 int launch_conv_wino(const ConvArgs& a, hipStream_t s);
 int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s);      // second pass of the K split, 2 / 4 / 8 parts (every Winograd kernel)
 // the same convolution with the channel contraction on the bf16 matrix pipe at fp32 accuracy (three exact bf16 pieces per operand,
 // six piece products, weights pre-split at pack time; conv_wino3.cpp): tile shape ids 10 / 11 (11: 2-way K split); needs ConvArgs::wpb
-bool conv_wino3_usable(const ConvArgs& a);
 int launch_conv_wino3(const ConvArgs& a, hipStream_t s);
 long conv_wino3_weight_floats(int CinP, int CoutP);           // size of the wpb buffer, in floats
 // the same kernel as PERSISTENT workgroups (one per CU, each walks a contiguous range of (region, cout tile[, K half]) items, the K loop's
 // staging pipeline runs on across item boundaries; conv_wino3p.cpp): tile shape ids 16 / 17 (17: 2-way K split); bit-identical results
-bool conv_wino3p_usable(const ConvArgs& a);
 int launch_conv_wino3p(const ConvArgs& a, hipStream_t s);
 int launch_pack_wino3_weight(const float* w, float* wb, int Cout, int Cin, int CinP, int CoutP, hipStream_t s);    // wb zero-filled
 // the same convolution on the fp16 matrix pipe, operands split into two fp16 pieces (22-bit operands, three piece products; weights
 // pre-split at pack time; conv_wino2h.cpp): tile shape ids 12 / 13 (13: 2-way K split); needs ConvArgs::wph.
 // np = 1: the same kernel with ONE fp16 piece per operand (a draft arithmetic: 11-bit operands, fp32 accumulate): shape ids 24 / 25 (25: 2-way
-// K split); reads the first piece of the same ConvArgs::wph.  One usable() rule serves both piece counts.
-bool conv_wino2h_usable(const ConvArgs& a);
+// K split); reads the first piece of the same ConvArgs::wph.  One admission rule serves both piece counts.
 int launch_conv_wino2h(const ConvArgs& a, int np, hipStream_t s);
 long conv_wino2h_weight_floats(int CinP, int CoutP);          // size of the wph buffer (header + pieces), in floats
 int launch_pack_wino2h_weight(const float* w, float* wh, int Cout, int Cin, int CinP, int CoutP, hipStream_t s);   // wh zero-filled

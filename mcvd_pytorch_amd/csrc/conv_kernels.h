@@ -1,20 +1,10 @@
 // The convolution kernel variants, once: what each "shape id" is, what it needs, what it turns into when an arithmetic option is off and
 // what a launch tries after it.  The ids are public (the context options conv_shape / conv_shape1, the committed tuning tables under
 // profiles/, mcvd_last_conv_kernel / mcvd_model_op_kernel): a new variant gets a new number and one line here; numbers are never reused.
-// Plain C++17, no HIP: the static_asserts at the end check the table in every build.
-//
-// Input channels of the Winograd families (common.h: WINO_MAX_CIN = 2048, WINO_TABLE_CH = 1024, WINO_TABLE_CH_PLANE = 2048): a workgroup's GroupNorm
-// coefficient table covers the channels of its own K part, so a launch needs  Cin <= WINO_MAX_CIN  and  CinP / max(kparts, 1) <= WINO_TABLE_CH at
-// 8 x 8 (two samples per workgroup), <= WINO_TABLE_CH_PLANE on every other plane (one sample per workgroup, twice the entries per thread).  On planes
-// of 16 x 16 and larger the unsplit ids 4 / 10 / 12 / 24 take every layer up to 2048 channels -- no K-split scratch, so also the 32 x 32 layers of a model
-// above 1024 channels; at 8 x 8 they stop at 1024 and layers of 1040 .. 2048 are served by the K-split ids 8 / 11 / 18 / 19 / 13 / 26 / 25 / 27 where the
-// split's own conditions hold.  The persistent kernel (CF_WINO3P: 16 / 17 / 20) was NOT widened: it keeps one table of all Cin channels per run of
-// items, and a per-part table would have to be reloaded inside its item boundary; its fallback lists (17 -> 11, 20 -> 17 -> 16 -> 11) route round it.
-// The SPADE-fused loader of CF_WINO (ConvArgs::gb) stays at 1024 as well.
-// A split of four or more parts takes WINO_MAX_CIN_K4 = 2304 channels: layers of 2049 .. 2304 (the 2304-channel concats of the ngf-288 UCF-101 nets)
-// are served by ids 18 / 19 (bf16x3), 26 (f16x2) and 27 (f16x1) only.  The 2-way ids 8 / 11 / 13 / 25 refuse them (Cin <= WINO_MAX_CIN; at 8 x 8 also by the
-// table rule, 1152 channels per part), and CF_WINO has no 4-way split: with bf16x3 off such a layer runs the direct tile kernel.
+// Plain C++17, no HIP: the static_asserts at the end check the table in every build.  Which launches the Winograd families take is the second
+// table of this file (kWinoRules / wino_admits, below the id table).
 #pragma once
+#include <cstddef>
 #include <initializer_list>
 
 namespace mcvd {
@@ -105,6 +95,89 @@ constexpr int without_f16x2(int id) { return conv_kernel(id).id == id ? conv_ker
 constexpr int without_bf16x3(int id) { return conv_kernel(id).id == id ? conv_kernel(id).no_bf16x3 : id; }
 constexpr int without_f16x1(int id) { return conv_kernel(id).id == id ? conv_kernel(id).no_f16x1 : id; }
 
+// ---- which launches the Winograd families take ----
+// A workgroup parks the GroupNorm (A, B) coefficients of the channels ITS 16-channel chunks contract -- all of them without a K split, one
+// part's with one -- in an LDS table.  A workgroup of 8 x 16-pixel regions (every plane but 8 x 8) serves ONE sample and parks up to
+// WINO_TABLE_CH_PLANE entries (four per thread of the 512-thread kernels, two per thread of conv_wino.cpp's 1024); an 8 x 8 launch serves TWO
+// samples per workgroup and parks up to WINO_TABLE_CH entries for each: four entries for two samples do not fit the LDS.  So a launch needs
+//     Cin <= wino_max_cin(parts)   and   CinP / parts <= wino_table_ch(8 x 8 ?):
+// on planes of 16 x 16 and larger the unsplit ids 4 / 10 / 12 / 24 take every layer up to 2048 channels -- no K-split scratch, so also the
+// 32 x 32 layers of a model above 1024 channels; at 8 x 8 they stop at 1024 and layers of 1040 .. 2048 channels are served by the K-split ids
+// 8 / 11 / 18 / 19 / 13 / 26 / 25 / 27 where the split's own conditions hold.  A split of four or more parts takes WINO_MAX_CIN_K4 channels (144
+// chunks: 576 per part at 4 parts, 288 at 8): layers of 2049 .. 2304 (the concats of the ngf-288 UCF-101 nets) are served by ids 18 / 19
+// (bf16x3), 26 (f16x2) and 27 (f16x1) only.  The 2-way and unsplit launches stop at WINO_MAX_CIN -- the 2-way split by this constant alone
+// on a plane, where a part of 1152 channels would fit the table: its part buffers and the tuner's candidate rules are sized for it -- and
+// CF_WINO has no 4-way split: with bf16x3 off such a layer runs the direct tile kernel.
+// The persistent kernel (CF_WINO3P) was NOT widened: it keeps one table of ALL Cin channels per run of items of a sample, split or not (an
+// item of another part would need its table reloaded inside the item boundary), so it stops at WINO_TABLE_CH; its fallback lists
+// (17 -> 11, 20 -> 17 -> 16 -> 11) route round it.  The SPADE-fused loader of CF_WINO (ConvArgs::gb) stays at WINO_TABLE_CH as well.
+// The LDS request is no term of the rule: each kernel file static_asserts that the widest table its row admits fits a CU's 160 KiB.
+constexpr int WINO_MAX_CIN = 2048;
+constexpr int WINO_MAX_CIN_K4 = 2304;          // a split of four or more parts takes this many
+constexpr int WINO_TABLE_CH = 1024;            // table entries per sample, 8 x 8 launches (two samples per workgroup); the persistent kernel; the SPADE-fused loader
+constexpr int WINO_TABLE_CH_PLANE = 2048;      // ... launches of 8 x 16-pixel regions (one sample per workgroup)
+static_assert(WINO_TABLE_CH_PLANE == 2 * WINO_TABLE_CH && WINO_MAX_CIN <= WINO_TABLE_CH_PLANE, "an unsplit plane launch parks every channel up to WINO_MAX_CIN");
+static_assert(WINO_MAX_CIN_K4 > 2 * WINO_TABLE_CH && WINO_MAX_CIN <= 2 * WINO_TABLE_CH, "above WINO_MAX_CIN a 2-way part overflows the 8 x 8 table");
+constexpr int wino_max_cin(int parts) { return parts >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN; }
+constexpr int wino_table_ch(bool g8) { return g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE; }
+constexpr int wino_part_channels(int CinP, int parts) { return CinP / (parts >= 2 ? parts : 1); }      // PC: the table's entries per sample
+constexpr bool wino_needs_4_parts(int Cin) { return Cin > WINO_MAX_CIN; }      // no launch of fewer than four parts takes this layer (the tuner offers 4 at every batch)
+// the K parts a kernel makes of ConvArgs::ksplit.  conv_wino.cpp counts 2 as a split and every other value, 4 included, as none; the others
+// take the value as it comes, and the rule refuses the counts their row does not have
+constexpr int wino_kernel_parts(ConvFamily f, int ksplit) { return f == CF_WINO ? (ksplit == 2 ? 2 : 1) : ksplit; }
+
+struct WinoLaunch {        // what the rule reads of a launch
+    int ks, H, W, B, Cin, CinP, C0, C1, Cout, CoutP;
+    int parts;             // wino_kernel_parts(family, ConvArgs::ksplit)
+    bool weights;          // the family's weight image is present
+    bool spade;            // ConvArgs::gb: the SPADE-fused loader
+    size_t part_floats;    // room for the K split's partial results, in floats; 0: no scratch
+};
+
+struct WinoRule {
+    ConvFamily family;
+    int chunk;             // input channels per chunk: CinP is a multiple, and no chunk straddles the concat seam
+    bool g8;               // serves 8 x 8 images in pairs, next to regions of 8 x 16 pixels
+    int max_hw;            // H * W at most; 0: no cap
+    int min_chunks[4];     // fewest chunks per part of an unsplit launch and of 2, 4, 8 parts; 0: the family has no such split
+    bool spade;            // has the SPADE-fused loader, for Cin <= WINO_TABLE_CH
+    bool persistent;       // one table of all Cin channels (Cin <= WINO_TABLE_CH, split or not); 32-bit item count
+};
+inline constexpr WinoRule kWinoRules[] = {
+    // family    chunk  g8    max_hw  min_chunks      spade  persistent
+    {CF_WINO,     16,  true,  0,      {1, 2, 0, 0},   true,  false},
+    {CF_WINO2H,   16,  true,  16384,  {1, 2, 3, 0},   false, false},     // CF_WINO1H as well: one rule for both piece counts; 4 parts: the prologue requests three chunks
+    {CF_WINO3,    16,  true,  16384,  {1, 2, 2, 2},   false, false},
+    {CF_WINO3P,   16,  false, 16384,  {4, 4, 4, 4},   false, true},      // the stream of an item needs four chunks
+};
+constexpr const WinoRule* wino_rule(ConvFamily f) {
+    for (const WinoRule& r : kWinoRules)
+        if (r.family == (f == CF_WINO1H ? CF_WINO2H : f)) return &r;
+    return nullptr;
+}
+
+constexpr bool wino_admits(ConvFamily f, const WinoLaunch& l) {
+    const WinoRule* r = wino_rule(f);
+    if (!r || l.ks != 3 || !l.weights) return false;
+    const bool g8 = l.H == 8 && l.W == 8;
+    if (!((l.H % 8 == 0 && l.W % 16 == 0 && l.H >= 8 && l.W >= 16) || (r->g8 && g8))) return false;
+    if (r->max_hw && l.H * l.W > r->max_hw) return false;
+    if (l.CinP % r->chunk != 0 || (l.C1 != 0 && l.C0 % r->chunk != 0)) return false;
+    if ((long)l.B * (l.C0 > l.C1 ? l.C0 : l.C1) * l.H * l.W >= (1L << 29)) return false;      // 32-bit byte offsets of the patch loads
+    if (l.spade && !(r->spade && l.Cin <= WINO_TABLE_CH)) return false;
+    const int parts = l.parts >= 2 ? l.parts : 1;
+    const int slot = parts == 1 ? 0 : parts == 2 ? 1 : parts == 4 ? 2 : parts == 8 ? 3 : -1;
+    if (slot < 0 || r->min_chunks[slot] == 0) return false;
+    const int nch = l.CinP / r->chunk;
+    if (nch % parts != 0 || nch / parts < r->min_chunks[slot]) return false;
+    if (r->persistent) {
+        if (l.Cin > WINO_TABLE_CH || (long)l.B * (l.H / 8) * (l.W / 16) * (l.CoutP / 32) * 8 >= (1L << 31)) return false;
+    } else if (l.Cin > wino_max_cin(parts) || wino_part_channels(l.CinP, parts) > wino_table_ch(g8)) {
+        return false;
+    }
+    return parts == 1 || (l.part_floats != 0 && (size_t)parts * l.B * l.Cout * l.H * l.W <= l.part_floats);
+}
+
 // ---- the table, checked ----
 namespace conv_kernels_check {
 constexpr int N = sizeof(kConvKernels) / sizeof(kConvKernels[0]);
@@ -180,6 +253,61 @@ static_assert(CK_WINO2H_K4 == 26 && CK_WINO1H_K4 == 27 && pieces(26) == 2 && pie
 static_assert(without_f16x2(26) == 18 && without_f16x1(26) == 26 && without_bf16x3(26) == 26 && without_f16x1(27) == 18 && without_f16x2(27) == 27 &&
               without_bf16x3(27) == 27, "their option off: the three-piece 4-way split; the other options leave them alone");
 static_assert(without_bf16x3(without_f16x2(26)) == 8 && without_bf16x3(without_f16x1(27)) == 8, "... and bf16x3 off as well: the fp32-MFMA 2-way split");
+
+// the admission rule over concrete launches: B = 2, Cout = 32, a square plane, weights present, room for exactly the parts.  ksplit is
+// ConvArgs::ksplit as a caller hands it over; C0 = 0: one source.  tests/test_wino_rule_cpu.py evaluates the same list with tests/wino_rule.py.
+struct WinoCase { ConvFamily family; int Cin, CinP, ksplit, plane, C0; bool spade, admitted; };
+inline constexpr WinoCase kWinoCases[] = {
+    // the two table sizes: 1024 entries per sample at 8 x 8, 2048 on a plane
+    {CF_WINO3, 1040, 1040, 0, 8, 0, false, false},  {CF_WINO3, 1040, 1040, 0, 16, 0, false, true},
+    {CF_WINO3, 1024, 1024, 0, 8, 0, false, true},   {CF_WINO3, 1024, 1024, 0, 16, 0, false, true},
+    {CF_WINO3, 2048, 2048, 0, 16, 0, false, true},  {CF_WINO3, 2035, 2048, 0, 16, 0, false, true},   {CF_WINO3, 2048, 2048, 0, 8, 0, false, false},
+    {CF_WINO3, 2064, 2064, 0, 8, 0, false, false},  {CF_WINO3, 2064, 2064, 0, 16, 0, false, false},
+    {CF_WINO3, 2049, 2064, 0, 8, 0, false, false},  {CF_WINO3, 2049, 2064, 0, 16, 0, false, false},
+    {CF_WINO3, 1440, 1440, 0, 32, 0, false, true},  {CF_WINO3, 1152, 1152, 0, 32, 0, false, true},
+    {CF_WINO3, 1344, 1344, 0, 16, 0, false, true},  {CF_WINO3, 1728, 1728, 0, 16, 0, false, true},
+    // 2304 channels: four parts or eight; two parts are refused by the channel bound even where a part of 1152 channels fits the table
+    {CF_WINO3, 2304, 2304, 2, 8, 0, false, false},  {CF_WINO3, 2304, 2304, 2, 16, 0, false, false},  {CF_WINO3, 2304, 2304, 0, 16, 0, false, false},
+    {CF_WINO3, 2304, 2304, 4, 8, 0, false, true},   {CF_WINO3, 2304, 2304, 4, 16, 0, false, true},   {CF_WINO3, 2304, 2304, 8, 8, 0, false, true},
+    {CF_WINO3, 2290, 2304, 4, 8, 0, false, true},   {CF_WINO3, 2320, 2320, 4, 8, 0, false, false},   {CF_WINO3, 2160, 2160, 4, 8, 0, false, false},
+    {CF_WINO2H, 2304, 2304, 4, 8, 0, false, true},  {CF_WINO1H, 2304, 2304, 4, 16, 0, false, true},  {CF_WINO2H, 2304, 2304, 2, 16, 0, false, false},
+    // part counts a family does not have
+    {CF_WINO2H, 2304, 2304, 8, 8, 0, false, false}, {CF_WINO3, 768, 768, 3, 8, 0, false, false},     {CF_WINO3, 1024, 1024, 16, 8, 0, false, false},
+    {CF_WINO3P, 768, 768, 16, 16, 0, false, false}, {CF_WINO1H, 768, 768, 3, 16, 0, false, false},
+    // the 4-way split of the fp16 kernels: chunks that divide by 4, three per part at least, no chunk across the seam
+    {CF_WINO2H, 192, 192, 4, 8, 0, false, true},    {CF_WINO2H, 128, 128, 4, 8, 0, false, false},    {CF_WINO2H, 288, 288, 4, 8, 0, false, false},
+    {CF_WINO2H, 256, 256, 4, 8, 100, false, false}, {CF_WINO2H, 256, 256, 4, 8, 160, false, true},   {CF_WINO2H, 250, 256, 4, 8, 0, false, true},
+    {CF_WINO2H, 1088, 1088, 4, 8, 0, false, true},  {CF_WINO2H, 1040, 1040, 4, 8, 0, false, false},  {CF_WINO2H, 2320, 2320, 4, 8, 0, false, false},
+    {CF_WINO1H, 192, 192, 4, 16, 0, false, true},   {CF_WINO1H, 128, 128, 4, 16, 0, false, false},   {CF_WINO3, 128, 128, 4, 16, 0, false, true},
+    // the persistent kernel: all of Cin in one table, four chunks per part, regions only
+    {CF_WINO3P, 1040, 1040, 0, 16, 0, false, false}, {CF_WINO3P, 1040, 1040, 2, 16, 0, false, false}, {CF_WINO3P, 1024, 1024, 2, 16, 0, false, true},
+    {CF_WINO3P, 48, 48, 0, 16, 0, false, false},    {CF_WINO3P, 96, 96, 2, 16, 0, false, false},     {CF_WINO3P, 96, 96, 0, 16, 0, false, true},
+    {CF_WINO3P, 256, 256, 0, 8, 0, false, false},   {CF_WINO3, 256, 256, 0, 8, 0, false, true},
+    // conv_wino.cpp: the SPADE-fused loader stays at 1024 channels; only 2 is a split
+    {CF_WINO, 1152, 1152, 0, 16, 0, true, false},   {CF_WINO, 1152, 1152, 0, 16, 0, false, true},    {CF_WINO, 1024, 1024, 0, 16, 0, true, true},
+    {CF_WINO3, 256, 256, 0, 16, 0, true, false},    {CF_WINO, 48, 48, 2, 8, 0, false, false},        {CF_WINO, 48, 48, 4, 8, 0, false, true},
+    {CF_WINO, 1152, 1152, 4, 8, 0, false, false},   {CF_WINO, 1152, 1152, 2, 8, 0, false, true},     {CF_WINO, 2304, 2304, 2, 16, 0, false, false},
+};
+constexpr WinoLaunch wino_case_launch(const WinoCase& c) {
+    const int parts = wino_kernel_parts(c.family, c.ksplit);
+    return {3, c.plane, c.plane, 2, c.Cin, c.CinP, c.C0 ? c.C0 : c.Cin, c.C0 ? c.Cin - c.C0 : 0, 32, 32, parts, true, c.spade,
+            parts >= 2 ? (size_t)parts * 2 * 32 * c.plane * c.plane : 0};
+}
+constexpr int first_wrong_wino_case() {
+    int i = 0;
+    for (const WinoCase& c : kWinoCases) {
+        if (wino_admits(c.family, wino_case_launch(c)) != c.admitted) return i;
+        ++i;
+    }
+    return -1;
+}
+static_assert(first_wrong_wino_case() == -1, "the admission rule disagrees with kWinoCases at this index");
+constexpr WinoLaunch with_room(WinoLaunch l, size_t part_floats) { l.part_floats = part_floats; return l; }
+static_assert(!wino_admits(CF_WINO3, with_room(wino_case_launch({CF_WINO3, 1056, 1056, 2, 8, 0, false, true}), 2 * 2 * 32 * 64 - 1)) &&
+              !wino_admits(CF_WINO3, with_room(wino_case_launch({CF_WINO3, 1056, 1056, 2, 8, 0, false, true}), 0)) &&
+              wino_admits(CF_WINO3, with_room(wino_case_launch({CF_WINO3, 1056, 1056, 2, 8, 0, false, true}), 2 * 2 * 32 * 64)),
+              "a K split needs room for its partial results");
+static_assert(wino_needs_4_parts(2304) && !wino_needs_4_parts(2048), "layers the tuner offers four parts at every batch");
 }  // namespace conv_kernels_check
 
 }  // namespace mcvd

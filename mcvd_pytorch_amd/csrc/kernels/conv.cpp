@@ -47,16 +47,32 @@ static ConvArgs with_k_parts(const ConvKernelDesc& k, const ConvArgs& a) {
 static int dma1_chunk(int id) { return id == CK_DMA1_CK32 ? 32 : 16; }      // channels per chunk
 static int dma1_pxw(int id) { return id == CK_DMA1_PX64 ? 2 : 1; }          // 2: 64 pixels per wave
 
+// what the admission rule (conv_kernels.h: wino_admits) reads of a launch of `family` with a.ksplit = ksplit
+static WinoLaunch wino_launch_of(ConvFamily family, const ConvArgs& a, int ksplit) {
+    const float* w = family == CF_WINO ? a.wpw : (family == CF_WINO2H || family == CF_WINO1H) ? a.wph : a.wpb;
+    return {a.ks, a.H, a.W, a.B, a.Cin, a.CinP, a.C0, a.C1, a.Cout, a.CoutP, wino_kernel_parts(family, ksplit), w != nullptr, a.gb != nullptr,
+            a.part ? a.part_floats : 0};
+}
+
+int conv_wino_require(ConvFamily family, const ConvArgs& a, const char* what) {
+    const int parts = wino_kernel_parts(family, a.ksplit);
+    MCVD_REQUIRE(wino_admits(family, wino_launch_of(family, a, a.ksplit)),
+                 "%s: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weights %s; Cin <= %d, %d channels per K part)", what, a.ks, a.H, a.W,
+                 a.Cin, a.C0, a.ksplit, wino_launch_of(family, a, a.ksplit).weights ? "present" : "missing",
+                 family == CF_WINO3P ? WINO_TABLE_CH : wino_max_cin(parts), family == CF_WINO3P ? WINO_TABLE_CH : wino_table_ch(a.H == 8 && a.W == 8));
+    return 0;
+}
+
 // One usable / launch pair for every kernel the dispatcher serves, keyed by id.  The direct tiles (launch_conv_mfma's heuristic) and the GEMM
 // forms of a 3x3 (model.cpp) are not launched from here: not usable.
 bool conv_kernel_usable(int id, const ConvArgs& a) {
     const ConvKernelDesc& k = conv_kernel(id);
     switch (k.family) {
-        case CF_WINO: return conv_wino_usable(with_k_parts(k, a));
+        case CF_WINO:
         case CF_WINO2H:
-        case CF_WINO1H: return conv_wino2h_usable(with_k_parts(k, a));
-        case CF_WINO3: return conv_wino3_usable(with_k_parts(k, a));
-        case CF_WINO3P: return conv_wino3p_usable(with_k_parts(k, a));
+        case CF_WINO1H:
+        case CF_WINO3:
+        case CF_WINO3P: return wino_admits(k.family, wino_launch_of(k.family, a, k.id != CK_WINO ? k.kparts : a.ksplit));      // (with_k_parts)
         case CF_SPLIT1: return conv1x1_h2_supported(a, a.cot, k.pieces);
         case CF_DMA1: return conv1x1_dma_supported(a, dma1_chunk(id), dma1_pxw(id)) && !(id == CK_DMA1_CK32 && a.cot == 9);
         default: return false;

@@ -626,8 +626,12 @@ static constexpr size_t wino_lds_bytes(int pc, bool g8, bool spade = false) {
     return k > epi ? k : epi;
 }
 static_assert(WR_PP != 24 || wino_lds_bytes(WINO_TABLE_CH_PLANE, false) == 112672, "a plane's table of WINO_TABLE_CH_PLANE channels");
-static_assert(wino_lds_bytes(WINO_TABLE_CH_PLANE, false) <= 160 * 1024 && wino_lds_bytes(WINO_TABLE_CH, true, true) <= 160 * 1024,
-              "the widest coefficient tables fit the LDS: a plane's, and the SPADE loader's two tables for two 8 x 8 samples");
+// the widest launches the rule admits (conv_kernels.h: kWinoRules) fit a CU's LDS, so the rule carries no LDS term
+static_assert(wino_lds_bytes(WINO_TABLE_CH_PLANE, false) <= 160 * 1024 && wino_lds_bytes(WINO_TABLE_CH, true) <= 160 * 1024 &&
+              wino_lds_bytes(WINO_TABLE_CH, true, true) <= 160 * 1024 && wino_lds_bytes(WINO_TABLE_CH, false, true) <= wino_lds_bytes(WINO_TABLE_CH_PLANE, false, true) &&
+              wino_lds_bytes(WINO_TABLE_CH_PLANE, false, true) <= 160 * 1024,
+              "the widest coefficient tables fit the LDS: a plane's, two 8 x 8 samples', and the SPADE loader's two tables on either geometry (on a plane "
+              "it takes WINO_TABLE_CH channels; even a padded CinP of a whole plane table would fit)");
 
 #ifdef MCVD_DIAG
 template <int EXP>
@@ -699,19 +703,33 @@ int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s) {
     return 0;
 }
 
+// The grid of the one-shot kernels (this file, conv_wino2h.cpp, conv_wino3.cpp): regions of 8 x 16 pixels or pairs of 8 x 8 images, rounded up
+// to eight, times the cout tiles of bco channels; y: the K parts.
+dim3 wino_grid(const ConvArgs& a, bool g8, int bco, int parts) {
+    const int nreg = g8 ? (a.B + 1) / 2 : a.B * (a.H / 8) * (a.W / 16);
+    return dim3(((nreg + 7) / 8) * 8 * (a.CoutP / bco), parts);
+}
+
+// After the launch of any Winograd kernel: the K split's second pass, else the count of statistics partials its epilogue wrote.
+int wino_launch_done(const ConvArgs& a, bool g8, int parts, hipStream_t s) {
+    MCVD_HIP_CHECK(hipGetLastError());
+    if (parts >= 2) return launch_wino_ksplit_reduce(a, s);
+    if (a.stats) set_last_conv_stats_np(g8 ? 1 : (a.H / 8) * (a.W / 16));
+    return 0;
+}
+
 template <int COT, int PRO, bool G8>
 static int wino_launch3(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
-    const size_t lds = wino_lds_bytes(wino_part_channels(a.CinP, a.ksplit == 2 ? 2 : 1), G8, PRO == 3);
+    const int ksp = wino_kernel_parts(CF_WINO, a.ksplit);
+    const size_t lds = wino_lds_bytes(wino_part_channels(a.CinP, ksp), G8, PRO == 3);
     static PerDeviceOnce raised;
     if (raised.first_use()) {
         MCVD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_kernel<COT, PRO, G8>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         raised.done();
     }
-    const int nreg = G8 ? (a.B + 1) / 2 : a.B * (a.H / 8) * (a.W / 16);
-    const int ksp = a.ksplit == 2 ? 2 : 1;
-    dim3 grid(((nreg + 7) / 8) * 8 * (a.CoutP / BCO), ksp);
+    const dim3 grid = wino_grid(a, G8, BCO, ksp);
     ConvArgs k = a;
     if (k.dbg) k.wdma = 0;                 // wave 0 records its phase times
 #ifdef MCVD_DIAG
@@ -728,13 +746,7 @@ static int wino_launch3(const ConvArgs& a, hipStream_t s) {
     } else
 #endif
     hipLaunchKernelGGL((conv_wino_kernel<COT, PRO, G8>), grid, dim3(WR_NT), lds, s, k);
-    MCVD_HIP_CHECK(hipGetLastError());
-    if (ksp == 2) {
-        if (int rc = launch_wino_ksplit_reduce(a, s)) return rc;
-    } else if (a.stats) {
-        set_last_conv_stats_np(G8 ? 1 : (a.H / 8) * (a.W / 16));
-    }
-    return 0;
+    return wino_launch_done(a, G8, ksp, s);
 }
 
 template <int COT, int PRO>
@@ -762,25 +774,10 @@ int conv_wino_cout_tile(int Cout) {
     return 1;
 }
 
-// Shape ids 4 / 8 apply to this launch: geometry, channel layout, packed weights present (8: and an even chunk count).
-bool conv_wino_usable(const ConvArgs& a) {
-    // (this kernel splits two ways only: WINO_MAX_CIN_K4, the bound of the splits of four or more parts, never applies to it)
-    const int pc = wino_part_channels(a.CinP, a.ksplit == 2 ? 2 : 1);
-    static_assert(WINO_MAX_CIN_K4 > 2 * WINO_TABLE_CH && WINO_MAX_CIN <= 2 * WINO_TABLE_CH, "above WINO_MAX_CIN a 2-way part overflows the 8 x 8 table");
-    const bool g8 = a.H == 8 && a.W == 8;
-    return conv_wino_supported(a.ks, a.H, a.W) && a.wpw && a.Cin <= WINO_MAX_CIN && pc <= (g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE) && a.CinP % WR_CK == 0 &&
-           (a.gb == nullptr || a.Cin <= WINO_TABLE_CH) &&                            // the SPADE-fused loader (PRO 3) stays where it was
-
-           (a.C1 == 0 || a.C0 % WR_CK == 0) &&                                       // a chunk never straddles the concat seam
-           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) &&      // 32-bit byte offsets of the patch loads
-           wino_lds_bytes(pc, a.H == 8 && a.W == 8, a.gb != nullptr) <= 160 * 1024 &&
-           (a.ksplit != 2 || ((a.CinP / WR_CK) % 2 == 0 && a.CinP / WR_CK >= 4 && conv_part_fits(a)));
-}
-
 // a.wpw must hold the operand-major layout (launch_pack_wino_weight) packed for conv_wino_cout_tile(Cout).
 int launch_conv_wino(const ConvArgs& a, hipStream_t s) {
-    MCVD_REQUIRE(conv_wino_usable(a), "winograd conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weights %s; Cin <= %d, %d channels per K part)", a.ks,
-                 a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpw ? "present" : "missing", WINO_MAX_CIN, wino_table_ch(a.H == 8 && a.W == 8));
+    static_assert(wino_rule(CF_WINO)->chunk == WR_CK, "the rule's chunk is the kernel's");
+    if (int rc = conv_wino_require(CF_WINO, a, "winograd conv")) return rc;
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {

@@ -702,17 +702,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
 static constexpr size_t wino2h_lds_bytes(int np, int pc, bool g8) {
     return (size_t)(2 * h2_vw(np) + 2 * (H2_CK * 10 * H2_PP + 4) + (g8 ? 4 : 2) * pc + 6 * H2_NT) * sizeof(float);
 }
-// conv_wino2h_usable() serves both piece counts with the two-piece size in its LDS bound: the size grows with np, pc and g8, usable() holds pc
-// to WINO_TABLE_CH (8 x 8) or WINO_TABLE_CH_PLANE (regions of a plane, half the entries per channel), and the largest request fits -- the bound never decides, for either count
+// The size grows with np, pc and g8; the rule (conv_kernels.h: kWinoRules, one row for both piece counts) holds pc to WINO_TABLE_CH (8 x 8) or
+// WINO_TABLE_CH_PLANE (regions of a plane, half the entries per channel), and the largest request fits: the rule carries no LDS term
 static_assert(wino2h_lds_bytes(2, WINO_TABLE_CH, true) == 124960 && wino2h_lds_bytes(2, WINO_TABLE_CH, true) <= 160 * 1024,
               "two pieces, a full coefficient table for two samples: the most LDS a usable launch asks for");
 // regions of a plane park one sample's table of up to WINO_TABLE_CH_PLANE = 2 * WINO_TABLE_CH channels: the same words.  One piece with that
 // table asks for more than half a CU's LDS -- one workgroup per CU where the narrower launches run two; the tuner times it
 static_assert(wino2h_lds_bytes(2, WINO_TABLE_CH_PLANE, false) == 124960 && wino2h_lds_bytes(1, WINO_TABLE_CH_PLANE, false) == 92192,
               "a plane's table of WINO_TABLE_CH_PLANE channels, two pieces and one");
-
-// the K-split second pass lives in conv_wino.cpp
-int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s);
 
 template <int NP, int COT, int PRO, bool G8, int EXP>
 static int wino2h_launch_k(const ConvArgs& k, dim3 grid, size_t lds, hipStream_t s) {
@@ -730,9 +727,8 @@ template <int NP, int COT, int PRO, bool G8>
 static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
     const size_t lds = wino2h_lds_bytes(NP, wino_part_channels(a.CinP, a.ksplit), G8);
-    const int nreg = G8 ? (a.B + 1) / 2 : a.B * (a.H / 8) * (a.W / 16);
     const int ksp = a.ksplit >= 2 ? a.ksplit : 1;
-    dim3 grid(((nreg + 7) / 8) * 8 * (a.CoutP / BCO), ksp);
+    const dim3 grid = wino_grid(a, G8, BCO, ksp);
     int rc = 0;
     if constexpr (NP == 1) {               // no recording, no ablations (DIAG in the kernel): the caller's arguments as they come
         rc = wino2h_launch_k<1, COT, PRO, G8, 0>(a, grid, lds, s);
@@ -766,11 +762,7 @@ static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
             rc = wino2h_launch_k<2, COT, PRO, G8, 0>(k, grid, lds, s);
         }
     }
-    if (rc) return rc;
-    MCVD_HIP_CHECK(hipGetLastError());
-    if (ksp >= 2) return launch_wino_ksplit_reduce(a, s);
-    if (a.stats) set_last_conv_stats_np(G8 ? 1 : (a.H / 8) * (a.W / 16));
-    return 0;
+    return rc ? rc : wino_launch_done(a, G8, ksp, s);
 }
 
 template <int NP, int COT, bool G8>
@@ -785,23 +777,13 @@ static int wino2h_launch(const ConvArgs& a, hipStream_t s) {
     return (a.H == 8 && a.W == 8) ? wino2h_launch1<NP, COT, true>(a, s) : wino2h_launch1<NP, COT, false>(a, s);
 }
 
-// Shape ids 12 / 13 / 26 (two pieces) and 24 / 25 / 27 (one piece) apply to this launch: regions of 8 x 16 output pixels or 8 x 8 images (two per
-// workgroup), no SPADE prologue, pre-split packed weights present (13 / 25: and an even chunk count, two chunks per part at least; 26 / 27: a
-// chunk count that divides by 4, H2_MINCH_K4 chunks per part at least; all four: room for the parts in a.part).  One rule for both piece counts.
-bool conv_wino2h_usable(const ConvArgs& a) {
-    const bool g8 = a.H == 8 && a.W == 8;
-    const int nch = a.CinP / H2_CK;
-    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wph && !a.gb && a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) && wino_part_channels(a.CinP, a.ksplit) <= (g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE) &&
-           a.CinP % H2_CK == 0 && (a.C1 == 0 || a.C0 % H2_CK == 0) && a.H * a.W <= 16384 &&
-           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino2h_lds_bytes(2, wino_part_channels(a.CinP, a.ksplit), g8) <= 160 * 1024 &&
-           (a.ksplit < 2 || ((a.ksplit == 2 || (a.ksplit == 4 && nch / 4 >= H2_MINCH_K4)) && nch % a.ksplit == 0 && nch >= 2 * a.ksplit &&
-                             conv_part_fits(a)));
-}
+// Shape ids 12 / 13 / 26 (two pieces) and 24 / 25 / 27 (one piece): one row of the rule for both piece counts.
+static_assert(wino_rule(CF_WINO2H) == wino_rule(CF_WINO1H) && wino_rule(CF_WINO2H)->chunk == H2_CK && wino_rule(CF_WINO2H)->min_chunks[2] == H2_MINCH_K4,
+              "the rule's chunk and the fewest chunks of a 4-way part are the kernel's");
 
 template <int NP>
 static int wino2h_launch_np(const ConvArgs& a, hipStream_t s) {
-    MCVD_REQUIRE(conv_wino2h_usable(a), "winograd f16x%d conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d, %d channels per K part)",
-                 NP, a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wph ? "present" : "missing", wino_max_cin(a.ksplit), wino_table_ch(a.H == 8 && a.W == 8));
+    if (int rc = conv_wino_require(NP == 1 ? CF_WINO1H : CF_WINO2H, a, NP == 1 ? "winograd f16x1 conv" : "winograd f16x2 conv")) return rc;
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd f16x%d conv: CoutP=%d vs tile %d", NP, a.CoutP, 32 * cot);
     switch (cot) {

@@ -714,10 +714,7 @@ static constexpr size_t wino3_lds_bytes(int pc, bool g8) {
 // the widest tables either geometry parks fit a CU's LDS (the pitch is a build-time variant: the figure holds for the committed one)
 static_assert(W3_PP != 24 || wino3_lds_bytes(WINO_TABLE_CH_PLANE, false) == 151616, "a plane's table of WINO_TABLE_CH_PLANE channels");
 static_assert(wino3_lds_bytes(WINO_TABLE_CH_PLANE, false) <= 160 * 1024 && wino3_lds_bytes(WINO_TABLE_CH, true) <= 160 * 1024,
-              "the widest coefficient table, regions of a plane and 8 x 8, fits the LDS");
-
-// the K-split second pass lives in conv_wino.cpp
-int launch_wino_ksplit_reduce(const ConvArgs& a, hipStream_t s);
+              "the widest coefficient table the rule admits (conv_kernels.h: kWinoRules), regions of a plane and 8 x 8, fits the LDS: no LDS term in the rule");
 
 template <int COT, int PRO, bool G8, int EXP>
 static int wino3_launch_k(const ConvArgs& k, dim3 grid, size_t lds, hipStream_t s) {
@@ -735,9 +732,8 @@ template <int COT, int PRO, bool G8>
 static int wino3_launch2(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
     const size_t lds = wino3_lds_bytes(wino_part_channels(a.CinP, a.ksplit), G8);
-    const int nreg = G8 ? (a.B + 1) / 2 : a.B * (a.H / 8) * (a.W / 16);
     const int ksp = a.ksplit >= 2 ? a.ksplit : 1;
-    dim3 grid(((nreg + 7) / 8) * 8 * (a.CoutP / BCO), ksp);
+    const dim3 grid = wino_grid(a, G8, BCO, ksp);
     ConvArgs k = a;
     int rc = 0;
     if (k.dbg) k.wdma = 0;                 // wave 0 records its phase times
@@ -767,11 +763,7 @@ static int wino3_launch2(const ConvArgs& a, hipStream_t s) {
     {
         rc = wino3_launch_k<COT, PRO, G8, 0>(k, grid, lds, s);
     }
-    if (rc) return rc;
-    MCVD_HIP_CHECK(hipGetLastError());
-    if (ksp >= 2) return launch_wino_ksplit_reduce(a, s);
-    if (a.stats) set_last_conv_stats_np(G8 ? 1 : (a.H / 8) * (a.W / 16));
-    return 0;
+    return rc ? rc : wino_launch_done(a, G8, ksp, s);
 }
 
 template <int COT, bool G8>
@@ -786,21 +778,10 @@ static int wino3_launch(const ConvArgs& a, hipStream_t s) {
     return (a.H == 8 && a.W == 8) ? wino3_launch1<COT, true>(a, s) : wino3_launch1<COT, false>(a, s);
 }
 
-// Shape ids 10 / 11 apply to this launch: regions of 8 x 16 output pixels or 8 x 8 images (two per workgroup), no SPADE prologue,
-// pre-split packed weights present (11: and an even chunk count).
-bool conv_wino3_usable(const ConvArgs& a) {
-    const bool g8 = a.H == 8 && a.W == 8;
-    return a.ks == 3 && ((a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16) || g8) && a.wpb && !a.gb && a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) && wino_part_channels(a.CinP, a.ksplit) <= (g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE) &&
-           a.CinP % W3_CK == 0 && (a.C1 == 0 || a.C0 % W3_CK == 0) && a.H * a.W <= 16384 &&
-           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino3_lds_bytes(wino_part_channels(a.CinP, a.ksplit), g8) <= 160 * 1024 &&
-           (a.ksplit < 2 || ((a.ksplit == 2 || a.ksplit == 4 || a.ksplit == 8) && (a.CinP / W3_CK) % a.ksplit == 0 &&
-                             a.CinP / W3_CK >= 2 * a.ksplit && conv_part_fits(a)));        // every part at least two chunks
-}
-
 // a.wpb: the layout of launch_pack_wino3_weight, packed for conv_wino_cout_tile(Cout).
 int launch_conv_wino3(const ConvArgs& a, hipStream_t s) {
-    MCVD_REQUIRE(conv_wino3_usable(a), "winograd bf16x3 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d, %d channels per K part)",
-                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpb ? "present" : "missing", wino_max_cin(a.ksplit), wino_table_ch(a.H == 8 && a.W == 8));
+    static_assert(wino_rule(CF_WINO3)->chunk == W3_CK, "the rule's chunk is the kernel's");
+    if (int rc = conv_wino_require(CF_WINO3, a, "winograd bf16x3 conv")) return rc;
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd bf16x3 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {

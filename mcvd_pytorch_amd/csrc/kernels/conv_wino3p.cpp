@@ -607,9 +607,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
 #undef WP_VALU_PHASE
 }
 
-static size_t wino3p_lds_bytes(int Cin) {
+static constexpr size_t wino3p_lds_bytes(int Cin) {
     return (size_t)(2 * WP_VW + 2 * 4096 + 2 * Cin + 2 * WP_NPL * WP_NT) * sizeof(float);
 }
+static_assert(wino3p_lds_bytes(WINO_TABLE_CH) == 151552 && wino3p_lds_bytes(WINO_TABLE_CH) <= 160 * 1024,
+              "the widest table the rule admits (conv_kernels.h: kWinoRules, all Cin <= WINO_TABLE_CH channels) fits the LDS: no LDS term in the rule");
 
 // compute units of the current device (one persistent workgroup each), cached per device
 static int wino3p_num_cus() {
@@ -649,10 +651,7 @@ static int wino3p_launch2(const ConvArgs& a, hipStream_t s) {
     k.wdma &= 0xff;
 #endif
     hipLaunchKernelGGL((conv_wino3p_kernel<COT, PRO>), grid, dim3(WP_NT), wino3p_lds_bytes(a.Cin), s, k);
-    MCVD_HIP_CHECK(hipGetLastError());
-    if (ksp >= 2) return launch_wino_ksplit_reduce(a, s);
-    if (a.stats) set_last_conv_stats_np((a.H / 8) * (a.W / 16));
-    return 0;
+    return wino_launch_done(a, false, ksp, s);
 }
 
 template <int COT>
@@ -662,24 +661,12 @@ static int wino3p_launch1(const ConvArgs& a, hipStream_t s) {
     return wino3p_launch2<COT, 2>(a, s);
 }
 
-// Shape ids 16 / 17 apply to this launch: regions of 8 x 16 output pixels (not the 8x8 images), no SPADE prologue, no consumer-side
-// GroupNorm reduction, pre-split packed weights present, at least WP_MINCH chunks per item (17: per K half, and an even chunk count).
-// Cin <= WINO_TABLE_CH with or without a K split: a persistent workgroup keeps ONE table of all Cin channels per run of items of a sample
-// (an item of another part would need its table reloaded inside the item boundary); wider layers take the one-shot kernel (ids 11 / 18 / 19).
-bool conv_wino3p_usable(const ConvArgs& a) {
-    const int nchunks = a.CinP / WP_CK;
-    return a.ks == 3 && a.H % 8 == 0 && a.W % 16 == 0 && a.H >= 8 && a.W >= 16 && a.wpb && !a.gb && a.Cin <= WINO_TABLE_CH &&
-           a.CinP % WP_CK == 0 && (a.C1 == 0 || a.C0 % WP_CK == 0) && a.H * a.W <= 16384 &&
-           (long)a.B * (a.C0 > a.C1 ? a.C0 : a.C1) * a.H * a.W < (1L << 29) && wino3p_lds_bytes(a.Cin) <= 160 * 1024 &&
-           (long)a.B * (a.H / 8) * (a.W / 16) * (a.CoutP / 32) * 8 < (1L << 31) &&
-           (a.ksplit >= 2 ? ((a.ksplit == 2 || a.ksplit == 4 || a.ksplit == 8) && nchunks % a.ksplit == 0 && nchunks / a.ksplit >= WP_MINCH &&
-                             conv_part_fits(a))
-                          : nchunks >= WP_MINCH);
-}
-
+// Shape ids 16 / 17 / 20: regions of 8 x 16 output pixels only, at least WP_MINCH chunks per item, all Cin channels in one table (the rule's row
+// says why it stops at WINO_TABLE_CH); wider layers take the one-shot kernel (ids 11 / 18 / 19).
 int launch_conv_wino3p(const ConvArgs& a, hipStream_t s) {
-    MCVD_REQUIRE(conv_wino3p_usable(a), "persistent winograd bf16x3 conv: unsupported (ks=%d H=%d W=%d Cin=%d C0=%d ksplit=%d, packed weight pieces %s; Cin <= %d)",
-                 a.ks, a.H, a.W, a.Cin, a.C0, a.ksplit, a.wpb ? "present" : "missing", WINO_TABLE_CH);
+    static_assert(wino_rule(CF_WINO3P)->chunk == WP_CK && wino_rule(CF_WINO3P)->min_chunks[0] == WP_MINCH && wino_rule(CF_WINO3P)->min_chunks[3] == WP_MINCH,
+                  "the rule's chunk and the fewest chunks of an item are the kernel's");
+    if (int rc = conv_wino_require(CF_WINO3P, a, "persistent winograd bf16x3 conv")) return rc;
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "persistent winograd bf16x3 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
     switch (cot) {

@@ -832,8 +832,8 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
                 ConvArgs t = a;
                 t.shape_hint = a.shape_hint == CK_WINO_K2 ? CK_WINO_K2 : CK_WINO;
                 t.ksplit = k_parts(t.shape_hint);
-                bool fused = want_fused && conv_wino_usable(t);
-                if (!fused && t.ksplit == 2) { t.ksplit = 0; t.shape_hint = CK_WINO; fused = want_fused && conv_wino_usable(t); }
+                bool fused = want_fused && conv_kernel_usable(CK_WINO, t);
+                if (!fused && t.ksplit == 2) { t.ksplit = 0; t.shape_hint = CK_WINO; fused = want_fused && conv_kernel_usable(CK_WINO, t); }
                 if (fused) {
                     a.shape_hint = t.shape_hint;
                     ++fused_launches[2];
@@ -1109,7 +1109,7 @@ int mcvd_model::autotune(int B) {
             const long pairs = op.ks == 3 ? (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout))) : 0;
             // (a layer of more than WINO_MAX_CIN channels has no 2-way split to fall back on -- 4 parts are the shallowest Winograd launch that takes
             // it -- so it is offered the 4-way ids at every batch; the 8-way one on the terms of every other layer)
-            const bool few_pairs = op.ks == 3 && (2 * pairs < 1024 || cin > WINO_MAX_CIN);
+            const bool few_pairs = op.ks == 3 && (2 * pairs < 1024 || wino_needs_4_parts(cin));
             if (op.ks == 3 && ctx->winograd && ctx->bf16x3 && !spade_fused) {     // Winograd on the bf16 pipe, three exact pieces per operand
                 for (int id : {CK_WINO3, CK_WINO3_K2, CK_WINO3P, CK_WINO3P_K2})    // (persistent: the staging pipeline runs on across the items of a CU)
                     if (int rc = offer(id, op.cot)) return rc;
@@ -1228,7 +1228,7 @@ int mcvd_model::ensure_ksplit(int B) {
         int parts = 2;
         const bool g8 = op.H == 8 && op.W == 8;
         const long pairs = (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout)));
-        const bool wide = op.src0.C + (op.src1.kind == REF_NONE ? 0 : op.src1.C) > WINO_MAX_CIN;             // no 2-way split takes it: autotune() offers 4 parts at every batch
+        const bool wide = wino_needs_4_parts(op.src0.C + (op.src1.kind == REF_NONE ? 0 : op.src1.C));        // autotune() offers 4 parts at every batch
         if (ctx->autotune && !table && tuned_B != B && (2 * pairs < 1024 || wide)) parts = 4 * pairs < 1024 ? 8 : 4;    // the candidates autotune() is about to time
         auto deepen = [&](int shape) { parts = std::max(parts, k_parts(shape)); };
         deepen(ctx->conv_shape);

@@ -1,14 +1,17 @@
 """CPU: the 4-way K split of the two fp16 Winograd kernels (shape ids 26 / 27; conv_wino2h.cpp with two pieces and with one) -- the partition of the
-16-channel chunks into parts and the rule that admits a layer, restated here and walked over every layer shape up to 1024 channels.
+16-channel chunks into parts, walked over every layer shape the rule admits (CinP up to 2304 channels).
 
 The kernels: `nch = CinP / 16` chunks; workgroup (.., blockIdx.y = part) contracts chunks [part * nch / 4, (part + 1) * nch / 4) and writes its raw
 partial result to a.part[part]; chunk c reads channels 16 c .. 16 c + 15 from x0 when 16 c < C0, else from x1 (one source per chunk).
-usable(): nch % 4 == 0, nch / 4 >= MINCH_K4 = 3 (the prologue requests the patches of three chunks; a shorter part would fetch its
-neighbour's), no chunk across the concat seam (C1 == 0 or C0 % 16 == 0), Cin <= 1024 -- and room for four partial results, which is the
-caller's buffer and not restated here.  The table rows and static_asserts of conv_kernels.h are checked by every build of the library.
+The rule (conv_kernels.h: wino_admits, restated by tests/wino_rule.py): nch % 4 == 0, nch / 4 >= MINCH_K4 = 3 (the prologue requests the patches
+of three chunks; a shorter part would fetch its neighbour's), no chunk across the concat seam (C1 == 0 or C0 % 16 == 0), Cin <= WINO_MAX_CIN_K4
+= 2304 and a part of at most 1024 channels at 8 x 8 -- and room for four partial results, which is the caller's buffer and not walked here.  The
+table rows and static_asserts of conv_kernels.h are checked by every build of the library.
 """
 import os
 import re
+
+from tests import wino_rule
 
 CK = 16
 MINCH_K4 = 3
@@ -16,10 +19,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcvd_pytorch_amd", "csrc")
 
 
-def usable_k4(Cin, CinP, C0, C1):
-    nch = CinP // CK
-    return (Cin <= 1024 and CinP % CK == 0 and (C1 == 0 or C0 % CK == 0)
-            and nch % 4 == 0 and nch >= 2 * 4 and nch // 4 >= MINCH_K4)
+def usable_k4(Cin, CinP, C0, C1, plane=8):
+    assert C0 + C1 == Cin
+    ok = wino_rule.admits("WINO2H", Cin, CinP, 4, plane=plane, C0=C0)
+    assert ok == wino_rule.admits("WINO1H", Cin, CinP, 4, plane=plane, C0=C0)          # one rule for both piece counts
+    return ok
 
 
 def parts(nch, ksp):
@@ -33,26 +37,31 @@ def chunk_source(c, Cin, C0):
 
 
 def test_the_restated_minimum_is_the_kernels():
-    f, name = "conv_wino2h.cpp", "H2_MINCH_K4"               # one kernel source, one constant, one usable() for both piece counts
+    f, name = "conv_wino2h.cpp", "H2_MINCH_K4"               # one kernel source, one constant, one row of the rule for both piece counts
     src = open(os.path.join(CSRC, "kernels", f)).read()
     m = re.findall(r"constexpr int \w*MINCH_K4 = (\d+);", src)
     assert m == [str(MINCH_K4)] and re.search(r"constexpr int %s = (\d+);" % name, src), (f, m)
-    assert re.search(r"a\.ksplit == 4 && nch / 4 >= %s" % name, src), f"{f}: usable() does not state the minimum"
-    assert len(re.findall(r"\nbool conv_wino\w+_usable\(", src)) == 1
+    assert "wino_rule(CF_WINO2H)->min_chunks[2] == %s" % name in src, f"{f}: the rule's minimum is not pinned to the kernel's"
+    assert wino_rule.RULES["WINO2H"][3][2] == MINCH_K4 and "WINO1H" not in wino_rule.RULES
     table = open(os.path.join(CSRC, "conv_kernels.h")).read()
     assert "CK_WINO2H_K4 = 26" in table and "CK_WINO1H_K4 = 27" in table
 
 
 def test_every_admitted_layer_is_partitioned_soundly():
-    admitted = seam_inside_a_part = 0
-    for CinP in range(CK, 1024 + 1, CK):
+    admitted = wide = seam_inside_a_part = 0
+    for CinP in range(CK, 2304 + CK + 1, CK):
         for Cin in sorted({CinP, CinP - 7, CinP - CK + 1}):         # full last chunk, padded ones
-            for C0 in range(1, Cin + 1):
+            # up to 1024 channels every seam; above, where nothing but the count changes, the seams on and next to the chunk boundaries
+            seams = range(1, Cin + 1) if CinP <= 1024 else sorted({Cin} | {c + d for c in range(CK, Cin, CK) for d in (-1, 0, 1)})
+            for C0 in seams:
                 C1 = Cin - C0
                 if not usable_k4(Cin, CinP, C0, C1):
+                    assert CinP <= 2304 or Cin > 2304
                     continue
                 admitted += 1
+                wide += CinP > 1024
                 nch = CinP // CK
+                assert Cin <= 2304 and CinP // 4 <= 1024
                 pp = parts(nch, 4)
                 owner = [0] * nch
                 for b, e in pp:
@@ -71,7 +80,8 @@ def test_every_admitted_layer_is_partitioned_soundly():
                     assert all((ch >= C0) == bool(src) for ch in (lo, hi - 1)), (Cin, C0, c)
                 if C1 and any(b * CK < C0 < e * CK for b, e in pp):
                     seam_inside_a_part += 1
-    assert admitted > 1000 and seam_inside_a_part > 100, (admitted, seam_inside_a_part)
+    print(f"{admitted} admitted (Cin, CinP, C0) layers, {wide} of them above 1024 channels; the seam inside a part {seam_inside_a_part} times")
+    assert admitted > 1000 and wide > 1000 and seam_inside_a_part > 100, (admitted, wide, seam_inside_a_part)
 
 
 def test_the_rule_refuses_what_it_must():
@@ -80,5 +90,10 @@ def test_the_rule_refuses_what_it_must():
     assert not usable_k4(288, 288, 288, 0)                  # 18 chunks: not divisible by 4
     assert not usable_k4(256, 256, 100, 156)                # the seam inside a chunk
     assert usable_k4(256, 256, 160, 96)                     # the seam inside a part (chunk 10 of 16), on a chunk boundary
-    assert not usable_k4(1040, 1040, 1040, 0)               # beyond the coefficient table
+    assert usable_k4(1088, 1088, 1088, 0)                   # 68 chunks, 272 channels per part: beyond the unsplit 8 x 8 table, inside a part's
+    assert not usable_k4(1040, 1040, 1040, 0)               # 65 chunks do not divide by 4
+    assert not usable_k4(2320, 2320, 2320, 0)               # 145 chunks, and above WINO_MAX_CIN_K4: the channel bound
+    assert usable_k4(2304, 2304, 2304, 0) and not usable_k4(2368, 2368, 2368, 0)          # 148 chunks divide by 4: the channel bound alone
     assert usable_k4(250, 256, 250, 0)                      # a padded last chunk
+    for plane in (8, 16):
+        assert usable_k4(2304, 2304, 1152, 1152, plane) and not wino_rule.admits("WINO2H", 2304, parts=8, plane=plane)

@@ -122,9 +122,11 @@ def test_every_kernel_id_has_a_statistics_case_or_a_reason():
 
 def test_expected_np_restates_the_launchers():
     src = lambda f: open(os.path.join(CSRC, "kernels", f)).read()
+    # the Winograd launchers end in one shared tail (conv_wino.cpp: wino_launch_done), each with its own geometry; the persistent kernel: regions only
+    assert "if (a.stats) set_last_conv_stats_np(g8 ? 1 : (a.H / 8) * (a.W / 16));" in src("conv_wino.cpp")
     for f in ("conv_wino.cpp", "conv_wino2h.cpp", "conv_wino3.cpp"):          # conv_wino2h.cpp: one launch chain for both piece counts
-        assert "set_last_conv_stats_np(G8 ? 1 : (a.H / 8) * (a.W / 16))" in src(f), f
-    assert "set_last_conv_stats_np((a.H / 8) * (a.W / 16))" in src("conv_wino3p.cpp")
+        assert "wino_launch_done(a, G8, ksp, s)" in src(f) and src(f).count("wino_launch_done(") == (2 if f == "conv_wino.cpp" else 1), f      # (conv_wino.cpp defines it)
+    assert "return wino_launch_done(a, false, ksp, s);" in src("conv_wino3p.cpp") and "set_last_conv_stats_np" not in src("conv_wino3p.cpp")
     assert src("conv1x1_dma.cpp").count("set_last_conv_stats_np(a.H * a.W / 32)") == 2
     assert "(HW >= Q1_PT || HW == 64)) set_last_conv_stats_np(HW >= Q1_PT ? HW / Q1_PT : 1)" in src("conv1x1_h2.cpp")
     assert re.search(r"constexpr int Q1_PT = 128;", src("conv1x1_h2.cpp"))

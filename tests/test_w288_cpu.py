@@ -8,7 +8,6 @@
   * The admission rule with the second constant: Cin <= (P >= 4 ? WINO_MAX_CIN_K4 = 2304 : WINO_MAX_CIN = 2048), the rest as before.
 """
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,15 +16,21 @@ import torch
 from oracle import sampler_ref, synth, unet_ref
 from tests import test_wide_conv_cpu as T
 from tests import w288_cases as W
+from tests import wino_rule
 
-WINO_MAX_CIN_K4 = 2304
+WINO_MAX_CIN_K4 = wino_rule.WINO_MAX_CIN_K4
 CK = T.CK
 
 
 def admitted(Cin, CinP, P):
-    """conv_wino3_usable's channel conditions (conv_wino2h, either piece count: the same, 4 parts at most; conv_wino: 2 parts at most)."""
+    """The bf16x3 family at 8 x 8 (the fp16 kernels, either piece count: the same, 4 parts at most; conv_wino.cpp: 2 parts at most)."""
+    return wino_rule.admits("WINO3", Cin, CinP, P, plane=8)
+
+
+def admitted_parent(Cin, CinP, P):
+    """The rule before the second constant, as the commit before this file's wrote it: the historical comparison."""
     nch = CinP // CK
-    return (Cin <= (WINO_MAX_CIN_K4 if P >= 4 else T.WINO_MAX_CIN) and CinP % CK == 0 and CinP // max(P, 1) <= T.WINO_TABLE_CH
+    return (Cin <= T.WINO_MAX_CIN and CinP % CK == 0 and CinP // max(P, 1) <= T.WINO_TABLE_CH
             and (P < 2 or (P in (2, 4, 8) and nch % P == 0 and nch >= 2 * P)))
 
 
@@ -77,24 +82,23 @@ def test_oracle_sampler_matches_reference_at_ngf_288(fixture):
 
 
 # ------------------------------------------------------------------------------------------------ the table, 2049 .. 2304 channels
-def test_common_h_holds_both_constants_and_the_predicates_name_the_new_one():
-    common = T._src("common.h")
-    assert re.search(r"constexpr int WINO_MAX_CIN = 2048;", common) and re.search(r"constexpr int WINO_TABLE_CH = 1024;", common)
-    assert re.search(r"constexpr int WINO_MAX_CIN_K4 = 2304;", common)
-    for f, fn in T.FAMILIES:
-        m = re.search(r"bool %s\(const ConvArgs& a\) \{(.*?)\n\}" % fn, T._src(os.path.join("kernels", f)), re.S)
-        assert m, (f, fn)
-        body = m.group(1)
-        assert "WINO_MAX_CIN_K4" in body and re.search(r"WINO_MAX_CIN\b(?!_)", body) and "WINO_TABLE_CH" in body, f"{fn} does not name both bounds"
-    assert [f for f, _ in T.FAMILIES[:2]] == ["conv_wino3.cpp", "conv_wino2h.cpp"]
-    for f, fn in T.FAMILIES[:2]:          # the families with a 4-way split (conv_wino2h.cpp: both piece counts) take the new bound from ksplit >= 4 on
-        assert "a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN)" in T._src(os.path.join("kernels", f)), f
-    # conv_wino.cpp splits two ways only: its bound stays WINO_MAX_CIN
-    assert "a.Cin <= WINO_MAX_CIN &&" in T._src(os.path.join("kernels", "conv_wino.cpp"))
+def test_every_family_takes_the_second_constant_where_it_has_four_parts():
+    assert wino_rule.header_constants()["WINO_MAX_CIN_K4"] == 2304 == WINO_MAX_CIN_K4 and T.WINO_MAX_CIN == 2048
+    for plane in (8, 16):
+        # the families with a 4-way split (the fp16 kernels: both piece counts) take the new bound from 4 parts on
+        for fam in ("WINO3", "WINO2H", "WINO1H"):
+            assert wino_rule.admits(fam, 2304, parts=4, plane=plane) and not wino_rule.admits(fam, 2320, parts=4, plane=plane), (fam, plane)
+            assert not wino_rule.admits(fam, 2304, parts=2, plane=plane) and not wino_rule.admits(fam, 2304, parts=1, plane=plane), (fam, plane)
+        assert wino_rule.admits("WINO3", 2304, parts=8, plane=plane) and not wino_rule.admits("WINO2H", 2304, parts=8, plane=plane)
+        # conv_wino.cpp splits two ways only: its bound stays WINO_MAX_CIN, whatever ksplit says
+        for ksplit in (0, 2, 4, 8):
+            assert not wino_rule.admits("WINO", 2304, parts=wino_rule.kernel_parts("WINO", ksplit), plane=plane)
+        assert wino_rule.admits("WINO", 2048, parts=2, plane=plane)
     # the persistent kernel and the SPADE-fused loader stay at WINO_TABLE_CH
-    assert re.search(r"bool conv_wino3p_usable.*?a\.Cin <= WINO_TABLE_CH", T._src(os.path.join("kernels", "conv_wino3p.cpp")), re.S)
-    assert "(a.gb == nullptr || a.Cin <= WINO_TABLE_CH)" in T._src(os.path.join("kernels", "conv_wino.cpp"))
-    assert "WINO_MAX_CIN_K4 = 2304" in T._src("conv_kernels.h")
+    for parts in (1, 2, 4, 8):
+        assert wino_rule.admits("WINO3P", 1024, parts=parts, plane=16) and not wino_rule.admits("WINO3P", 1152, parts=parts, plane=16)
+    assert wino_rule.admits("WINO", 1024, plane=16, spade=True) and not wino_rule.admits("WINO", 1040, plane=16, spade=True)
+    assert wino_rule.admits("WINO", 1040, plane=16) and not wino_rule.admits("WINO3", 512, plane=16, spade=True)
 
 
 def test_the_rule_with_the_second_constant():
@@ -110,7 +114,7 @@ def test_the_rule_with_the_second_constant():
     for CinP in range(CK, 2048 + 1, CK):
         for Cin in (CinP, CinP - 7):
             for P in (1, 2, 4, 8):
-                assert admitted(Cin, CinP, P) == T.admitted(Cin, CinP, P), (Cin, CinP, P)
+                assert admitted(Cin, CinP, P) == admitted_parent(Cin, CinP, P), (Cin, CinP, P)
     # and the 2-way split never takes more than WINO_MAX_CIN by the table rule alone
     assert all(not admitted(c, c, 2) for c in range(2064, 2400, CK))
 

@@ -8,30 +8,30 @@ second sample at offset PC).
     last chunk of the last part -- and parks entry tid + k * 512 when it is below PC;
   * reader:  patch slot (chunk ch, channel code cc, image img) reads entry min((ch - c_begin) * 16 + cc, PC - 1) + img * PC; the clamp keeps the
     look-ahead of the K loop (it activates a patch of chunk c_end that nobody reads) inside the table;
-  * usable(): Cin <= WINO_MAX_CIN = 2048 and CinP / max(P, 1) <= WINO_TABLE_CH = 1024 (two entries per thread and sample), next to the
-    conditions of the split itself (nch % P == 0, at least two chunks per part; three for the 4-way split of the fp16 kernels, which
-    tests/test_f16_ksplit4_cpu.py restates) and room for the partial results, which is the caller's buffer and not restated here.
+  * the rule (conv_kernels.h: wino_admits; tests/wino_rule.py restates it): at 8 x 8, where this walk asks, Cin <= WINO_MAX_CIN = 2048 and
+    CinP / max(P, 1) <= WINO_TABLE_CH = 1024 (two entries per thread and sample), next to the conditions of the split itself (nch % P == 0,
+    at least two chunks per part; three for the 4-way split of the fp16 kernels: tests/test_f16_ksplit4_cpu.py) and room for the partial
+    results, which is the caller's buffer and not walked here.
 """
 import os
 import re
 
 import numpy as np
 
+from tests import wino_rule
+
 CK = 16
 NT = 512
 LDS_MAX = 160 * 1024
-WINO_MAX_CIN = 2048
-WINO_TABLE_CH = 1024
+WINO_MAX_CIN = wino_rule.WINO_MAX_CIN
+WINO_TABLE_CH = wino_rule.WINO_TABLE_CH
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcvd_pytorch_amd", "csrc")
-FAMILIES = (("conv_wino3.cpp", "conv_wino3_usable"), ("conv_wino2h.cpp", "conv_wino2h_usable"),       # the first two: the families with a 4-way split
-            ("conv_wino.cpp", "conv_wino_usable"))
 
 
 def admitted(Cin, CinP, P):
-    nch = CinP // CK
-    return (Cin <= WINO_MAX_CIN and CinP % CK == 0 and CinP // max(P, 1) <= WINO_TABLE_CH
-            and (P < 2 or (P in (2, 4, 8) and nch % P == 0 and nch >= 2 * P)))
+    """The bf16x3 family at 8 x 8: one table of WINO_TABLE_CH entries per sample."""
+    return wino_rule.admits("WINO3", Cin, CinP, P, plane=8)
 
 
 def part_range(nch, P, kh):
@@ -80,16 +80,11 @@ def _src(name):
     return open(os.path.join(CSRC, name)).read()
 
 
-def test_the_constants_and_the_predicates_name_one_rule():
-    common = _src("common.h")
-    assert re.search(r"constexpr int WINO_MAX_CIN = 2048;", common) and re.search(r"constexpr int WINO_TABLE_CH = 1024;", common)
-    assert re.search(r"inline int wino_part_channels\(int CinP, int ksplit\) \{ return CinP / \(ksplit >= 2 \? ksplit : 1\); \}", common)
-    for f, fn in FAMILIES:
+def test_the_kernels_write_the_expressions_restated_here():
+    """(The rule itself is not read off the sources: tests/test_wino_rule_cpu.py compares tests/wino_rule.py with the header's table and cases.)"""
+    assert re.search(r"constexpr int wino_part_channels\(int CinP, int parts\) \{ return CinP / \(parts >= 2 \? parts : 1\); \}", _src("conv_kernels.h"))
+    for f in ("conv_wino3.cpp", "conv_wino2h.cpp", "conv_wino.cpp"):
         src = _src(os.path.join("kernels", f))
-        m = re.search(r"bool %s\(const ConvArgs& a\) \{(.*?)\n\}" % fn, src, re.S)
-        assert m, (f, fn)
-        body = m.group(1)
-        assert "WINO_MAX_CIN" in body and "WINO_TABLE_CH" in body and "wino_part_channels(a.CinP" in body, f"{fn} does not name the rule"
         assert not re.search(r"a\.Cin <= 1024", src), f"{f}: a bare 1024"
         assert "lds_bytes(a.Cin" not in src, f"{f}: the LDS size still takes all Cin channels"
     for f in ("conv_wino3.cpp", "conv_wino2h.cpp"):        # the expressions restated above, as the kernels write them
@@ -106,8 +101,9 @@ def test_the_constants_and_the_predicates_name_one_rule():
     src = _src(os.path.join("kernels", "conv_wino.cpp"))
     assert "min(CK * c_begin + tid, Cin - 1)" in src and "const int PC = (nch_all / ksp) * CK;" in src
     assert "min(((ch) - c_begin) * CK + (p_ci[sl] & (CK - 1)), PC - 1) + (G8 ? p_img[sl] * PC : 0)" in src
-    # the persistent kernel keeps whole-Cin tables and says so
-    assert re.search(r"bool conv_wino3p_usable.*?a\.Cin <= WINO_TABLE_CH", _src(os.path.join("kernels", "conv_wino3p.cpp")), re.S)
+    # the persistent kernel keeps whole-Cin tables: its LDS request takes Cin, and the rule holds Cin itself to the table
+    assert "wino3p_lds_bytes(a.Cin)" in _src(os.path.join("kernels", "conv_wino3p.cpp"))
+    assert not wino_rule.admits("WINO3P", 1040, plane=16) and not wino_rule.admits("WINO3P", 1040, parts=2, plane=16) and wino_rule.admits("WINO3P", 1024, plane=16)
 
 
 def _check_tables(Cin, CinP, P, g8):

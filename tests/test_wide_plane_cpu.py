@@ -9,11 +9,11 @@ The kernels (conv_wino3.cpp, conv_wino2h.cpp with two pieces or one: 512 threads
   * G8 (8 x 8, two samples per workgroup): PC <= WINO_TABLE_CH = 1024, two entries per thread and sample (conv_wino.cpp: one) -- four for two
     samples do not fit the LDS (tests/test_wide_conv_cpu.py::test_the_whole_cin_table_would_not_fit).
   * the reader is unchanged: entry min((ch - c_begin) * 16 + cc, PC - 1) (+ img * PC).
-  * usable(): Cin <= (P >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) and CinP / max(P, 1) <= (8 x 8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE), next to the
-    conditions of the split itself.
+  * the rule (conv_kernels.h: wino_admits; tests/wino_rule.py): Cin <= (P >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN) and
+    CinP / max(P, 1) <= (8 x 8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE), next to the conditions of the split itself.
 
 The 2-way split at 2304 channels: a part of 1152 channels fits a plane's table, but `Cin <= WINO_MAX_CIN` for splits of fewer than four parts is
-part of the rule and stays (tests/test_w288_cpu.py asserts the expression in the sources; model.cpp sizes and offers by it), so (2304, P = 2) is
+part of the rule and stays (conv_kernels.h asserts the case; model.cpp sizes and offers by it), so (2304, P = 2) is
 refused on every plane -- by the channel bound, no longer by the table.  test_the_rule_refuses_and_admits_what_it_must says so.
 """
 import os
@@ -22,13 +22,14 @@ import re
 import numpy as np
 
 from tests import test_wide_conv_cpu as T
+from tests import wino_rule
 
 CK = T.CK
 LDS_MAX = T.LDS_MAX
 WINO_MAX_CIN = T.WINO_MAX_CIN
-WINO_MAX_CIN_K4 = 2304
+WINO_MAX_CIN_K4 = wino_rule.WINO_MAX_CIN_K4
 WINO_TABLE_CH = T.WINO_TABLE_CH
-WINO_TABLE_CH_PLANE = 2048
+WINO_TABLE_CH_PLANE = wino_rule.WINO_TABLE_CH_PLANE
 # (threads, table entries per thread and sample: regions of a plane, G8, K parts the family has)
 FAMILY_512 = dict(NT=512, NE=4, NE_G8=2, parts=(1, 2, 4, 8))          # conv_wino3.cpp; conv_wino2h.cpp: parts up to 4
 FAMILY_1024 = dict(NT=1024, NE=2, NE_G8=1, parts=(1, 2))              # conv_wino.cpp
@@ -39,10 +40,8 @@ def table_ch(g8):
 
 
 def admitted(Cin, CinP, P, g8):
-    """conv_wino3_usable's channel conditions (conv_wino2h: the same, 4 parts at most; conv_wino: 2 parts at most)."""
-    nch = CinP // CK
-    return (Cin <= (WINO_MAX_CIN_K4 if P >= 4 else WINO_MAX_CIN) and CinP % CK == 0 and CinP // max(P, 1) <= table_ch(g8)
-            and (P < 2 or (P in (2, 4, 8) and nch % P == 0 and nch >= 2 * P)))
+    """The bf16x3 family at 8 x 8 or on a 16 x 16 plane (the fp16 kernels: the same, 4 parts at most; conv_wino.cpp: 2 parts at most)."""
+    return wino_rule.admits("WINO3", Cin, CinP, P, plane=8 if g8 else 16)
 
 
 def admitted_parent(Cin, CinP, P):
@@ -150,28 +149,17 @@ def test_lds_requests_at_the_widest_plane_table():
     assert T.lds_wino3(2048, True) > LDS_MAX                             # why 8 x 8 keeps the smaller table
 
 
-def _body(f, fn):
-    m = re.search(r"bool %s\(const ConvArgs& a\) \{(.*?)\n\}" % fn, T._src(os.path.join("kernels", f)), re.S)
-    assert m, (f, fn)
-    return m.group(1)
-
-
-def test_the_new_constant_and_the_predicates_name_one_rule():
-    common = T._src("common.h")
-    assert re.search(r"constexpr int WINO_TABLE_CH = 1024;", common) and re.search(r"constexpr int WINO_TABLE_CH_PLANE = 2048;", common)
-    assert "inline int wino_table_ch(bool g8) { return g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE; }" in common
-    for f, fn in T.FAMILIES[:2]:
-        body = _body(f, fn)
-        assert "const bool g8 = a.H == 8 && a.W == 8;" in body, fn
-        assert "wino_part_channels(a.CinP, a.ksplit) <= (g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE)" in body, fn
-        assert "a.Cin <= (a.ksplit >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN)" in body, fn
-    body = _body(*T.FAMILIES[2])
-    assert "const int pc = wino_part_channels(a.CinP, a.ksplit == 2 ? 2 : 1);" in body
-    assert "pc <= (g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE)" in body and "a.Cin <= WINO_MAX_CIN &&" in body
-    assert "(a.gb == nullptr || a.Cin <= WINO_TABLE_CH)" in body                      # the SPADE-fused loader stays
-    assert re.search(r"bool conv_wino3p_usable.*?a\.Cin <= WINO_TABLE_CH &&", T._src(os.path.join("kernels", "conv_wino3p.cpp")), re.S)
+def test_every_family_parks_by_the_two_table_sizes():
+    assert wino_rule.header_constants()["WINO_TABLE_CH_PLANE"] == 2048 == 2 * WINO_TABLE_CH
+    for fam in ("WINO3", "WINO2H", "WINO1H", "WINO"):
+        assert wino_rule.admits(fam, 2048, plane=16) and wino_rule.admits(fam, 1040, plane=32) and not wino_rule.admits(fam, 2064, plane=16), fam
+        assert wino_rule.admits(fam, 1024, plane=8) and not wino_rule.admits(fam, 1040, plane=8), fam
+        assert wino_rule.admits(fam, 2048, parts=2, plane=8) and wino_rule.admits(fam, 2048, parts=2, plane=16), fam
+    # conv_wino.cpp makes an unsplit launch of every ksplit but 2: its part is then all of CinP
+    assert wino_rule.kernel_parts("WINO", 4) == 1 and not wino_rule.admits("WINO", 2048, parts=wino_rule.kernel_parts("WINO", 4), plane=8)
+    assert wino_rule.admits("WINO", 1040, plane=16) and not wino_rule.admits("WINO", 1040, plane=16, spade=True)      # the SPADE-fused loader stays
+    assert not wino_rule.admits("WINO3P", 1040, plane=16) and not wino_rule.admits("WINO3P", 1040, parts=2, plane=16)   # and so does the persistent kernel
     assert "WINO_TABLE_CH_PLANE" not in T._src(os.path.join("kernels", "conv_wino3p.cpp"))
-    assert "WINO_TABLE_CH_PLANE = 2048" in T._src("conv_kernels.h")
 
 
 def test_the_kernels_fill_the_table_as_restated():
