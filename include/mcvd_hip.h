@@ -351,6 +351,35 @@ int mcvd_fpndm_run(mcvd_model* m, float* x_inout, const float* cond, int subsamp
  * reference computes: x0 = c_x0a*(x - c_x0b*eps); clip; x = c_mean0*x0 + c_mean1*(ddpm: x | ddim: eps) + c_noise*z. */
 int mcvd_sampler_update(mcvd_ctx* ctx, int kind, float* x_inout, const float* eps, const float* noise, float c_x0a,
                         float c_x0b, float c_mean0, float c_mean1, float c_noise, int clip, int64_t n);
+/* ---- classifier-free guidance ------------------------------------------------------- */
+/* A guided evaluation is ONE forward at 2B rows: rows [0, B) carry (x, cond), rows [B, 2B) carry (x, cond_weak), and for a cond_emb net
+ * cond_mask = 1 | weak_mask.  Per element, in fp32, one rounding per operation, no fma (as torch evaluates e_c + (s - 1) * (e_c - e_u)):
+ *     d = e_c - e_u;   e = e_c + w * d;        w = (float)(guidance_scale - 1)
+ * so guidance_scale 1 gives e_c bit for bit.  cond_weak: [B, C*(nc + future), S, S], NULL = zeros.  Noise belongs to the B rows of the
+ * call: a seeded row b is keyed (seed, sample_offset + b, draw), as in an unguided call.  The [2B] input, conditioning and epsilon
+ * buffers are allocated by the first guided call at that B; the 2B-row forward has the tuning table and the captured graph of batch 2B,
+ * and the f16x2 / f16x1 range guard scans all 2B rows.  MCVD_EINVAL for a net without conditioning frames, a noise_in_cond net and
+ * MCVD_FLAG_GAMMA. */
+/* mcvd_sampler_run with every network evaluation (each step and the denoise pass) guided. */
+int mcvd_sampler_run_guided(mcvd_model* m, int kind, float* x_inout, const float* cond, const float* cond_weak, double guidance_scale,
+                            int weak_mask, const float* noise, uint64_t seed, uint64_t sample_offset, int subsample_steps, int flags,
+                            double t_min, int B);
+/* mcvd_fpndm_run with every network evaluation (the four of a Runge-Kutta step, float midpoint labels included) guided. */
+int mcvd_fpndm_run_guided(mcvd_model* m, float* x_inout, const float* cond, const float* cond_weak, double guidance_scale, int weak_mask,
+                          int subsample_steps, int flags, int B);
+/* One guided evaluation: eps_out:[B, C*nf, S, S] = e for x:[B, ...], labels int64 [B] (the _ft form: float timesteps [B]). */
+int mcvd_unet_forward_guided(mcvd_model* m, const float* x, const int64_t* labels, const float* cond, const float* cond_weak,
+                             double guidance_scale, int weak_mask, float* eps_out, int B);
+int mcvd_unet_forward_guided_ft(mcvd_model* m, const float* x, const float* t, const float* cond, const float* cond_weak,
+                                double guidance_scale, int weak_mask, float* eps_out, int B);
+/* mcvd_sampler_update on e: eps2 = [e_c | e_u], two blocks of n floats; x_inout holds n floats; x_dup = NULL, or 2n floats that receive
+ * the new x twice (the [2B] network input) in the same pass.  z: `noise` (n floats), or with use_philox the stream of mcvd_randn for
+ * (seed, sample_offset + row, draw), row = element / per_sample of the n-float tensor (never of the 2n-float one). */
+int mcvd_sampler_update_guided(mcvd_ctx* ctx, int kind, float* x_inout, float* x_dup, const float* eps2, const float* noise, float w,
+                               float c_x0a, float c_x0b, float c_mean0, float c_mean1, float c_noise, int clip, int64_t n,
+                               int use_philox, uint64_t seed, uint64_t sample_offset, uint64_t draw, int64_t per_sample);
+/* eps_out[i] = e for i < n (n a multiple of 4); eps_out may alias eps_c. */
+int mcvd_guidance_combine(mcvd_ctx* ctx, float* eps_out, const float* eps_c, const float* eps_u, float w, int64_t n);
 /* z ~ N(0,1) from the same Philox stream mcvd_sampler_run uses: out:[B, per_sample], per_sample a multiple of 4.  Row b is keyed by
  * (seed, sample_offset + b, draw), its float4 i by counter i.  The high word of the sample index shares a counter word with bits 24.. of
  * the draw word: (sample + 2^32, draw) and (sample, draw ^ 2^24) are the same stream, so global sample indices must stay below 2^32. */

@@ -84,6 +84,12 @@ _PROTOS = {
     "mcvd_sampler_run": (_i, [_vp, _i, _vp, _vp, _vp, _u64, _u64, _i, _i, C.c_double, _i]),
     "mcvd_fpndm_run": (_i, [_vp, _vp, _vp, _i, _i, _i]),
     "mcvd_sampler_update": (_i, [_vp, _i, _vp, _vp, _vp, _f, _f, _f, _f, _f, _i, _i64]),
+    "mcvd_sampler_run_guided": (_i, [_vp, _i, _vp, _vp, _vp, C.c_double, _i, _vp, _u64, _u64, _i, _i, C.c_double, _i]),
+    "mcvd_fpndm_run_guided": (_i, [_vp, _vp, _vp, _vp, C.c_double, _i, _i, _i, _i]),
+    "mcvd_unet_forward_guided": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _i]),
+    "mcvd_unet_forward_guided_ft": (_i, [_vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp, _i]),
+    "mcvd_sampler_update_guided": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _f, _f, _i, _i64, _i, _u64, _u64, _u64, _i64]),
+    "mcvd_guidance_combine": (_i, [_vp, _vp, _vp, _vp, _f, _i64]),
     "mcvd_randn": (_i, [_vp, _vp, _u64, _u64, _u64, _i, _i64]),
     "mcvd_pack_frames_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "mcvd_frame_metrics": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),

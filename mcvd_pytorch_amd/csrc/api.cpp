@@ -499,6 +499,9 @@ void mcvd_model_destroy(mcvd_model* m) {
     if (m->temb_tmp) (void)hipFree(m->temb_tmp);
     if (m->temb_lab) (void)hipFree(m->temb_lab);
     if (m->fp_buf) (void)hipFree(m->fp_buf);
+    if (m->gd_x) (void)hipFree(m->gd_x);
+    if (m->gd_cond) (void)hipFree(m->gd_cond);
+    if (m->gd_mask) (void)hipFree(m->gd_mask);
     if (m->alphas_dev) (void)hipFree(m->alphas_dev);
     if (m->cond_z) (void)hipFree(m->cond_z);
     if (m->noise_buf) (void)hipFree(m->noise_buf);
@@ -900,9 +903,42 @@ int mcvd_model_module_output(mcvd_model* m, int module, int B, float* dst, int64
 }
 
 // ------------------------------------------------------------------------------------------------ sampler
-int mcvd_sampler_run(mcvd_model* m, int kind, float* x, const float* cond, const float* noise, uint64_t seed,
-                     uint64_t sample_offset, int subsample_steps, int flags, double t_min, int B) {
-    API_TRY
+// Classifier-free guidance of one call (include/mcvd_hip.h): the weak conditioning, w = float32(s - 1), the cond_emb mask of the weak rows.
+struct GuidedCall {
+    const float* cond_weak;
+    float w;
+    int weak_mask;
+};
+
+// What a guided call needs before its first forward: the workspace and tuning of batch 2B, the [2B] buffers, gd_cond = [cond ; cond_weak].
+static int guided_begin(mcvd_model* m, const char* who, const float* cond, const GuidedCall& g, int B) {
+    MCVD_REQUIRE(m->d.num_frames_cond > 0 && cond, "%s: guidance needs a net with conditioning frames (and its cond)", who);
+    MCVD_REQUIRE(!m->d.noise_in_cond, "%s: guidance on a noise_in_cond net is not defined (two z per evaluation)", who);
+    MCVD_REQUIRE(B <= (1 << 29), "%s: B = %d", who, B);
+    if (int rc = m->prepare_B(2 * B)) return rc;
+    if (int rc = m->ensure_guided(B, g.weak_mask)) return rc;
+    const size_t cbytes = (size_t)B * m->d.channels * m->d.num_frames_cond * m->d.image_size * m->d.image_size * sizeof(float);
+    hipStream_t s = m->ctx->stream;
+    MCVD_HIP_CHECK(hipMemcpyAsync(m->gd_cond, cond, cbytes, hipMemcpyDeviceToDevice, s));
+    char* weak = reinterpret_cast<char*>(m->gd_cond) + cbytes;
+    if (g.cond_weak) MCVD_HIP_CHECK(hipMemcpyAsync(weak, g.cond_weak, cbytes, hipMemcpyDeviceToDevice, s));
+    else MCVD_HIP_CHECK(hipMemsetAsync(weak, 0, cbytes, s));
+    m->cond_cache_valid = false;          // SPADE maps of whatever gd_cond held before
+    return 0;
+}
+
+// gd_x = [x ; x]   (n floats each)
+static int guided_dup_x(mcvd_model* m, const float* x, int64_t n) {
+    hipStream_t s = m->ctx->stream;
+    MCVD_HIP_CHECK(hipMemcpyAsync(m->gd_x, x, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    MCVD_HIP_CHECK(hipMemcpyAsync(m->gd_x + n, x, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// mcvd_sampler_run (g == NULL) and mcvd_sampler_run_guided: one loop.  A guided call forwards FB = 2B rows from gd_x / gd_cond into eps_buf
+// and its elementwise kernels combine the two halves; everything else -- schedule, labels, draws, coefficients -- is the B-row call's.
+static int sampler_run_impl(mcvd_model* m, int kind, float* x, const float* cond, const float* noise, uint64_t seed,
+                            uint64_t sample_offset, int subsample_steps, int flags, double t_min, int B, const GuidedCall* g) {
     MCVD_REQUIRE(m && x && B > 0, "sampler_run: bad arguments");
     MCVD_REQUIRE(kind == MCVD_SAMPLER_DDPM || kind == MCVD_SAMPLER_DDIM, "sampler_run: kind %d", kind);
     MCVD_REQUIRE(m->finalized, "sampler_run before mcvd_model_finalize");
@@ -927,9 +963,20 @@ int mcvd_sampler_run(mcvd_model* m, int kind, float* x, const float* cond, const
     const int L = (int)steps.size();
     const int64_t per = (int64_t)m->d.channels * m->d.num_frames * m->d.image_size * m->d.image_size;
     const int64_t n = per * B;
-    if (int rc = m->prepare_B(B)) return rc;
-    if (int rc = m->prepare_cond(cond, B)) return rc;      // SPADE: gamma/beta once per sampler call (cond is constant)
-    struct CacheGuard { mcvd_model* m; ~CacheGuard() { m->cond_cache_valid = false; } } guard{m};
+    const int FB = g ? 2 * B : B;                          // rows of every forward of this call
+    const float* xin = x;                                  // what the network reads
+    if (g) {
+        MCVD_REQUIRE(!(flags & MCVD_FLAG_GAMMA), "sampler_run_guided: MCVD_FLAG_GAMMA with guidance is not served");
+        if (int rc = guided_begin(m, "sampler_run_guided", cond, *g, B)) return rc;
+        if (int rc = guided_dup_x(m, x, n)) return rc;
+        cond = m->gd_cond;
+        xin = m->gd_x;
+    }
+    if (int rc = m->prepare_B(FB)) return rc;
+    if (int rc = m->prepare_cond(cond, FB)) return rc;     // SPADE: gamma/beta once per sampler call (cond is constant)
+    struct CacheGuard { mcvd_model* m; ~CacheGuard() { m->cond_cache_valid = false; m->cond_mask = nullptr; } } guard{m};
+    if (g && m->d.cond_emb) m->cond_mask = m->gd_mask;     // rows [0, B) ones, rows [B, 2B) weak_mask
+    const float* eps_u = m->eps_buf + n;                   // guided: the weak half of the [2B] epsilon
     hipStream_t s = m->ctx->stream;
     m->profile_armed = true;          // with option "profile": the first forward of this call is event-instrumented
     const bool gam = (flags & MCVD_FLAG_GAMMA) != 0;
@@ -986,8 +1033,12 @@ int mcvd_sampler_run(mcvd_model* m, int kind, float* x, const float* cond, const
             if (gam) {
                 if (int rc = gamma_draw(i)) return rc;
             }
-            if (int rc = launch_renoise(x, gam ? m->noise_buf : (noise ? noise + draw * n : nullptr), sqrtf(a), sqrtf(1.0f - a), n,
-                                        use_philox, seed, sample_offset, draw, per, s))
+            if (g) {
+                if (int rc = launch_renoise_dup(x, m->gd_x, noise ? noise + draw * n : nullptr, sqrtf(a), sqrtf(1.0f - a), n, use_philox,
+                                                seed, sample_offset, draw, per, s))
+                    return rc;
+            } else if (int rc = launch_renoise(x, gam ? m->noise_buf : (noise ? noise + draw * n : nullptr), sqrtf(a), sqrtf(1.0f - a), n,
+                                               use_philox, seed, sample_offset, draw, per, s))
                 return rc;
             ++draw;
         }
@@ -995,11 +1046,11 @@ int mcvd_sampler_run(mcvd_model* m, int kind, float* x, const float* cond, const
         // :283 (with the call's embedding table live nothing but a noise_in_cond net reads the labels: the fill is skipped)
         const bool need_labels = !m->temb_row_live || m->d.noise_in_cond;
         if (need_labels)
-            if (int rc = launch_fill_labels(m->labels, steps[i], B, s)) return rc;
+            if (int rc = launch_fill_labels(m->labels, steps[i], FB, s)) return rc;
         set_cond_gamma(steps[i]);
         if (m->temb_row_live)
-            if (int rc = m->use_temb_row(fwd_no++, B)) return rc;
-        if (int rc = m->forward(x, m->labels, cond, m->eps_buf, B)) return rc;           // :284
+            if (int rc = m->use_temb_row(fwd_no++, FB)) return rc;
+        if (int rc = m->forward(xin, m->labels, cond, m->eps_buf, FB)) return rc;        // :284
         const float c_x0a = 1.0f / sqrtf(a), c_x0b = sqrtf(1.0f - a);                    // :287
         float c0, c1, cn = 0.0f;
         if (kind == MCVD_SAMPLER_DDPM) {
@@ -1015,22 +1066,45 @@ int mcvd_sampler_run(mcvd_model* m, int kind, float* x, const float* cond, const
         if (draws && gam)
             if (int rc = gamma_draw(i)) return rc;
         const float* zsrc = !draws ? nullptr : (gam ? m->noise_buf : (noise ? noise + draw * n : nullptr));
-        if (int rc = launch_sampler_update(kind, x, m->eps_buf, zsrc, c_x0a, c_x0b, c0,
-                                           c1, cn, (flags & MCVD_FLAG_CLIP_BEFORE) ? 1 : 0, n, (draws && use_philox) ? 1 : 0,
-                                           seed, sample_offset, draw, per, s))
+        if (g) {
+            if (int rc = launch_sampler_update_guided(kind, x, m->gd_x, m->eps_buf, eps_u, zsrc, g->w, c_x0a, c_x0b, c0, c1, cn,
+                                                      (flags & MCVD_FLAG_CLIP_BEFORE) ? 1 : 0, n, (draws && use_philox) ? 1 : 0, seed,
+                                                      sample_offset, draw, per, s))
+                return rc;
+        } else if (int rc = launch_sampler_update(kind, x, m->eps_buf, zsrc, c_x0a, c_x0b, c0,
+                                                  c1, cn, (flags & MCVD_FLAG_CLIP_BEFORE) ? 1 : 0, n, (draws && use_philox) ? 1 : 0,
+                                                  seed, sample_offset, draw, per, s))
             return rc;
         if (draws) ++draw;
     }
     if (flags & MCVD_FLAG_DENOISE) {                                                      // :331-333, label L-1 (sic)
         if (!m->temb_row_live || m->d.noise_in_cond)
-            if (int rc = launch_fill_labels(m->labels, L - 1, B, s)) return rc;
+            if (int rc = launch_fill_labels(m->labels, L - 1, FB, s)) return rc;
         set_cond_gamma(L - 1);
         if (m->temb_row_live)
-            if (int rc = m->use_temb_row(fwd_no++, B)) return rc;
-        if (int rc = m->forward(x, m->labels, cond, m->eps_buf, B)) return rc;
-        if (int rc = launch_axpy_out(x, m->eps_buf, sqrtf(1.0f - al[L - 1]), n, s)) return rc;
+            if (int rc = m->use_temb_row(fwd_no++, FB)) return rc;
+        if (int rc = m->forward(xin, m->labels, cond, m->eps_buf, FB)) return rc;
+        if (g) {
+            if (int rc = launch_axpy_out_guided(x, m->eps_buf, eps_u, g->w, sqrtf(1.0f - al[L - 1]), n, s)) return rc;
+        } else if (int rc = launch_axpy_out(x, m->eps_buf, sqrtf(1.0f - al[L - 1]), n, s)) return rc;
     }
     return (m->ctx->f16x2 || m->ctx->f16x1) ? mcvd_ctx_check_range(m->ctx) : 0;      // f16x2 / f16x1 range guard: a non-finite epsilon anywhere in the loop is an error
+}
+
+int mcvd_sampler_run(mcvd_model* m, int kind, float* x, const float* cond, const float* noise, uint64_t seed,
+                     uint64_t sample_offset, int subsample_steps, int flags, double t_min, int B) {
+    API_TRY
+    return sampler_run_impl(m, kind, x, cond, noise, seed, sample_offset, subsample_steps, flags, t_min, B, nullptr);
+    API_CATCH
+}
+
+int mcvd_sampler_run_guided(mcvd_model* m, int kind, float* x, const float* cond, const float* cond_weak, double guidance_scale,
+                            int weak_mask, const float* noise, uint64_t seed, uint64_t sample_offset, int subsample_steps, int flags,
+                            double t_min, int B) {
+    API_TRY
+    MCVD_REQUIRE(weak_mask == 0 || weak_mask == 1, "sampler_run_guided: weak_mask %d", weak_mask);
+    const GuidedCall g{cond_weak, (float)(guidance_scale - 1.0), weak_mask};
+    return sampler_run_impl(m, kind, x, cond, noise, seed, sample_offset, subsample_steps, flags, t_min, B, &g);
     API_CATCH
 }
 
@@ -1038,8 +1112,9 @@ int mcvd_sampler_run(mcvd_model* m, int kind, float* x, const float* cond, const
 // t_next = the previous step (-1 first), alpha table = flipped alphas indexed by t + 1, network label = t, Runge-Kutta for the first
 // three steps (4 evaluations, midpoint label (t + t_next) / 2 as a float), 4th-order Adams-Bashforth afterwards.  The scalar
 // coefficients are evaluated in fp32, operation by operation, as torch evaluates the reference's 0-dim tensor expressions.
-int mcvd_fpndm_run(mcvd_model* m, float* x, const float* cond, int subsample_steps, int flags, int B) {
-    API_TRY
+// mcvd_fpndm_run (g == NULL) and mcvd_fpndm_run_guided.  A guided evaluation copies its input into both halves of gd_x, forwards 2B rows
+// into eps_buf and combines the halves into the B-row estimate the loop asked for; the combinations and transfers are the B-row ones.
+static int fpndm_run_impl(mcvd_model* m, float* x, const float* cond, int subsample_steps, int flags, int B, const GuidedCall* g) {
     MCVD_REQUIRE(m && x && B > 0, "fpndm_run: bad arguments");
     MCVD_REQUIRE(m->finalized, "fpndm_run before mcvd_model_finalize");
     if (int rc = mcvd_ctx_clear_range(m->ctx)) return rc;
@@ -1047,9 +1122,15 @@ int mcvd_fpndm_run(mcvd_model* m, float* x, const float* cond, int subsample_ste
     MCVD_REQUIRE(subsample_steps > 0 && subsample_steps <= T, "fpndm_run: subsample_steps=%d (the reference divides by it)", subsample_steps);
     const int64_t per = (int64_t)m->d.channels * m->d.num_frames * m->d.image_size * m->d.image_size;
     const int64_t n = per * B;
-    if (int rc = m->prepare_B(B)) return rc;
-    if (int rc = m->prepare_cond(cond, B)) return rc;
-    struct CacheGuard { mcvd_model* m; ~CacheGuard() { m->cond_cache_valid = false; m->uniform_labels = 0; } } guard{m};
+    const int FB = g ? 2 * B : B;
+    if (g) {
+        if (int rc = guided_begin(m, "fpndm_run_guided", cond, *g, B)) return rc;
+        cond = m->gd_cond;
+    }
+    if (int rc = m->prepare_B(FB)) return rc;
+    if (int rc = m->prepare_cond(cond, FB)) return rc;
+    struct CacheGuard { mcvd_model* m; ~CacheGuard() { m->cond_cache_valid = false; m->uniform_labels = 0; m->cond_mask = nullptr; } } guard{m};
+    if (g && m->d.cond_emb) m->cond_mask = m->gd_mask;
     m->uniform_labels = 1;
     hipStream_t s = m->ctx->stream;
     if (m->fp_B < B) {
@@ -1073,16 +1154,23 @@ int mcvd_fpndm_run(mcvd_model* m, float* x, const float* cond, int subsample_ste
         const float c2 = 1.0f / (sa * (sqrtf((1.0f - an) * at) + sqrtf((1.0f - at) * an)));
         return launch_pndm_transfer(out, xx, et, d, c1, c2, clip, n, s);
     };
+    auto combine = [&](float* out) -> int { return launch_guidance_combine(out, m->eps_buf, m->eps_buf + n, g->w, n, s); };
     auto model_i = [&](const float* xx, int t, float* out) -> int {
-        if (int rc = launch_fill_labels(m->labels, t, B, s)) return rc;
-        return m->forward(xx, m->labels, cond, out, B);
+        if (int rc = launch_fill_labels(m->labels, t, FB, s)) return rc;
+        if (!g) return m->forward(xx, m->labels, cond, out, B);
+        if (int rc = guided_dup_x(m, xx, n)) return rc;
+        if (int rc = m->forward(m->gd_x, m->labels, cond, m->eps_buf, FB)) return rc;
+        return combine(out);
     };
     auto model_f = [&](const float* xx, float t, float* out) -> int {
-        if (int rc = launch_fill_labels_f(m->labels_f, t, B, s)) return rc;
+        if (int rc = launch_fill_labels_f(m->labels_f, t, FB, s)) return rc;
+        if (g)
+            if (int rc = guided_dup_x(m, xx, n)) return rc;
         m->labels_f32 = 1;
-        const int rc = m->forward(xx, m->labels_f, cond, out, B);
+        const int rc = g ? m->forward(m->gd_x, m->labels_f, cond, m->eps_buf, FB) : m->forward(xx, m->labels_f, cond, out, B);
         m->labels_f32 = 0;
-        return rc;
+        if (rc || !g) return rc;
+        return combine(out);
     };
     int n_ets = 0;
     int t_prev = -1;
@@ -1120,7 +1208,75 @@ int mcvd_fpndm_run(mcvd_model* m, float* x, const float* cond, int subsample_ste
         t_prev = t;
     }
     return (m->ctx->f16x2 || m->ctx->f16x1) ? mcvd_ctx_check_range(m->ctx) : 0;      // f16x2 / f16x1 range guard
+}
+
+int mcvd_fpndm_run(mcvd_model* m, float* x, const float* cond, int subsample_steps, int flags, int B) {
+    API_TRY
+    return fpndm_run_impl(m, x, cond, subsample_steps, flags, B, nullptr);
     API_CATCH
+}
+
+int mcvd_fpndm_run_guided(mcvd_model* m, float* x, const float* cond, const float* cond_weak, double guidance_scale, int weak_mask,
+                          int subsample_steps, int flags, int B) {
+    API_TRY
+    MCVD_REQUIRE(weak_mask == 0 || weak_mask == 1, "fpndm_run_guided: weak_mask %d", weak_mask);
+    const GuidedCall g{cond_weak, (float)(guidance_scale - 1.0), weak_mask};
+    return fpndm_run_impl(m, x, cond, subsample_steps, flags, B, &g);
+    API_CATCH
+}
+
+// One guided evaluation for the host loops: [x ; x], [labels ; labels] and [cond ; cond_weak] are assembled for this forward alone.
+static int forward_guided(mcvd_model* m, const float* x, const void* lab, int float_t, const float* cond, const float* cond_weak,
+                          double guidance_scale, int weak_mask, float* eps_out, int B) {
+    MCVD_REQUIRE(m && x && lab && eps_out && B > 0, "forward_guided: bad arguments");
+    MCVD_REQUIRE(m->finalized, "forward_guided before mcvd_model_finalize");
+    MCVD_REQUIRE(weak_mask == 0 || weak_mask == 1, "forward_guided: weak_mask %d", weak_mask);
+    const GuidedCall g{cond_weak, (float)(guidance_scale - 1.0), weak_mask};
+    if (int rc = guided_begin(m, "forward_guided", cond, g, B)) return rc;
+    const int64_t n = (int64_t)B * m->d.channels * m->d.num_frames * m->d.image_size * m->d.image_size;
+    if (int rc = guided_dup_x(m, x, n)) return rc;
+    hipStream_t s = m->ctx->stream;
+    const size_t lbytes = (size_t)B * (float_t ? sizeof(float) : sizeof(int64_t));
+    char* lab2 = float_t ? reinterpret_cast<char*>(m->labels_f) : reinterpret_cast<char*>(m->labels);
+    MCVD_HIP_CHECK(hipMemcpyAsync(lab2, lab, lbytes, hipMemcpyDeviceToDevice, s));
+    MCVD_HIP_CHECK(hipMemcpyAsync(lab2 + lbytes, lab, lbytes, hipMemcpyDeviceToDevice, s));
+    if (m->d.cond_emb) m->cond_mask = m->gd_mask;
+    m->labels_f32 = float_t;
+    const int rc = m->forward(m->gd_x, lab2, m->gd_cond, m->eps_buf, 2 * B);
+    m->labels_f32 = 0;
+    m->cond_mask = nullptr;
+    m->cond_cache_valid = false;
+    if (rc) return rc;
+    return launch_guidance_combine(eps_out, m->eps_buf, m->eps_buf + n, g.w, n, s);
+}
+
+int mcvd_unet_forward_guided(mcvd_model* m, const float* x, const int64_t* labels, const float* cond, const float* cond_weak,
+                             double guidance_scale, int weak_mask, float* eps_out, int B) {
+    API_TRY
+    return forward_guided(m, x, labels, 0, cond, cond_weak, guidance_scale, weak_mask, eps_out, B);
+    API_CATCH
+}
+
+int mcvd_unet_forward_guided_ft(mcvd_model* m, const float* x, const float* t, const float* cond, const float* cond_weak,
+                                double guidance_scale, int weak_mask, float* eps_out, int B) {
+    API_TRY
+    return forward_guided(m, x, t, 1, cond, cond_weak, guidance_scale, weak_mask, eps_out, B);
+    API_CATCH
+}
+
+int mcvd_sampler_update_guided(mcvd_ctx* ctx, int kind, float* x, float* x_dup, const float* eps2, const float* noise, float w, float c_x0a,
+                               float c_x0b, float c_mean0, float c_mean1, float c_noise, int clip, int64_t n, int use_philox,
+                               uint64_t seed, uint64_t sample_offset, uint64_t draw, int64_t per_sample) {
+    MCVD_REQUIRE(ctx && x && eps2 && n > 0, "sampler_update_guided: bad arguments");
+    MCVD_REQUIRE(kind == MCVD_SAMPLER_DDPM || kind == MCVD_SAMPLER_DDIM, "sampler_update_guided: kind %d", kind);
+    MCVD_REQUIRE(!use_philox || (per_sample > 0 && n % per_sample == 0), "sampler_update_guided: n is not a whole number of rows");
+    return launch_sampler_update_guided(kind, x, x_dup, eps2, eps2 + n, noise, w, c_x0a, c_x0b, c_mean0, c_mean1, c_noise, clip, n,
+                                        use_philox ? 1 : 0, seed, sample_offset, draw, use_philox ? per_sample : 4, ctx->stream);
+}
+
+int mcvd_guidance_combine(mcvd_ctx* ctx, float* eps_out, const float* eps_c, const float* eps_u, float w, int64_t n) {
+    MCVD_REQUIRE(ctx && n > 0, "guidance_combine: bad arguments");
+    return launch_guidance_combine(eps_out, eps_c, eps_u, w, n, ctx->stream);
 }
 
 int mcvd_sampler_update(mcvd_ctx* ctx, int kind, float* x, const float* eps, const float* noise, float c_x0a, float c_x0b,

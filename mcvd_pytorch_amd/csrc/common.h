@@ -268,6 +268,16 @@ int launch_sampler_update(int kind, float* x, const float* eps, const float* noi
 int launch_renoise(float* x, const float* noise, float ca, float cb, int64_t n, int use_philox, uint64_t seed,
                    uint64_t sample_offset, uint64_t draw, int64_t per_sample, hipStream_t s);
 int launch_axpy_out(float* x, const float* eps, float c, int64_t n, hipStream_t s);   // x -= c * eps
+// classifier-free guidance (kernels/sampler.cpp): e = e_c + w (e_c - e_u), one rounding per operation, then the chain of the unguided
+// kernel of the same name; n / per_sample / the Philox row are those of the B-row call; xdup = NULL or the [2B] network input
+int launch_sampler_update_guided(int kind, float* x, float* xdup, const float* eps_c, const float* eps_u, const float* noise, float w,
+                                 float c_x0a, float c_x0b, float c_mean0, float c_mean1, float c_noise, int clip, int64_t n,
+                                 int use_philox, uint64_t seed, uint64_t sample_offset, uint64_t draw, int64_t per_sample,
+                                 hipStream_t s);
+int launch_guidance_combine(float* out, const float* eps_c, const float* eps_u, float w, int64_t n, hipStream_t s);   // out = e
+int launch_axpy_out_guided(float* x, const float* eps_c, const float* eps_u, float w, float c, int64_t n, hipStream_t s);   // x -= c * e
+int launch_renoise_dup(float* x, float* xdup, const float* noise, float ca, float cb, int64_t n, int use_philox, uint64_t seed,
+                       uint64_t sample_offset, uint64_t draw, int64_t per_sample, hipStream_t s);
 int launch_nonfinite_flag(const float* v, int64_t n, int* flag, hipStream_t s);          // *flag = 1 if any v[i] is Inf / NaN (f16x2 / f16x1 range guard)
 int launch_pack_frames_u8(const float* in, uint8_t* out, int B, int T, int C, int HW, hipStream_t s);
 // per-frame MSE (fp32) and SSIM (fp64) of video_gen's test mode, kernels/metrics.cpp; part: frame_metrics_scratch_bytes of device scratch

@@ -203,6 +203,150 @@ int launch_axpy_out(float* x, const float* eps, float c, int64_t n, hipStream_t 
     return 0;
 }
 
+// ---- classifier-free guidance.  A guided step is ONE forward at 2B rows -- rows [0, B) on (x, cond), rows [B, 2B) on (x, cond_weak) --
+// and one of the kernels below, which forms, per element, in fp32 with one rounding per operation and no fma (as torch evaluates
+// `e_c + (s - 1) * (e_c - e_u)`),
+//     d = e_c - e_u;   e = e_c + w * d            w = float32(s - 1)
+// and then runs the chain of its unguided twin above on e: same operations, same order.  n, per_sample and the Philox row are those of
+// the B-row call; `xdup` (NULL, or the network's [2B] input buffer) receives the new x in both halves in the same pass.
+__device__ __forceinline__ float guided_eps(float ec, float eu, float w) { return __fadd_rn(ec, __fmul_rn(w, __fsub_rn(ec, eu))); }
+
+__device__ __forceinline__ void store_dup(float* xdup, int64_t i, int64_t n4, float4 v) {
+    reinterpret_cast<float4*>(xdup)[i] = v;
+    reinterpret_cast<float4*>(xdup)[n4 + i] = v;
+}
+
+struct GuidedUpdArgs {
+    UpdArgs u;              // u.eps = the conditional half
+    const float* eps_u;     // the weak half
+    float* xdup;
+    float w;
+};
+
+__global__ __launch_bounds__(256) void sampler_update_guided_kernel(GuidedUpdArgs g) {
+    const UpdArgs& a = g.u;
+    const int64_t n4 = a.n >> 2;
+    for (int64_t i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 xv = reinterpret_cast<const float4*>(a.x)[i];
+        const float4 cv = reinterpret_cast<const float4*>(a.eps)[i];
+        const float4 uv = reinterpret_cast<const float4*>(g.eps_u)[i];
+        float4 zv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (a.c_noise != 0.0f) {
+            if (a.use_philox) {
+                const int64_t e = i * 4;
+                const int64_t row = e / a.per_sample;             // a row of the B-row call
+                zv = philox_normal4(a.seed, a.sample_offset + (uint64_t)row, a.draw, (uint64_t)((e - row * a.per_sample) >> 2));
+            } else {
+                zv = reinterpret_cast<const float4*>(a.noise)[i];
+            }
+        }
+        float xs[4] = {xv.x, xv.y, xv.z, xv.w}, cs[4] = {cv.x, cv.y, cv.z, cv.w}, us[4] = {uv.x, uv.y, uv.z, uv.w};
+        float zs[4] = {zv.x, zv.y, zv.z, zv.w}, o[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float ej = guided_eps(cs[j], us[j], g.w);
+            float x0 = __fmul_rn(a.c_x0a, __fsub_rn(xs[j], __fmul_rn(a.c_x0b, ej)));
+            if (a.clip) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+            const float second = (a.kind == 0) ? xs[j] : ej;
+            float v = __fadd_rn(__fmul_rn(a.c_mean0, x0), __fmul_rn(a.c_mean1, second));
+            if (a.c_noise != 0.0f) v = __fadd_rn(v, __fmul_rn(a.c_noise, zs[j]));
+            o[j] = v;
+        }
+        const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+        reinterpret_cast<float4*>(a.x)[i] = ov;
+        if (g.xdup) store_dup(g.xdup, i, n4, ov);
+    }
+}
+
+int launch_sampler_update_guided(int kind, float* x, float* xdup, const float* eps_c, const float* eps_u, const float* noise, float w,
+                                 float c_x0a, float c_x0b, float c_mean0, float c_mean1, float c_noise, int clip, int64_t n,
+                                 int use_philox, uint64_t seed, uint64_t sample_offset, uint64_t draw, int64_t per_sample,
+                                 hipStream_t s) {
+    MCVD_REQUIRE(x && eps_c && eps_u, "sampler_update_guided: NULL argument");
+    MCVD_REQUIRE(n % 4 == 0 && (per_sample % 4 == 0 || !use_philox), "sampler_update_guided: n must be a multiple of 4");
+    MCVD_REQUIRE(c_noise == 0.0f || use_philox || noise, "sampler_update_guided: noise needed");
+    GuidedUpdArgs g{{kind, x, eps_c, noise, c_x0a, c_x0b, c_mean0, c_mean1, c_noise, clip, n, use_philox, seed, sample_offset, draw,
+                     per_sample}, eps_u, xdup, w};
+    hipLaunchKernelGGL(sampler_update_guided_kernel, dim3(grid_for(n >> 2)), dim3(256), 0, s, g);
+    MCVD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// eps_out = e  (the host loops and F-PNDM, whose lincomb / transfer kernels then run on B rows)
+__global__ __launch_bounds__(256) void guidance_combine_kernel(float* out, const float* eps_c, const float* eps_u, float w, int64_t n) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        const float4 c = reinterpret_cast<const float4*>(eps_c)[i];
+        const float4 u = reinterpret_cast<const float4*>(eps_u)[i];
+        reinterpret_cast<float4*>(out)[i] =
+            make_float4(guided_eps(c.x, u.x, w), guided_eps(c.y, u.y, w), guided_eps(c.z, u.z, w), guided_eps(c.w, u.w, w));
+    }
+}
+
+int launch_guidance_combine(float* out, const float* eps_c, const float* eps_u, float w, int64_t n, hipStream_t s) {
+    MCVD_REQUIRE(out && eps_c && eps_u && n % 4 == 0, "guidance_combine: NULL argument, or n is not a multiple of 4");
+    hipLaunchKernelGGL(guidance_combine_kernel, dim3(grid_for(n >> 2)), dim3(256), 0, s, out, eps_c, eps_u, w, n);
+    MCVD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// x = x - c*e         (the guided denoise pass; nothing reads the network's input buffer afterwards)
+__global__ __launch_bounds__(256) void axpy_out_guided_kernel(float* x, const float* eps_c, const float* eps_u, float w, float c,
+                                                               int64_t n) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        float4 xv = reinterpret_cast<float4*>(x)[i];
+        const float4 cv = reinterpret_cast<const float4*>(eps_c)[i];
+        const float4 uv = reinterpret_cast<const float4*>(eps_u)[i];
+        xv.x = __fsub_rn(xv.x, __fmul_rn(c, guided_eps(cv.x, uv.x, w)));
+        xv.y = __fsub_rn(xv.y, __fmul_rn(c, guided_eps(cv.y, uv.y, w)));
+        xv.z = __fsub_rn(xv.z, __fmul_rn(c, guided_eps(cv.z, uv.z, w)));
+        xv.w = __fsub_rn(xv.w, __fmul_rn(c, guided_eps(cv.w, uv.w, w)));
+        reinterpret_cast<float4*>(x)[i] = xv;
+    }
+}
+
+int launch_axpy_out_guided(float* x, const float* eps_c, const float* eps_u, float w, float c, int64_t n, hipStream_t s) {
+    MCVD_REQUIRE(x && eps_c && eps_u && n % 4 == 0, "axpy_guided: NULL argument, or n is not a multiple of 4");
+    hipLaunchKernelGGL(axpy_out_guided_kernel, dim3(grid_for(n >> 2)), dim3(256), 0, s, x, eps_c, eps_u, w, c, n);
+    MCVD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// x = ca*x + cb*z     (the t_min re-noise of a guided call: the B rows draw what an unguided call draws; both halves of xdup get the result)
+__global__ __launch_bounds__(256) void renoise_dup_kernel(float* x, float* xdup, const float* noise, float ca, float cb, int64_t n,
+                                                           int use_philox, uint64_t seed, uint64_t sample_offset, uint64_t draw,
+                                                           int64_t per_sample) {
+    const int64_t n4 = n >> 2;
+    for (int64_t i = blockIdx.x * 256L + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+        float4 xv = reinterpret_cast<float4*>(x)[i];
+        float4 zv;
+        if (use_philox) {
+            const int64_t e = i * 4;
+            const int64_t row = e / per_sample;
+            zv = philox_normal4(seed, sample_offset + (uint64_t)row, draw, (uint64_t)((e - row * per_sample) >> 2));
+        } else {
+            zv = reinterpret_cast<const float4*>(noise)[i];
+        }
+        xv.x = __fadd_rn(__fmul_rn(ca, xv.x), __fmul_rn(cb, zv.x));
+        xv.y = __fadd_rn(__fmul_rn(ca, xv.y), __fmul_rn(cb, zv.y));
+        xv.z = __fadd_rn(__fmul_rn(ca, xv.z), __fmul_rn(cb, zv.z));
+        xv.w = __fadd_rn(__fmul_rn(ca, xv.w), __fmul_rn(cb, zv.w));
+        reinterpret_cast<float4*>(x)[i] = xv;
+        store_dup(xdup, i, n4, xv);
+    }
+}
+
+int launch_renoise_dup(float* x, float* xdup, const float* noise, float ca, float cb, int64_t n, int use_philox, uint64_t seed,
+                       uint64_t sample_offset, uint64_t draw, int64_t per_sample, hipStream_t s) {
+    MCVD_REQUIRE(x && xdup && n % 4 == 0 && (per_sample % 4 == 0 || !use_philox), "renoise_dup: NULL argument, or n is not a multiple of 4");
+    MCVD_REQUIRE(use_philox || noise, "renoise_dup: noise needed");
+    hipLaunchKernelGGL(renoise_dup_kernel, dim3(grid_for(n >> 2)), dim3(256), 0, s, x, xdup, noise, ca, cb, n, use_philox, seed,
+                       sample_offset, draw, per_sample);
+    MCVD_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // f16x2 range guard: the two-piece fp16 kernels clamp nothing -- an activation beyond the fp16 range becomes Inf, the accumulators NaN,
 // GroupNorm spreads it over the sample -- so a scan of the forward's epsilon sees every overflow.  One flag word, written only on a hit.
 __global__ __launch_bounds__(256) void nonfinite_flag_kernel(const float* v, int64_t n, int* flag) {

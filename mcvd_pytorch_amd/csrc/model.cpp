@@ -636,7 +636,34 @@ int mcvd_model::ensure_workspace(int B) {
     return 0;
 }
 
-float* mcvd_model::resolve(const TRef& r, const float* x, const float* cond, float* out, int B) const {
+// Buffers of a guided call at B rows (model.h: gd_x, gd_cond, gd_mask), grown on demand; the mask rows are uploaded when B or the weak
+// rows' value changes.  The 2B-row layout always starts at the buffers' heads, whatever their capacity.
+int mcvd_model::ensure_guided(int B, int weak_mask) {
+    hipStream_t s = ctx->stream;
+    const size_t plane = (size_t)d.channels * d.image_size * d.image_size;
+    if (B > gd_B) {
+        MCVD_HIP_CHECK(hipStreamSynchronize(s));
+        if (gd_x) MCVD_HIP_CHECK(hipFree(gd_x));
+        if (gd_cond) MCVD_HIP_CHECK(hipFree(gd_cond));
+        if (gd_mask) MCVD_HIP_CHECK(hipFree(gd_mask));
+        gd_x = nullptr; gd_cond = nullptr; gd_mask = nullptr; gd_B = 0; gd_mask_B = 0;
+        MCVD_HIP_CHECK(hipMalloc((void**)&gd_x, 2 * (size_t)B * plane * d.num_frames * sizeof(float)));
+        MCVD_HIP_CHECK(hipMalloc((void**)&gd_cond, 2 * (size_t)B * plane * d.num_frames_cond * sizeof(float)));
+        if (d.cond_emb) MCVD_HIP_CHECK(hipMalloc((void**)&gd_mask, 2 * (size_t)B * sizeof(int32_t)));
+        gd_B = B;
+    }
+    if (d.cond_emb && (gd_mask_B != B || gd_mask_val != weak_mask)) {
+        std::vector<int32_t> h(2 * (size_t)B, 1);
+        for (int b = 0; b < B; ++b) h[B + b] = weak_mask;
+        MCVD_HIP_CHECK(hipMemcpyAsync(gd_mask, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        MCVD_HIP_CHECK(hipStreamSynchronize(s));           // (h is a pageable temporary)
+        gd_mask_B = B;
+        gd_mask_val = weak_mask;
+    }
+    return 0;
+}
+
+float* mcvd_model::resolve(const TRef& r,const float* x, const float* cond, float* out, int B) const {
     switch (r.kind) {
         case REF_ARENA: return arena + r.off * (int64_t)B;
         case REF_X: return const_cast<float*>(x);

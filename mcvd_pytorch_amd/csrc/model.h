@@ -220,6 +220,14 @@ struct mcvd_model {
     float* labels_f = nullptr;        // [arena_B] float labels (F-PNDM midpoints)
     float* fp_buf = nullptr;          // F-PNDM device loop: 9 state-sized buffers (4 eps history, 3 Runge-Kutta eps, x temp, combination)
     int fp_B = 0;
+    // classifier-free guidance (api.cpp: GuidedCall): the 2B-row forward of a guided call at gd_B rows reads gd_x = [x ; x] and
+    // gd_cond = [cond ; cond_weak] (and, cond_emb, gd_mask = [1.. ; weak_mask..]) and writes eps_buf (2B rows of the workspace).
+    // Allocated by the first guided call at that B: an unguided user holds none of them
+    float* gd_x = nullptr;
+    float* gd_cond = nullptr;
+    int32_t* gd_mask = nullptr;
+    int gd_B = 0, gd_mask_B = 0, gd_mask_val = -1;
+    int ensure_guided(int B, int weak_mask);
     float* ksplit_buf = nullptr;      // partial outputs of the K-split Winograd layers (H*W <= 256): ensure_ksplit sizes it per batch
     size_t ksplit_floats = 0;
 

@@ -108,6 +108,36 @@ def task_conditioning(config, X, task):
     return real, cond, cond_mask, nfp
 
 
+GUIDANCE_DROPS = ("past", "future", "all")
+
+
+def guidance_conditioning(config, cond, drop="all"):
+    """The weak conditioning of a guided sampler call, `(cond_weak, mask)`, from cond in the layout of `conditioning_fn` ([past block |
+    future block], whose cond_mask is the keep mask of the past block): what a net trained with conditioning dropout saw for the dropped
+    part of its batches.  Feed it to the samplers as `guidance_cond=cond_weak, guidance_mask=mask`.
+
+      * "past":   the first C * num_frames_cond channels zeroed (prob_mask_cond), mask 0;
+      * "future": the trailing C * num_frames_future channels zeroed (prob_mask_future), mask 1; ValueError without future frames;
+      * "all":    zeros, mask 0.
+    `cond` is not modified."""
+    d = config.data
+    n_past, n_future = d.channels * d.num_frames_cond, d.channels * getattr(d, "num_frames_future", 0)
+    if drop not in GUIDANCE_DROPS:
+        raise ValueError(f"unknown guidance drop {drop!r}; one of {GUIDANCE_DROPS}")
+    if drop == "future" and n_future == 0:
+        raise ValueError("guidance drop 'future' needs data.num_frames_future > 0")
+    if cond.dim() != 4 or cond.shape[1] != n_past + n_future:
+        raise ValueError(f"cond has shape {tuple(cond.shape)}; expected [B, {n_past + n_future}, S, S]")
+    if drop == "all":
+        return torch.zeros_like(cond), 0
+    weak = cond.clone()
+    if drop == "past":
+        weak[:, :n_past] = 0
+        return weak, 0
+    weak[:, n_past:] = 0
+    return weak, 1
+
+
 def _mean_image(config, like):
     m = getattr(config, "image_mean", None)
     return None if m is None else m.to(like.device)[None, ...]
@@ -145,7 +175,7 @@ def inverse_data_transform(config, X):
 
 @torch.no_grad()
 def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, sampler=None, data_init=None, verbose=False,
-              log=False, task=None, cond_mask=None, **sampler_kwargs):
+              log=False, task=None, cond_mask=None, guidance_scale=None, guidance_drop="all", **sampler_kwargs):
     """Autoregressive block loop of NCSNRunner.video_gen (runners/ncsn_runner.py:1476-1569, prediction path: future == 0), kept on
     the device between blocks (the reference moves every block to the CPU and back, :1521-1539).  Returns [B, C*num_frames_pred, S, S].
 
@@ -180,7 +210,11 @@ def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, 
         on the shape: a RuntimeError before the second block here.
     `cond_mask` goes to the sampler as given for block 0 and as ones for every later block (:1885-1886).  It is not routed into the
     forward: the reference samplers take it into **kwargs and drop it (models/__init__.py:207-209), so a `model.cond_emb` net samples
-    as if the mask were ones, here as there.  data_init, init_prev_t, model.gamma and the per-block seed mean the same in every task."""
+    as if the mask were ones, here as there.  data_init, init_prev_t, model.gamma and the per-block seed mean the same in every task.
+
+    `guidance_scale` (no reference counterpart; None = off, the loop above untouched): every sampler call is guided (samplers.py), its
+    weak conditioning rebuilt from the shifted cond of each block, `guidance_conditioning(config, cond, guidance_drop)`.  It needs cond
+    (ValueError for the unconditional bootstrap)."""
     d, s = config.data, config.sampling
     C, nf, nc, S = d.channels, d.num_frames, d.num_frames_cond, d.image_size
     future = getattr(d, "num_frames_future", 0)
@@ -195,6 +229,8 @@ def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, 
     one_at_a_time = bool(getattr(s, "one_frame_at_a_time", False))
     sampler = sampler or get_sampler(config)
     dev = scorenet.device
+    if guidance_scale is not None and cond is None:
+        raise ValueError("video_gen: guidance_scale needs conditioning frames (cond is None)")
     if cond is not None:
         cond = cond.to(dev).float().contiguous()
         B = cond.shape[0]
@@ -243,6 +279,9 @@ def video_gen(config, scorenet, cond, num_frames_pred=None, init_noise_fn=None, 
         if task is not None and cond is not None and cond.shape[1] != cond_width:       # one_frame_at_a_time + kept future block
             raise RuntimeError(f"task {task!r}, block {i}: the cond shift left {cond.shape[1]} cond channels, the network takes "
                                f"{cond_width} (the reference's sampler call fails here too, :1700-1703, :1874-1877)")
+        if guidance_scale is not None:
+            weak, weak_mask = guidance_conditioning(config, cond, guidance_drop)
+            kw.update(guidance_scale=guidance_scale, guidance_cond=weak, guidance_mask=weak_mask)
         mask = cond_mask if (i == 0 or cond_mask is None) else torch.ones_like(cond_mask)   # :1885-1886
         out = sampler(x0, scorenet, cond=cond, cond_mask=mask, final_only=True, denoise=getattr(s, "denoise", True),
                       subsample_steps=getattr(s, "subsample", None), clip_before=getattr(s, "clip_before", True),
@@ -412,7 +451,7 @@ def _finish_video_gen(config, metrics, ckpt, train, out_dir, start_time, log, wr
 @torch.no_grad()
 def evaluate_video_gen(config, scorenet, batches, *, ckpt="latest", train=False, max_data_iter=None, preds_per_test=None,
                        lpips=None, fvd=None, fvd_batch=10, data_init_batches=None, out_dir=None, sampler=None,
-                       init_noise_fn=None, seed=None, shard=None, metrics=None, log=None):
+                       init_noise_fn=None, seed=None, shard=None, metrics=None, log=None, guidance_scale=None, guidance_drop="all"):
     """NCSNRunner.video_gen (runners/ncsn_runner.py:1304-2368), the mode `main.py --video_gen` runs, as one call: every batch of `batches`
     through the phases of `video_tasks(config)`, the frames of each phase into a `VideoMetrics`, and the reference's vid_metrics dict back.
     Frames stay on the device from the sampler to the metrics (the reference's per-block `.to('cpu')`, :1523, is not reproduced).
@@ -456,7 +495,10 @@ def evaluate_video_gen(config, scorenet, batches, *, ckpt="latest", train=False,
     all_gather_object after the loop, VideoMetrics.merged reassembles the global order, every rank returns the same dict -- the single-rank
     one, bit for bit -- and rank 0 writes the files.  A shard without a process group returns {'shard': (rank, world), 'state':
     metrics.state(), 'saved': {file stem: tensors}} for the caller to merge (VideoMetrics.merged(config, states).summary()).
-    data_transform's dequantisation noise is torch's and not row-keyed: a sharded run of such a config is not the single-rank one."""
+    data_transform's dequantisation noise is torch's and not row-keyed: a sharded run of such a config is not the single-rank one.
+
+    Guidance.  `guidance_scale` / `guidance_drop` go to video_gen in phases (1) and (2).  Phase (3) stays unguided: its cond is all zeros
+    already, guidance would double its cost and change nothing."""
     import logging
     import os
     import time
@@ -540,6 +582,8 @@ def evaluate_video_gen(config, scorenet, batches, *, ckpt="latest", train=False,
             kw = dict(seed=phase_seed, sample_offset=begin * ppt)
             if noise_fn is None and not gamma:
                 noise_fn = lambda blk, shp, dv: _philox_init(net, phase_seed + blk, begin * ppt, shp, dv)      # noqa: E731
+        if guidance_scale is not None and phase != 3:
+            kw.update(guidance_scale=guidance_scale, guidance_drop=guidance_drop)
         pred = video_gen(config, scorenet, cond, task=task, cond_mask=cond_mask, data_init=data_init, sampler=sampler,
                          init_noise_fn=noise_fn, verbose=not train, log=not train, **kw)
         return inverse_data_transform(config, pred)

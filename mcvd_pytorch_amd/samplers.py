@@ -65,11 +65,20 @@ def _f(t):
     return float(t)          # fp32 0-dim tensor -> python float (exact)
 
 
+def _sqrt_rn(t):
+    """Correctly rounded fp32 square root of a 0-dim tensor, as the library's device loops take it (sqrtf).  torch's CPU sqrt goes through a
+    vector math library on some hosts and is then a few ulp off: the coefficients of a host loop and of the device loop differ there (which
+    the unguided loops are allowed, tests/test_gpu_parity.py).  A guided host loop uses this one and returns the device loop's bits."""
+    return torch.tensor(np.sqrt(np.float32(t.item())), dtype=torch.float32)
+
+
 @torch.no_grad()
 def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False, denoise=True, subsample_steps=None,
             same_noise=False, noise_val=None, frac_steps=None, verbose=False, log=False, clip_before=True, t_min=-1,
-            gamma=False, noise=None, seed=None, sample_offset=0, cond_noise=None, steps_on_device=False, **kwargs):
+            gamma=False, noise=None, seed=None, sample_offset=0, cond_noise=None, steps_on_device=False, guidance_scale=None,
+            guidance_cond=None, guidance_mask=0, **kwargs):
     net = _unwrap(scorenet)
+    guided = net.guidance_args(x_mod.shape[0], guidance_scale, guidance_cond, guidance_mask, gamma=gamma)      # refusals: before any launch
     if gamma and not getattr(net, "gamma", False):
         raise AttributeError("'HipScoreNet' object has no attribute 'k_cum' (gamma=True needs a model.gamma net, models/__init__.py:224, :118)")
     # ddim_sampler reads `gamma` in ONE place: the t_min re-noise of the first executed step draws a standardised Gamma variate (:144-151);
@@ -141,11 +150,16 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
                 _lib.check(_lib.lib.mcvd_model_set_cond_noise(
                     net._model, C.c_void_p(cond_noise.data_ptr()) if cond_noise is not None else None, 0, 0, 0), "set_cond_noise")
             try:
-                rc = _lib.lib.mcvd_sampler_run(
-                    net._model, kind, C.c_void_p(x.data_ptr()), C.c_void_p(cond.data_ptr()) if cond is not None else None,
-                    C.c_void_p(noise.data_ptr()) if noise is not None else None, C.c_uint64(seed or 0),
-                    C.c_uint64(sample_offset), int(subsample_steps) if subsample_steps is not None else 0, flags,
-                    float(t_min), B)
+                tail = (C.c_void_p(noise.data_ptr()) if noise is not None else None, C.c_uint64(seed or 0), C.c_uint64(sample_offset),
+                        int(subsample_steps) if subsample_steps is not None else 0, flags, float(t_min), B)
+                if guided is None:
+                    rc = _lib.lib.mcvd_sampler_run(
+                        net._model, kind, C.c_void_p(x.data_ptr()), C.c_void_p(cond.data_ptr()) if cond is not None else None, *tail)
+                else:                      # every evaluation of the loop guided: forwards at 2B rows, noise of the B rows
+                    scale, weak, gmask = guided
+                    rc = _lib.lib.mcvd_sampler_run_guided(
+                        net._model, kind, C.c_void_p(x.data_ptr()), C.c_void_p(cond.data_ptr()),
+                        C.c_void_p(weak.data_ptr()) if weak is not None else None, scale, gmask, *tail)
             finally:
                 if nic:
                     _lib.lib.mcvd_model_set_cond_noise(net._model, None, 0, 0, 0)
@@ -162,6 +176,7 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
         noise_val = x.detach().clone()                                              # :259-260
     draw = [0]
     fwd_no = [0]
+    sq = _sqrt_rn if guided is not None else torch.sqrt
     if gamma:                                                                       # :224-225, :238-240, :255-257
         ks_cum, thetas = net.k_cum.cpu(), net.theta_t.cpu()
         if subsample_steps is not None and subsample_steps < len(net.alphas):
@@ -173,6 +188,8 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
         if nic and cond_noise is not None:
             net.set_next_cond_noise(cond_noise[fwd_no[0]])
         fwd_no[0] += 1
+        if guided is not None:
+            return net(xx, labels, cond=cond, guidance_scale=guided[0], guidance_cond=guided[1], guidance_mask=guided[2])
         return net(xx, labels, cond=cond)
 
     def next_noise(i=None):
@@ -221,17 +238,20 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
         c_beta, c_alpha, c_alpha_prev = betas[i], alphas[i], alphas_prev[i]
         if not x_transf and t_min > 0:                                              # :272-279
             z = next_noise(i)
-            x.mul_(_f(c_alpha.sqrt())).add_(z, alpha=_f((1 - c_alpha).sqrt()))
+            if guided is not None:          # product and sum rounded separately, as the device loop's re-noise kernel (and the reference, :279) does
+                x.mul_(_f(sq(c_alpha))).add_(_f(sq(1 - c_alpha)) * z)
+            else:
+                x.mul_(_f(c_alpha.sqrt())).add_(z, alpha=_f((1 - c_alpha).sqrt()))
         x_transf = True
         labels = (int(step) * torch.ones(B, device=dev)).long()                     # :283
         grad = call_net(x, labels)                                                  # :284
-        c_x0a, c_x0b = _f(1 / c_alpha.sqrt()), _f((1 - c_alpha).sqrt())             # :287
+        c_x0a, c_x0b = _f(1 / sq(c_alpha)), _f(sq(1 - c_alpha))                     # :287
         last_step = i + 1 == L
         if kind == _lib.SAMPLER_DDPM:
-            c0 = _f(c_alpha_prev.sqrt() * c_beta / (1 - c_alpha))                   # :290
-            c1 = _f((1 - c_beta).sqrt() * (1 - c_alpha_prev) / (1 - c_alpha))
+            c0 = _f(sq(c_alpha_prev) * c_beta / (1 - c_alpha))                      # :290
+            c1 = _f(sq(1 - c_beta) * (1 - c_alpha_prev) / (1 - c_alpha))
         else:
-            c0, c1 = _f(c_alpha_prev.sqrt()), _f((1 - c_alpha_prev).sqrt())         # :168
+            c0, c1 = _f(sq(c_alpha_prev)), _f(sq(1 - c_alpha_prev))                 # :168
         need_log = (i == 0 or (i + 1) % max(L // 10, 1) == 0) and (verbose or log)
         add_noise = kind == _lib.SAMPLER_DDPM and not last_step
         # The reference appends/logs x_mod BEFORE adding the step noise (:292-308 precede :324-328), so when something
@@ -240,7 +260,7 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
         z, cn = None, 0.0
         if add_noise:
             z = noise_val if same_noise else next_noise(i)
-            cn = _f(c_beta.sqrt()) if just_beta else _f(((1 - c_alpha_prev) / (1 - c_alpha) * c_beta).sqrt())   # :326/:328
+            cn = _f(sq(c_beta)) if just_beta else _f(sq((1 - c_alpha_prev) / (1 - c_alpha) * c_beta))   # :326/:328
         update(grad, None if split else z, c_x0a, c_x0b, c0, c1, 0.0 if split else cn)
         if not final_only:
             images.append(x.clone() if steps_on_device else x.to("cpu"))            # :292-293
@@ -256,11 +276,14 @@ def _sample(kind, x_mod, scorenet, cond=None, just_beta=False, final_only=False,
             if log:
                 logging.info(msg)
         if split:
-            x.add_(z, alpha=cn)
+            if guided is not None:          # two roundings, as the fused update kernel adds its noise (and the reference, :326-328): a guided host
+                x.add_(cn * z)              # loop returns the device loop's bits
+            else:
+                x.add_(z, alpha=cn)
 
     if denoise:                                                                     # :331-335 (label L-1, sic)
         last_noise = ((L - 1) * torch.ones(B, device=dev)).long()
-        x = x - _f((1 - alphas[-1]).sqrt()) * call_net(x, last_noise)
+        x = x - _f(sq(1 - alphas[-1])) * call_net(x, last_noise)
         if not final_only:
             images.append(x if steps_on_device else x.to("cpu"))                    # (a new tensor: nothing writes to it again)
     _lib.check(_lib.lib.mcvd_ctx_check_range(net._ctx), "sampler (f16x2 / f16x1 range guard)")      # no-op unless one of the two options is on
@@ -274,7 +297,14 @@ def ddpm_sampler(x_mod, scorenet, cond=None, just_beta=False, final_only=False, 
                  t_min=-1, gamma=False, **kwargs):
     """Reference: models/__init__.py:206-340.  Extra kwargs understood here: `noise` ([n_draws,B,C,H,W] injected
     sequence), `seed`, `sample_offset` (global index of row 0, for sharded runs), `steps_on_device` (with `final_only=False`
-    the step images are kept as device copies and the stacked result stays on the device; the values are the same)."""
+    the step images are kept as device copies and the stacked result stays on the device; the values are the same).
+
+    Classifier-free guidance (no reference counterpart; the same three kwargs on ddim_sampler and fpndm_sampler): `guidance_scale=s`
+    replaces every network evaluation of the call -- each step and the denoise pass -- by eps_c + (s - 1) * (eps_c - eps_u), eps_c on
+    (x, cond), eps_u on (x, `guidance_cond`) (shaped like cond, default zeros; a cond_emb net sees cond_mask = `guidance_mask` on the
+    weak rows and ones on the others): the reference's sampler handed a wrapped scorenet.  One forward at 2B rows per evaluation; the
+    noise streams are those of the B rows of an unguided call.  `None` (the default) is the unguided call, untouched.  Refused: a net
+    without conditioning frames (ValueError), model.noise_in_cond and gamma=True (NotImplementedError), a mis-shaped guidance_cond."""
     return _sample(_lib.SAMPLER_DDPM, x_mod, scorenet, cond=cond, just_beta=just_beta, final_only=final_only,
                    denoise=denoise, subsample_steps=subsample_steps, same_noise=same_noise, noise_val=noise_val,
                    frac_steps=frac_steps, verbose=verbose, log=log, clip_before=clip_before, t_min=t_min, gamma=gamma,
@@ -291,7 +321,8 @@ def ddim_sampler(x_mod, scorenet, cond=None, final_only=False, denoise=True, sub
 
 @torch.no_grad()
 def fpndm_sampler(x_mod, scorenet, cond=None, final_only=False, denoise=True, subsample_steps=None, verbose=False, log=True,
-                  clip_before=True, t_min=-1, gamma=False, steps_on_device=False, **kwargs):
+                  clip_before=True, t_min=-1, gamma=False, steps_on_device=False, guidance_scale=None, guidance_cond=None,
+                  guidance_mask=0, **kwargs):
     """F-PNDM: reference models/__init__.py:38-99 (FPNDM_sampler) with models/pndm.py (gen_order_4 :41-52, runge_kutta :3-17,
     transfer :19-33), behaviour mirrored statement by statement: steps 0, skip, 2*skip, ... with t_next = the previous step
     (-1 first), alpha table = flipped `alphas` indexed by t + 1, network label = t, float midpoint label (t + t_next) / 2;
@@ -303,6 +334,7 @@ def fpndm_sampler(x_mod, scorenet, cond=None, final_only=False, denoise=True, su
     net = _unwrap(scorenet)
     if subsample_steps is None:
         raise TypeError("FPNDM_sampler needs subsample_steps (the reference divides by it, models/__init__.py:60)")
+    guided = net.guidance_args(x_mod.shape[0], guidance_scale, guidance_cond, guidance_mask, gamma=gamma)
     net.sync_parameters(force=True)
     dev = net.device
     x = x_mod.to(device=dev, dtype=torch.float32).contiguous().clone()
@@ -324,11 +356,19 @@ def fpndm_sampler(x_mod, scorenet, cond=None, final_only=False, denoise=True, su
         # the whole loop inside the library (the reference never logs in this sampler, so verbose / log change nothing)
         with torch.cuda.device(dev):
             net._bind_stream()
-            _lib.check(_lib.lib.mcvd_fpndm_run(net._model, C.c_void_p(x.data_ptr()), C.c_void_p(cond.data_ptr()) if cond is not None else None,
-                                               int(subsample_steps), _lib.FLAG_CLIP_BEFORE if clip_before else 0, B), "fpndm_run")
+            flags = _lib.FLAG_CLIP_BEFORE if clip_before else 0
+            if guided is None:
+                _lib.check(_lib.lib.mcvd_fpndm_run(net._model, C.c_void_p(x.data_ptr()), C.c_void_p(cond.data_ptr()) if cond is not None else None,
+                                                   int(subsample_steps), flags, B), "fpndm_run")
+            else:                          # the four Runge-Kutta evaluations (float midpoint labels included) and every later one guided
+                scale, weak, gmask = guided
+                _lib.check(_lib.lib.mcvd_fpndm_run_guided(net._model, C.c_void_p(x.data_ptr()), C.c_void_p(cond.data_ptr()),
+                                                          C.c_void_p(weak.data_ptr()) if weak is not None else None, scale, gmask,
+                                                          int(subsample_steps), flags, B), "fpndm_run_guided")
         net._cond_key = None
         return x.unsqueeze(0)
     _lib.check(_lib.lib.mcvd_ctx_clear_range(net._ctx), "clear_range")
+    sq = _sqrt_rn if guided is not None else torch.sqrt
     alphas_old = net.alphas.cpu().flip(0)                                           # :57
     T = len(alphas_old)
     skip = T // subsample_steps                                                     # :60
@@ -337,13 +377,16 @@ def fpndm_sampler(x_mod, scorenet, cond=None, final_only=False, denoise=True, su
 
     def model(xx, t_value, as_float):
         dtype = torch.float32 if as_float else torch.int64
-        return net(xx, torch.full((B,), t_value, device=dev, dtype=dtype), cond=cond)
+        labels = torch.full((B,), t_value, device=dev, dtype=dtype)
+        if guided is not None:
+            return net(xx, labels, cond=cond, guidance_scale=guided[0], guidance_cond=guided[1], guidance_mask=guided[2])
+        return net(xx, labels, cond=cond)
 
     def transfer(xx, t_idx, tn_idx, et):                                            # pndm.py:19-33
         at, an = alphas_old[int(t_idx) + 1], alphas_old[int(tn_idx) + 1]            # t.long() truncates toward zero, as int()
         d = _f(an - at)
-        c1 = _f(1 / (at.sqrt() * (at.sqrt() + an.sqrt())))
-        c2 = _f(1 / (at.sqrt() * (((1 - an) * at).sqrt() + ((1 - at) * an).sqrt())))
+        c1 = _f(1 / (sq(at) * (sq(at) + sq(an))))
+        c2 = _f(1 / (sq(at) * (sq((1 - an) * at) + sq((1 - at) * an))))
         out = torch.empty_like(xx)
         with torch.cuda.device(dev):
             net._bind_stream()

@@ -337,11 +337,43 @@ class HipScoreNet:
             raise RuntimeError(f"{name} must live on {self.device} (got {t.device})")
         return t.to(dtype=torch.float32).contiguous()
 
+    def guidance_args(self, B, guidance_scale, guidance_cond=None, guidance_mask=0, gamma=False):
+        """The checked arguments of a guided call at B rows, `(scale, cond_weak, mask)`, or None with `guidance_scale=None`.  Raises
+        what a guided call refuses, before anything reaches the device: ValueError for a net without conditioning frames,
+        NotImplementedError for `model.noise_in_cond` (the wrapped reference net would draw two independent z per evaluation, and which
+        of them the weak branch sees is not defined) and for `gamma=True` (no config has gamma without noise_in_cond: it could not be
+        pinned), RuntimeError for a `guidance_cond` that is not shaped like cond."""
+        if guidance_scale is None:
+            return None
+        d = self._desc
+        if d.num_frames_cond == 0:
+            raise ValueError("guidance needs conditioning frames to weaken: this model has data.num_frames_cond == 0")
+        if self.noise_in_cond:
+            raise NotImplementedError("guidance on a model.noise_in_cond net: each of the two evaluations would draw its own conditioning "
+                                      "noise, and which of them the weak branch sees is not defined")
+        if gamma:
+            raise NotImplementedError("guidance with gamma=True is not served (model.gamma exists only with noise_in_cond)")
+        if int(guidance_mask) not in (0, 1):
+            raise ValueError(f"guidance_mask must be 0 or 1, got {guidance_mask!r}")
+        want = (B, d.channels * d.num_frames_cond, d.image_size, d.image_size)
+        if guidance_cond is not None:
+            if tuple(guidance_cond.shape) != want:
+                raise RuntimeError(f"guidance_cond has shape {tuple(guidance_cond.shape)}, expected the shape of cond {want}")
+            guidance_cond = guidance_cond.to(device=self.device, dtype=torch.float32).contiguous()
+        return float(guidance_scale), guidance_cond, int(guidance_mask)
+
     @torch.no_grad()
-    def __call__(self, x, y, cond=None, cond_mask=None):
-        """eps = UNet(x, y, cond)   (reference: UNetMore_DDPM.forward, ncsnpp_more.py:753-770)."""
+    def __call__(self, x, y, cond=None, cond_mask=None, guidance_scale=None, guidance_cond=None, guidance_mask=0):
+        """eps = UNet(x, y, cond)   (reference: UNetMore_DDPM.forward, ncsnpp_more.py:753-770).
+
+        With `guidance_scale=s`: one guided evaluation, eps_c + (s - 1) * (eps_c - eps_u) in fp32 with one rounding per operation, eps_c
+        on (x, cond), eps_u on (x, guidance_cond) (default zeros; a cond_emb net sees cond_mask = guidance_mask on those rows) -- one
+        forward at 2B rows and one combine launch."""
         if self.plan_only:
             raise RuntimeError("HipScoreNet(plan_only=True) cannot compute (no GPU context)")
+        guided = self.guidance_args(x.shape[0], guidance_scale, guidance_cond, guidance_mask)
+        if guided is not None and cond_mask is not None:
+            raise ValueError("cond_mask and guidance_scale together: a guided evaluation sets the mask itself (ones | guidance_mask)")
         self.sync_parameters()
         x = self._prep(x, "x")
         cond = self._prep(cond, "cond")
@@ -371,9 +403,19 @@ class HipScoreNet:
             if mask.shape != (B,):
                 raise RuntimeError(f"cond_mask has shape {tuple(mask.shape)}")
         out = torch.empty_like(x)
+        if guided is not None:
+            scale, weak, gmask = guided
+            with torch.cuda.device(self.device):
+                self._bind_stream()
+                fwd = _lib.lib.mcvd_unet_forward_guided_ft if float_t else _lib.lib.mcvd_unet_forward_guided
+                rc = fwd(self._model, _fptr(x), C.c_void_p(y.data_ptr()), _fptr(cond), _fptr(weak) if weak is not None else None,
+                         scale, gmask, _fptr(out), B)
+            self._cond_key = None                # the 2B-row forward prepared its own SPADE maps in the workspace
+            _lib.check(rc, "unet_forward_guided")
+            return out
         with torch.cuda.device(self.device):
             self._bind_stream()
-            if self.noise_in_cond and cond is not None:                        # ncsnpp_more.py:755-768: fresh noise every forward
+            if self.noise_in_cond and cond is not None:                       # ncsnpp_more.py:755-768: fresh noise every forward
                 if float_t:
                     raise IndexError("tensors used as indices must be long, int, byte or bool tensors (noise_in_cond indexes alphas "
                                      "with the labels)")
