@@ -308,6 +308,39 @@ static_assert(!wino_admits(CF_WINO3, with_room(wino_case_launch({CF_WINO3, 1056,
               wino_admits(CF_WINO3, with_room(wino_case_launch({CF_WINO3, 1056, 1056, 2, 8, 0, false, true}), 2 * 2 * 32 * 64)),
               "a K split needs room for its partial results");
 static_assert(wino_needs_4_parts(2304) && !wino_needs_4_parts(2048), "layers the tuner offers four parts at every batch");
+
+// the rule's geometric clause over planes that are not square: B = 2, Cout = 32, one source, CinP = Cin, weights present, room for exactly the
+// parts.  `parts` is what the kernel makes of the split (wino_kernel_parts), not ConvArgs::ksplit.  tests/test_wino_rule_cpu.py evaluates the
+// same list with tests/wino_rule.py; tests/test_gpu_conv_paths.py runs the admitted shapes and the refusals on the device.
+struct WinoPlaneCase { ConvFamily family; int H, W, parts, Cin; bool admitted; };
+inline constexpr WinoPlaneCase kWinoPlaneCases[] = {
+    // regions of 8 x 16 pixels: H a multiple of 8 (a power of two or not), W a multiple of 16
+    {CF_WINO3, 8, 16, 1, 64, true},      {CF_WINO3, 16, 32, 1, 64, true},     {CF_WINO3, 32, 16, 1, 64, true},    {CF_WINO3, 24, 16, 1, 64, true},
+    {CF_WINO3, 8, 32, 1, 64, true},      {CF_WINO3P, 8, 16, 1, 64, true},     {CF_WINO, 24, 16, 1, 64, true},     {CF_WINO1H, 8, 32, 1, 64, true},
+    {CF_WINO3, 16, 8, 1, 64, false},     {CF_WINO, 16, 8, 1, 64, false},      {CF_WINO3, 8, 24, 1, 64, false},    {CF_WINO3, 4, 16, 1, 64, false},
+    {CF_WINO3, 12, 16, 1, 64, false},    {CF_WINO2H, 12, 16, 1, 64, false},   {CF_WINO3P, 12, 16, 1, 64, false},  {CF_WINO, 12, 16, 1, 64, false},
+    // 8 x 8: pairs of images, every family but the persistent one
+    {CF_WINO, 8, 8, 1, 64, true},        {CF_WINO2H, 8, 8, 1, 64, true},      {CF_WINO1H, 8, 8, 1, 64, true},     {CF_WINO3, 8, 8, 1, 64, true},
+    {CF_WINO3P, 8, 8, 1, 64, false},
+    // max_hw: 16384 pixels but for conv_wino.cpp
+    {CF_WINO3, 128, 128, 1, 64, true},   {CF_WINO3, 128, 256, 1, 64, false},  {CF_WINO2H, 128, 256, 1, 64, false}, {CF_WINO3P, 128, 256, 1, 64, false},
+    {CF_WINO, 128, 256, 1, 64, true},    {CF_WINO3, 64, 256, 1, 64, true},
+    // a split on one region and on a plane whose H is no power of two
+    {CF_WINO3, 8, 16, 2, 64, true},      {CF_WINO3, 8, 16, 4, 64, false},     {CF_WINO2H, 24, 16, 4, 192, true},  {CF_WINO3P, 24, 16, 2, 128, true},
+    {CF_WINO, 8, 32, 2, 64, true},
+};
+constexpr WinoLaunch wino_plane_case_launch(const WinoPlaneCase& c) {
+    return {3, c.H, c.W, 2, c.Cin, c.Cin, c.Cin, 0, 32, 32, c.parts, true, false, c.parts >= 2 ? (size_t)c.parts * 2 * 32 * c.H * c.W : 0};
+}
+constexpr int first_wrong_wino_plane_case() {
+    int i = 0;
+    for (const WinoPlaneCase& c : kWinoPlaneCases) {
+        if (wino_admits(c.family, wino_plane_case_launch(c)) != c.admitted) return i;
+        ++i;
+    }
+    return -1;
+}
+static_assert(first_wrong_wino_plane_case() == -1, "the admission rule disagrees with kWinoPlaneCases at this index");
 }  // namespace conv_kernels_check
 
 }  // namespace mcvd

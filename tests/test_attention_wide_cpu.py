@@ -243,6 +243,20 @@ def test_dispatch_table():
     assert table(0, 0, 1, 1056, 1, 64) == AK_NAIVE and table(4, 0, 0, 1024, 1, 64) == AK_WIDE3
 
 
+def test_the_token_count_cases_expect_what_the_table_says():
+    """tests/test_gpu_parity.py::test_attention_token_counts_with_a_ragged_last_query_tile spells out the kernel per case."""
+    from tests import test_gpu_parity as P
+    src = _src("attn_kernels.h")
+    wide_from, band_hw = _const(src, "AK_WIDE_FROM_D"), _const(src, "AK_WIDE3_BAND_HW_MAX")
+    seen = set()
+    for D, mode, kern in P._TOKEN_COUNT_KERNELS:
+        for S in (32, 96, 160, 288):
+            must = kern[S] if isinstance(kern, dict) else kern
+            assert must == attn_kernel_for(mode, 0, 1, 3 * D, 3, S, wide_from, band_hw), (D, mode, S)
+            seen.add(must)
+    assert seen == {AK_FLASH_F32, AK_SPLIT2, AK_SPLIT3, AK_WIDE2, AK_WIDE3}
+
+
 def test_the_exports_are_declared():
     hdr = open(os.path.join(ROOT, "include", "mcvd_hip.h")).read()
     lib = open(os.path.join(ROOT, "mcvd_pytorch_amd", "_lib.py")).read()

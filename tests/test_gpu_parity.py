@@ -714,6 +714,48 @@ def test_attention(ctx, B, C, heads, H, naive):
     _close(got, want, what="attention")
 
 
+_TOKEN_REFS = {}
+
+
+def _token_count_case(D, S):
+    """(qkv, fp64 softmax attention) of one batch entry with three heads of dim D over S tokens, computed once per (D, S)."""
+    if (D, S) not in _TOKEN_REFS:
+        C = 3 * D
+        qkv = torch.randn(1, 3 * C, S, generator=_g(9 + D + S))
+        qkv[:, :C] *= 1.5
+        q, k, v = (qkv[:, i * C:(i + 1) * C].double().reshape(3, D, S) for i in range(3))
+        w = torch.softmax(torch.matmul(q.transpose(1, 2), k) * (int(D) ** (-0.5)), dim=-1)
+        _TOKEN_REFS[(D, S)] = (qkv, torch.matmul(v, w.transpose(1, 2)).reshape(1, C, S))
+    return _TOKEN_REFS[(D, S)]
+
+
+# (head dim, naive_attn, the kernel of attn_kernels.h that must run; a dict: by token count)
+_TOKEN_COUNT_KERNELS = [(D, mode, kern) for D in (32, 96, 128) for mode, kern in ((2, 1), (3, 2), (4, 3))] + [
+    (192, 3, 5), (192, 4, {32: 6, 96: 6, 160: 6, 288: 1}),       # three pieces wide up to AK_WIDE3_BAND_HW_MAX = 256 tokens, the fp32 flash kernel beyond
+    (320, 3, 5), (320, 4, 6)]
+
+
+@pytest.mark.parametrize("S", [32, 96, 160, 288])
+@pytest.mark.parametrize("D,mode,kern", _TOKEN_COUNT_KERNELS, ids=lambda v: str(v) if not isinstance(v, dict) else "band")
+def test_attention_token_counts_with_a_ragged_last_query_tile(ctx, D, mode, kern, S):
+    """attn_kernel_for sends every token count that is a multiple of 32 to the flash kernels, whose workgroups hold 128 (or 256) queries
+    and guard the ragged last tile with `active`: 32 tokens (one quarter of a tile), 96, 160 and 288 (a full tile and a part), three
+    heads, against softmax attention in fp64 under the standing gate."""
+    from mcvd_pytorch_amd import _lib
+    qkv, want = _token_count_case(D, S)
+    ctx.opt("naive_attn", mode)
+    try:
+        got = ctx.attention(qkv.cuda(), 3)
+        ran = _lib.lib.mcvd_last_attention_kernel()
+        again = ctx.attention(qkv.cuda(), 3)
+    finally:
+        ctx.opt("naive_attn", 0)
+    must = kern[S] if isinstance(kern, dict) else kern
+    assert ran == must, f"attention kernel {ran} ran, {must} must (D {D}, {S} tokens, naive_attn {mode})"
+    assert torch.isfinite(got).all() and torch.equal(got, again)
+    _close(got, want, what=f"attention D{D} S{S} mode {mode}")
+
+
 @pytest.mark.parametrize("pattern", ["ramp_up", "ramp_down", "spike_late", "flat", "huge_first"])
 @pytest.mark.parametrize("D", [32, 96, 128])
 def test_attention_lazy_softmax_reference(ctx, pattern, D):

@@ -35,6 +35,24 @@ def test_every_case_the_header_asserts_evaluates_the_same_here():
     assert ("WINO", 1152, 1152, 0, 16, 0, True, False) in cases and ("WINO", 1152, 1152, 0, 16, 0, False, True) in cases
 
 
+def test_every_plane_case_the_header_asserts_evaluates_the_same_here():
+    """The geometric clause -- H % 8, W % 16, the 8 x 8 pairs, max_hw -- over planes that are not square (kWinoPlaneCases)."""
+    cases = WR.header_plane_cases()
+    src = open(WR.HEADER).read()
+    body = src[src.index("kWinoPlaneCases[] = {"):src.index("constexpr WinoLaunch wino_plane_case_launch")]
+    assert len(cases) == body.count("{CF_") >= 20, (len(cases), body.count("{CF_"))                # every row parsed
+    assert "static_assert(first_wrong_wino_plane_case() == -1" in src
+    for fam, H, W, parts, Cin, want in cases:
+        assert WR.admits(fam, Cin, Cin, parts, (H, W)) == want, (fam, H, W, parts, Cin, want)
+    have = {c[:4] + (c[5],) for c in cases}
+    for must in (("WINO3", 8, 16, 1, True), ("WINO3", 16, 8, 1, False), ("WINO3", 24, 16, 1, True), ("WINO3", 12, 16, 1, False),
+                 ("WINO3", 128, 128, 1, True), ("WINO3", 128, 256, 1, False), ("WINO", 128, 256, 1, True), ("WINO3", 8, 16, 2, True)):
+        assert must in have, must
+    for fam in ("WINO", "WINO2H", "WINO1H", "WINO3", "WINO3P"):
+        assert (fam, 8, 8, 1, fam != "WINO3P") in have, fam
+    assert {c[5] for c in cases} == {True, False} and any(c[1] > c[2] for c in cases) and any(c[1] & (c[1] - 1) for c in cases if c[5])
+
+
 def test_room_for_the_parts_and_missing_weights():
     assert WR.admits("WINO3", 1056, parts=2, part_floats=2 * 2 * 32 * 64) and not WR.admits("WINO3", 1056, parts=2, part_floats=2 * 2 * 32 * 64 - 1)
     assert not WR.admits("WINO3", 1056, parts=2, part_floats=0) and WR.admits("WINO3", 512, parts=1, part_floats=0)

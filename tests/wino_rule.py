@@ -1,6 +1,6 @@
 """The admission rule of the Winograd 3x3 families (mcvd_pytorch_amd/csrc/conv_kernels.h: kWinoRules / wino_admits), restated once for the
-tests.  tests/test_wino_rule_cpu.py compares the rows below with the header's and evaluates every case the header static_asserts with
-admits(); the CPU walks (test_wide_conv_cpu, test_w288_cpu, test_wide_plane_cpu, test_f16_ksplit4_cpu) ask admits() what a launch takes.
+tests.  tests/test_wino_rule_cpu.py compares the rows below with the header's and evaluates every case the header static_asserts (kWinoCases,
+and kWinoPlaneCases for the planes that are not square) with admits(); tests/conv_ref.py asks it which id a forced launch ends in; the CPU walks (test_wide_conv_cpu, test_w288_cpu, test_wide_plane_cpu, test_f16_ksplit4_cpu) ask admits() what a launch takes.
 """
 import os
 import re
@@ -79,6 +79,14 @@ def header_rules():
     for fam, chunk, g8, hw, mc, sp, per in re.findall(r"\{CF_(\w+),\s*(\d+),\s*(true|false),\s*(\d+),\s*\{([\d, ]+)\},\s*(true|false),\s*(true|false)\}", body):
         rows[fam] = (int(chunk), g8 == "true", int(hw), tuple(int(v) for v in mc.split(",")), sp == "true", per == "true")
     return rows
+
+
+def header_plane_cases():
+    """[(family, H, W, parts, Cin, admitted)] parsed from kWinoPlaneCases, the header's static_asserted list of planes that are not square."""
+    src = open(HEADER).read()
+    body = src[src.index("kWinoPlaneCases[] = {"):src.index("constexpr WinoLaunch wino_plane_case_launch")]
+    return [(fam, int(h), int(w), int(parts), int(cin), ad == "true")
+            for fam, h, w, parts, cin, ad in re.findall(r"\{CF_(\w+),\s*(\d+),\s*(\d+),\s*(\d+),\s*(\d+),\s*(true|false)\}", body)]
 
 
 def header_cases():
