@@ -32,18 +32,15 @@
 //     prefetch behind the patch loads.  The wait points and the counts are spelled out at each use below.  The compiler does not
 //     know these registers are pending, so the build runs tools/check_wino_isa.py on the generated code (no read/copy/spill of
 //     a destination register before a vmcnt wait, no foreign VMEM in the loop) whenever this file is recompiled.
-//   * epilogue: per 32-cout sub-tile the 16 position planes go through LDS and every thread inverse-transforms one (cout, tile).
+//   * epilogue: per 32-cout sub-tile the 16 position planes go through LDS and every thread inverse-transforms one (cout, tile)
+//     (the output transform, like the vector types, SiLU and the launch helpers, is wino_common.h, shared with the three bf16 / fp16
+//     kernels; the exact (mean, M2) merge of the GroupNorm partials is this kernel's own).
 #include <stdlib.h>
 
 #include "../common.h"
+#include "wino_common.h"
 
 namespace mcvd {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float silu_wr(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 constexpr int WR_CK = 16;        // input channels per chunk (two 8-channel weight units)
 constexpr int WR_T = 32;         // tiles per workgroup (4 x 8 tiles = 8 x 16 output pixels)
@@ -230,7 +227,7 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(ConvArgs a) {
             float v = D[sl];                                                                                    \
             if (PRO >= 1) v = v * cfv[sl].x + cfv[sl].y;                                                        \
             if (PRO == 3) v = (v * (1.0f + gmv[sl]) + btv[sl]) * c2v[sl].x + c2v[sl].y;   /* spade_apply_kernel's order */ \
-            if (PRO >= 2) v = silu_wr(v);                                                                       \
+            if (PRO >= 2) v = wino_silu(v);                                                                       \
             sPw[p_lds[sl]] = (p_ci[sl] < min(nvalid, CK)) ? v : 0.0f;                                           \
         }                                                                                                       \
     }
@@ -496,14 +493,7 @@ __global__ __launch_bounds__(1024) void conv_wino_kernel(ConvArgs a) {
             float mm[16];
 #pragma unroll
             for (int xi = 0; xi < 16; ++xi) mm[xi] = sM[(xi * 32 + e_col) * T + e_tile];
-            float t0[4], t1[4];                                 // A^T M
-#pragma unroll
-            for (int l = 0; l < 4; ++l) {
-                t0[l] = mm[0 * 4 + l] + mm[1 * 4 + l] + mm[2 * 4 + l];
-                t1[l] = mm[1 * 4 + l] - mm[2 * 4 + l] - mm[3 * 4 + l];
-            }
-            float y00 = t0[0] + t0[1] + t0[2], y01 = t0[1] - t0[2] - t0[3];
-            float y10 = t1[0] + t1[1] + t1[2], y11 = t1[1] - t1[2] - t1[3];
+            WINO_OUT_TRANSFORM(mm)
             const float bvv = fin ? a.bias[co] : 0.0f;          // zero-padded to CoutP
             const float osc = fin ? a.out_scale : 1.0f;
             const float v00 = (y00 + bvv + r0.x) * osc, v01 = (y01 + bvv + r0.y) * osc;
@@ -636,14 +626,7 @@ static_assert(wino_lds_bytes(WINO_TABLE_CH_PLANE, false) <= 160 * 1024 && wino_l
 #ifdef MCVD_DIAG
 template <int EXP>
 static int wino_launch_exp1(const ConvArgs& k, dim3 grid, size_t lds, hipStream_t s) {
-    static PerDeviceOnce raised;
-    if (raised.first_use()) {
-        MCVD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_kernel<3, 2, false, EXP>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised.done();
-    }
-    hipLaunchKernelGGL((conv_wino_kernel<3, 2, false, EXP>), grid, dim3(WR_NT), lds, s, k);
-    return 0;
+    return wino_launch_kernel<conv_wino_kernel<3, 2, false, EXP>>(k, grid, WR_NT, lds, s);
 }
 static int wino_launch_exp(int e, const ConvArgs& k, dim3 grid, size_t lds, hipStream_t s) {
     switch (e) {
@@ -723,12 +706,6 @@ static int wino_launch3(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
     const int ksp = wino_kernel_parts(CF_WINO, a.ksplit);
     const size_t lds = wino_lds_bytes(wino_part_channels(a.CinP, ksp), G8, PRO == 3);
-    static PerDeviceOnce raised;
-    if (raised.first_use()) {
-        MCVD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino_kernel<COT, PRO, G8>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised.done();
-    }
     const dim3 grid = wino_grid(a, G8, BCO, ksp);
     ConvArgs k = a;
     if (k.dbg) k.wdma = 0;                 // wave 0 records its phase times
@@ -745,24 +722,8 @@ static int wino_launch3(const ConvArgs& a, hipStream_t s) {
         if (int rc = wino_launch_exp(exp_env, k, grid, lds, s)) return rc;
     } else
 #endif
-    hipLaunchKernelGGL((conv_wino_kernel<COT, PRO, G8>), grid, dim3(WR_NT), lds, s, k);
+    if (int rc = wino_launch_kernel<conv_wino_kernel<COT, PRO, G8>>(k, grid, WR_NT, lds, s)) return rc;
     return wino_launch_done(a, G8, ksp, s);
-}
-
-template <int COT, int PRO>
-static int wino_launch2(const ConvArgs& a, hipStream_t s) {
-    return (a.H == 8 && a.W == 8) ? wino_launch3<COT, PRO, true>(a, s) : wino_launch3<COT, PRO, false>(a, s);
-}
-
-template <int COT>
-static int wino_launch(const ConvArgs& a, hipStream_t s) {
-    if (a.gb) {
-        MCVD_REQUIRE(a.coef && a.act, "winograd conv: the SPADE prologue needs the GroupNorm coefficients and SiLU");
-        return wino_launch2<COT, 3>(a, s);
-    }
-    if (!a.coef && !a.act) return wino_launch2<COT, 0>(a, s);
-    if (!a.act) return wino_launch2<COT, 1>(a, s);
-    return wino_launch2<COT, 2>(a, s);
 }
 
 // Geometry the kernel serves: regions of 8 x 16 output pixels, or whole 8 x 8 images in pairs.
@@ -780,11 +741,8 @@ int launch_conv_wino(const ConvArgs& a, hipStream_t s) {
     if (int rc = conv_wino_require(CF_WINO, a, "winograd conv")) return rc;
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
-    switch (cot) {
-        case 1: return wino_launch<1>(a, s);
-        case 2: return wino_launch<2>(a, s);
-        default: return wino_launch<3>(a, s);
-    }
+    MCVD_REQUIRE(!a.gb || (a.coef && a.act), "winograd conv: the SPADE prologue needs the GroupNorm coefficients and SiLU");
+    return wino_dispatch<true>(a, cot, [&](auto COT, auto PRO, auto G8) { return wino_launch3<COT(), PRO(), G8()>(a, s); });
 }
 
 // U = G g G^T per (cout, cin), stored operand-major:

@@ -30,7 +30,9 @@
 //   * the MFMAs are inline asm (their A operand is a named register); the 3 * COT MFMAs of a position are ordered piece-major, so
 //     consecutive MFMAs target different accumulators.
 // VMEM of the K loop is hand-counted (inline asm loads + s_waitcnt vmcnt(N)) exactly as in conv_wino3.cpp; tools/check_wino_isa.py
-// checks the generated code of this file too.
+// checks the generated code of this file too.  The stage macros here have their own register map (v208 upward, two planes) and stay
+// in this file; the epilogue's task (output transform, 1 / scale, bias / residual, store, GroupNorm partial) and the launch helpers
+// are wino_common.h, shared with conv_wino3.cpp and conv_wino3p.cpp.
 //
 // ONE PIECE (template parameter NP = 1; shape ids 24 / 25 / 27, context option "f16x1", off by default): the same kernel with the second
 // piece of both operands dropped, each MFMA operand rounded to ONE fp16 value (11 significant bits, round to nearest even):
@@ -57,17 +59,9 @@
 #include <stdlib.h>
 
 #include "../common.h"
+#include "wino_common.h"
 
 namespace mcvd {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float silu_h2(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 constexpr int H2_CK = 16;        // input channels per chunk = K of one fp16 MFMA
 constexpr int H2_T = 32;         // tiles per workgroup (4 x 8 tiles = 8 x 16 output pixels)
@@ -316,7 +310,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
               "v"(cfv[3].x), "v"(cfv[3].y), "v"(cfv[4].x), "v"(cfv[4].y), "v"(cfv[5].x), "v"(cfv[5].y), "s"(vtok));       \
         _Pragma("unroll") for (int sl = 0; sl < MAXP; ++sl) {                                                   \
             float v = PV[sl];                                                                                   \
-            if (PRO >= 2) v = silu_h2(v);                                                                       \
+            if (PRO >= 2) v = wino_silu(v);                                                                       \
             sPw[p_pk[sl] & 0xfff] = ((int)((p_pk[sl] >> 12) & 0xff) < min(nvalid, CK)) ? v * H2_ACT_SCALE : 0.0f; \
             HOOK(sl, v)                                                                                         \
         }                                                                                                       \
@@ -597,66 +591,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(202))) void con
         for (int t2 = 0; t2 < 2; ++t2) {
             const int e_col = e_col0 + 16 * t2;
             const int co = co0 + ct * 32 + e_col;
-            const f32x2 r0 = e_r0[ct][t2], r1 = e_r1[ct][t2];
-            float mm[16];
-#pragma unroll
-            for (int xi = 0; xi < 16; ++xi) mm[xi] = sM[(xi * 32 + e_col) * T + e_tile];
-            float t0[4], t1[4];                                 // A^T M
-#pragma unroll
-            for (int l = 0; l < 4; ++l) {
-                t0[l] = mm[0 * 4 + l] + mm[1 * 4 + l] + mm[2 * 4 + l];
-                t1[l] = mm[1 * 4 + l] - mm[2 * 4 + l] - mm[3 * 4 + l];
-            }
-            const float y00 = t0[0] + t0[1] + t0[2], y01 = t0[1] - t0[2] - t0[3];
-            const float y10 = t1[0] + t1[1] + t1[2], y11 = t1[1] - t1[2] - t1[3];
-            const float bvv = e_bias[ct][t2];
-            const float osc = fin ? a.out_scale : 1.0f;
-            const float v00 = (y00 * inv + bvv + r0.x) * osc, v01 = (y01 * inv + bvv + r0.y) * osc;
-            const float v10 = (y10 * inv + bvv + r1.x) * osc, v11 = (y11 * inv + bvv + r1.y) * osc;
-            if (co < a.Cout && e_valid) {
-                const long o = ((long)e_b * a.Cout + co) * HW + pix;
-                *reinterpret_cast<float2*>(ydst + o) = make_float2(v00, v01);
-                *reinterpret_cast<float2*>(ydst + o + W) = make_float2(v10, v11);
-            }
-            if (a.stats && fin) {
-                // GroupNorm partials of the FINAL values (ConvArgs::stats): the tiles of this cout are the 32 lanes of a half-wave (G8:
-                // 16 lanes = one DPP row per image).  Pilot-shifted moments: with p = the group's first value (a sample of the
-                // distribution, so |mean - p| is a few sigma at most and M2 = q - s^2 / n loses a digit, not the result),
-                // s = sum (v - p) and q = sum (v - p)^2 merge by plain addition -- two v_add_f32 with a DPP source per level, where the
-                // exact (mean, M2) pairs of conv_wino.cpp cost eight instructions per level and a quarter of this epilogue.
-                float pil;
-                {
-                    const int pv = __builtin_bit_cast(int, v00);
-                    const int s0 = __builtin_amdgcn_readlane(pv, 0), s2 = __builtin_amdgcn_readlane(pv, 32);
-                    if (G8) {
-                        const int s1 = __builtin_amdgcn_readlane(pv, 16), s3 = __builtin_amdgcn_readlane(pv, 48);
-                        pil = __builtin_bit_cast(float, (lane & 32) ? ((lane & 16) ? s3 : s2) : ((lane & 16) ? s1 : s0));
-                    } else {
-                        pil = __builtin_bit_cast(float, (lane & 32) ? s2 : s0);
-                    }
-                }
-                const float d0 = v00 - pil, d1 = v01 - pil, d2 = v10 - pil, d3 = v11 - pil;
-                float sm = (d0 + d1) + (d2 + d3);
-                float qm = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-#define H2_MERGE(CTRL, ROWMASK)                                                                                     \
-                {                                                                                                   \
-                    sm += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sm), CTRL, ROWMASK, 0xf, false)); \
-                    qm += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, qm), CTRL, ROWMASK, 0xf, false)); \
-                }
-                H2_MERGE(0xB1, 0xf)                   // quad_perm [1,0,3,2]
-                H2_MERGE(0x4E, 0xf)                   // quad_perm [2,3,0,1]
-                H2_MERGE(0x124, 0xf)                  // row_ror:4
-                H2_MERGE(0x128, 0xf)                  // row_ror:8: every lane of a row of 16 holds the row's totals
-                if (!G8) H2_MERGE(0x142, 0xa)         // row_bcast:15: lanes 16-31 / 48-63 add the totals of the row below
-#undef H2_MERGE
-                const bool writer = G8 ? (e_tile & 15) == 0 : e_tile == 31;
-                if (writer && co < a.Cout && e_valid) {
-                    constexpr float NPIX = G8 ? 64.0f : 128.0f;
-                    float* q = a.stats + (((long)e_b * a.Cout + co) * (rx_n * ry_n) + rr) * 2;
-                    q[0] = sm + NPIX * pil;           // the partial's sum over its pixels
-                    q[1] = fmaxf(qm - sm * sm * (1.0f / NPIX), 0.0f);      // M2 about the partial's own mean
-                }
-            }
+            WINO_EPILOGUE_TASK(G8, false, sM, sM, inv, e_bias[ct][t2], e_r0[ct][t2], e_r1[ct][t2], e_b, e_valid, rx_n * ry_n, rr)
         }
         if (ct + 1 < COT) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
@@ -711,18 +646,6 @@ static_assert(wino2h_lds_bytes(2, WINO_TABLE_CH, true) == 124960 && wino2h_lds_b
 static_assert(wino2h_lds_bytes(2, WINO_TABLE_CH_PLANE, false) == 124960 && wino2h_lds_bytes(1, WINO_TABLE_CH_PLANE, false) == 92192,
               "a plane's table of WINO_TABLE_CH_PLANE channels, two pieces and one");
 
-template <int NP, int COT, int PRO, bool G8, int EXP>
-static int wino2h_launch_k(const ConvArgs& k, dim3 grid, size_t lds, hipStream_t s) {
-    static PerDeviceOnce raised;
-    if (raised.first_use()) {
-        MCVD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino2h_kernel<NP, COT, PRO, G8, EXP>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised.done();
-    }
-    hipLaunchKernelGGL((conv_wino2h_kernel<NP, COT, PRO, G8, EXP>), grid, dim3(H2_NT), lds, s, k);
-    return 0;
-}
-
 template <int NP, int COT, int PRO, bool G8>
 static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
@@ -731,7 +654,7 @@ static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
     const dim3 grid = wino_grid(a, G8, BCO, ksp);
     int rc = 0;
     if constexpr (NP == 1) {               // no recording, no ablations (DIAG in the kernel): the caller's arguments as they come
-        rc = wino2h_launch_k<1, COT, PRO, G8, 0>(a, grid, lds, s);
+        rc = wino_launch_kernel<conv_wino2h_kernel<1, COT, PRO, G8, 0>>(a, grid, H2_NT, lds, s);
     } else {
         ConvArgs k = a;
         if (k.dbg) k.wdma = 0;             // wave 0 records its phase times
@@ -746,35 +669,23 @@ static int wino2h_launch2(const ConvArgs& a, hipStream_t s) {
         const int e = exp_s ? atoi(exp_s) : 0;
         if (COT == 3 && PRO == 2 && !G8 && e != 0) {           // tests/gpu_diag.py w3exp
             switch (e) {
-                case 1: rc = wino2h_launch_k<2, 3, 2, false, 1>(k, grid, lds, s); break;        // no transform
-                case 2: rc = wino2h_launch_k<2, 3, 2, false, 2>(k, grid, lds, s); break;        // no patch activation / park
-                case 3: rc = wino2h_launch_k<2, 3, 2, false, 3>(k, grid, lds, s); break;        // neither
-                case 4: rc = wino2h_launch_k<2, 3, 2, false, 4>(k, grid, lds, s); break;        // no VMEM in the loop
-                case 16: rc = wino2h_launch_k<2, 3, 2, false, 16>(k, grid, lds, s); break;      // everything but the MFMAs
-                case 15: rc = wino2h_launch_k<2, 3, 2, false, 15>(k, grid, lds, s); break;      // MFMA only
-                case 27: rc = wino2h_launch_k<2, 3, 2, false, 27>(k, grid, lds, s); break;      // VMEM only
-                case 11: rc = wino2h_launch_k<2, 3, 2, false, 11>(k, grid, lds, s); break;      // VMEM + MFMA only
+                case 1: rc = wino_launch_kernel<conv_wino2h_kernel<2, 3, 2, false, 1>>(k, grid, H2_NT, lds, s); break;        // no transform
+                case 2: rc = wino_launch_kernel<conv_wino2h_kernel<2, 3, 2, false, 2>>(k, grid, H2_NT, lds, s); break;        // no patch activation / park
+                case 3: rc = wino_launch_kernel<conv_wino2h_kernel<2, 3, 2, false, 3>>(k, grid, H2_NT, lds, s); break;        // neither
+                case 4: rc = wino_launch_kernel<conv_wino2h_kernel<2, 3, 2, false, 4>>(k, grid, H2_NT, lds, s); break;        // no VMEM in the loop
+                case 16: rc = wino_launch_kernel<conv_wino2h_kernel<2, 3, 2, false, 16>>(k, grid, H2_NT, lds, s); break;      // everything but the MFMAs
+                case 15: rc = wino_launch_kernel<conv_wino2h_kernel<2, 3, 2, false, 15>>(k, grid, H2_NT, lds, s); break;      // MFMA only
+                case 27: rc = wino_launch_kernel<conv_wino2h_kernel<2, 3, 2, false, 27>>(k, grid, H2_NT, lds, s); break;      // VMEM only
+                case 11: rc = wino_launch_kernel<conv_wino2h_kernel<2, 3, 2, false, 11>>(k, grid, H2_NT, lds, s); break;      // VMEM + MFMA only
                 default: mcvd::set_error("MCVD_WINO2H_EXP=%d is not a built ablation", e); return -1;
             }
         } else
 #endif
         {
-            rc = wino2h_launch_k<2, COT, PRO, G8, 0>(k, grid, lds, s);
+            rc = wino_launch_kernel<conv_wino2h_kernel<2, COT, PRO, G8, 0>>(k, grid, H2_NT, lds, s);
         }
     }
     return rc ? rc : wino_launch_done(a, G8, ksp, s);
-}
-
-template <int NP, int COT, bool G8>
-static int wino2h_launch1(const ConvArgs& a, hipStream_t s) {
-    if (!a.coef && !a.act) return wino2h_launch2<NP, COT, 0, G8>(a, s);
-    if (!a.act) return wino2h_launch2<NP, COT, 1, G8>(a, s);
-    return wino2h_launch2<NP, COT, 2, G8>(a, s);
-}
-
-template <int NP, int COT>
-static int wino2h_launch(const ConvArgs& a, hipStream_t s) {
-    return (a.H == 8 && a.W == 8) ? wino2h_launch1<NP, COT, true>(a, s) : wino2h_launch1<NP, COT, false>(a, s);
 }
 
 // Shape ids 12 / 13 / 26 (two pieces) and 24 / 25 / 27 (one piece): one row of the rule for both piece counts.
@@ -786,11 +697,7 @@ static int wino2h_launch_np(const ConvArgs& a, hipStream_t s) {
     if (int rc = conv_wino_require(NP == 1 ? CF_WINO1H : CF_WINO2H, a, NP == 1 ? "winograd f16x1 conv" : "winograd f16x2 conv")) return rc;
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd f16x%d conv: CoutP=%d vs tile %d", NP, a.CoutP, 32 * cot);
-    switch (cot) {
-        case 1: return wino2h_launch<NP, 1>(a, s);
-        case 2: return wino2h_launch<NP, 2>(a, s);
-        default: return wino2h_launch<NP, 3>(a, s);
-    }
+    return wino_dispatch(a, cot, [&](auto COT, auto PRO, auto G8) { return wino2h_launch2<NP, COT(), PRO(), G8()>(a, s); });
 }
 
 // a.wph: the layout of launch_pack_wino2h_weight, packed for conv_wino_cout_tile(Cout).  np: operand pieces, 2 or 1 (one: the first piece is read).

@@ -20,7 +20,7 @@
 // owns positions 2w and 2w+1):
 //   * weights: [cout tile][chunk][position][cout sub-tile][piece][64 lanes][4 dwords], a dword = two bf16 = K slots (2j, 2j+1)
 //     of the lane's half; the 6*COT quads a wave needs per chunk are one contiguous block, fetched with global_load_dwordx4
-//     STRAIGHT INTO THE MFMA A-OPERAND REGISTERS (named registers the compiler does not allocate, v184-v255: see W3_LOAD_A) and
+//     STRAIGHT INTO THE MFMA A-OPERAND REGISTERS (named registers the compiler does not allocate, v184-v255: conv_wino3_stage.h) and
 //     reloaded for the next chunk as soon as the position's MFMAs have been issued: prefetch distance = one chunk.
 //   * K-slot convention of the 32x32x16 MFMA (both operands): lane half h, element e  <->  channel 2e + h of the chunk.
 //   * activations: raw patch fetched four pixels per lane (global_load_dwordx4) + one halo pixel, activated and parked in LDS with the
@@ -32,52 +32,19 @@
 //     smallest product first, so consecutive MFMAs target different accumulators.
 // VMEM of the K loop is hand-counted (inline asm loads + s_waitcnt vmcnt(N)) exactly as in conv_wino2h.cpp; tools/check_wino_isa.py
 // checks the generated code of this file too.
+//
+// The stage of one chunk -- constants, the named-register map, the macros that load, park, transform and multiply it -- is
+// conv_wino3_stage.h, one text for this kernel and the persistent one (conv_wino3p.cpp).  This file keeps the chunk loop, the prologue,
+// the coefficient table's index relative to the K part (W3_READ_C) and the per-phase clock stamps.  The epilogue's task (output
+// transform, bias / residual / scale, store, GroupNorm partial) and the launch helpers are wino_common.h, shared with conv_wino2h.cpp.
 #include <stdlib.h>
 
 #include "../common.h"
+#include "conv_wino3_stage.h"
 
 namespace mcvd {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float silu_w3(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-
-constexpr int W3_CK = 16;        // input channels per chunk = K of one bf16 MFMA
-constexpr int W3_T = 32;         // tiles per workgroup (4 x 8 tiles = 8 x 16 output pixels)
-constexpr int W3_NT = 512;
-#ifndef MCVD_W3_PP
-#define MCVD_W3_PP 24
-#endif
-// LDS patch row pitch in channel-pair columns (18 used; 20 for the two 8x8 images side by side).  The patch park stores a lane's four pixels as
-// single dwords at ((pair * 10 + row) * PP + col) * 2 + ce; the 32 lanes of a store group are 8 rows x 4 four-pixel items, bank = (row * 2 PP +
-// 8 item) mod 32: with 2 PP = 48 = 16 (mod 32) they fall on FOUR banks -- the "x4 patch park" conflict behind 27-29 percent of the LDS-active
-// cycles (profiles/r04_pmc_sq_wave_states.txt).  Round 5 built the conflict-free pitch (25: 2 PP = 18 mod 32, 16 banks, 2-way = free for
-// ds_write_b32) and measured it against 24 on one box (tools/build_variant.sh, -DMCVD_W3_PP=25; profiles/r05_patch_pitch_ab.txt): 5577 vs 5592
-// cycles per chunk, 248.1 / 248.5 vs 248.8 / 249.4 frames/s -- nothing.  The stores are not on the chunk's critical path; 24 stays.
-constexpr int W3_PP = MCVD_W3_PP;
-constexpr int W3_PW = 16 * 2 * 4 * W3_T;          // 32-bit words of one piece plane of a V chunk: [position][half][pair][tile]
-constexpr int W3_VW = 3 * W3_PW;                  // 32-bit words of one V chunk: [piece][position][half][pair][tile]
-
-// (lo, hi) -> packed bf16 pair, round to nearest even (v_cvt_pk_bf16_f32)
-__device__ __forceinline__ unsigned w3_cvt_pk(float lo, float hi) {
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-// exact three-way split of an adjacent register pair into packed bf16 pairs (w1 the leading pieces): the two subtractions of a
-// level are one v_pk_add_f32
-__device__ __forceinline__ void w3_split3(f32x2 v, unsigned& w1, unsigned& w2, unsigned& w3) {
-    w1 = w3_cvt_pk(v.x, v.y);
-    const f32x2 h = {__builtin_bit_cast(float, w1 << 16), __builtin_bit_cast(float, w1 & 0xffff0000u)};
-    v = v - h;
-    w2 = w3_cvt_pk(v.x, v.y);
-    const f32x2 g = {__builtin_bit_cast(float, w2 << 16), __builtin_bit_cast(float, w2 & 0xffff0000u)};
-    v = v - g;
-    w3 = w3_cvt_pk(v.x, v.y);
-}
+#define W3_SLOT_OFF(word) (word)         // the slot table holds plain byte offsets here
 
 // PRO: 0 raw input, 1 affine, 2 affine + SiLU (the GroupNorm / temb prologue of conv_wino.cpp)
 // a.ksplit == 2 / 4 / 8 (grid.y = that many): one part of the input channels per workgroup, raw partial result to a.part[part]; the reduce
@@ -89,7 +56,7 @@ __device__ __forceinline__ void w3_split3(f32x2 v, unsigned& w1, unsigned& w2, u
 //     fetch a dummy) and the halo of both patch buffers is zeroed once.  The coefficient table holds both samples.
 template <int COT, int PRO, bool G8, int EXP = 0>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv_wino3_kernel(ConvArgs a) {
-    // amdgpu_num_vgpr(86): the compiler may allocate v0-v171; v172-v255 hold the in-flight loads and the A operands (W3_LOAD_A).
+    // amdgpu_num_vgpr(86): the compiler may allocate v0-v171; v172-v255 hold the in-flight loads and the A operands (conv_wino3_stage.h).
     // On gfx90a+ LLVM DOUBLES the requested number (unified VGPR + AGPR file) before it checks it against the occupancy bound and
     // drops it silently when the doubled value exceeds 256: amdgpu_num_vgpr(172) would be ignored, amdgpu_num_vgpr(86) caps the
     // allocator at 172 registers (this kernel uses no AGPRs).  tools/check_wino_isa.py verifies the outcome on the generated code.
@@ -106,9 +73,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     constexpr int NPV = G8 ? 4 : 9;                             // values they bring
     constexpr int NQ = 3 * COT;                                 // weight quads per position: COT cout sub-tiles x 3 pieces
     constexpr int NA = 2 * NQ;                                  // weight loads per wave and chunk
-    constexpr int VM_A = NQ + NPL;                              // see W3_MFMA_PHASE
+    constexpr int VM_A = NQ + NPL;                              // see W3_MFMA_PHASE (conv_wino3_stage.h)
     constexpr int PQ = 5;                                       // weight quads whose registers hold the first two patches in the prologue
-    static_assert(NA <= 18 && NA > PQ, "named-register map below: v172-v180 patch, v184-v255 eighteen weight quads");
+    static_assert(NA <= 18 && NA > PQ, "named-register map of conv_wino3_stage.h: v172-v180 patch, v184-v255 eighteen weight quads");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned* sV = reinterpret_cast<unsigned*>(smem);           // [2][VW]
     float* sP = smem + 2 * VW;                  // [2][PBUF]
@@ -221,59 +188,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     const unsigned* wr_base = reinterpret_cast<const unsigned*>(a.wpb) + ((long)cotile * (a.CinP / CK) * 16 + 2 * wave_u) * (NQ * 256);
     const unsigned wr_voff = (unsigned)lane * 16u;
 
-    /* IN-FLIGHT DATA LIVES IN REGISTERS THE COMPILER DOES NOT ALLOCATE.  The kernel is compiled with amdgpu_num_vgpr(86): v172-v255 are
-       never touched by generated code.  The asm loads write them (weight quad q: v[184 + 4q : 187 + 4q]; patch slots: v[172:175], v[176:179], v180), the
-       waits are bare s_waitcnt, the MFMAs name their A operand in the instruction text.  (Loads whose results are compiler-visible
-       values are not safe here: the register allocator may assign the result and the operand of the later wait to different registers
-       and copy between them while the load is still in flight -- it did, a wrong result once in ~10^4 launches.)
-       Every statement that touches a named register is `asm volatile` (program order among them is kept) except the patch FMAs, which
-       take the wait's token (an SGPR) as an operand. */
-#define W3_QUADS(X, q, A1, A2) X(0, "v[184:187]", q, A1, A2) X(1, "v[188:191]", q, A1, A2) X(2, "v[192:195]", q, A1, A2) X(3, "v[196:199]", q, A1, A2) X(4, "v[200:203]", q, A1, A2) X(5, "v[204:207]", q, A1, A2) X(6, "v[208:211]", q, A1, A2) X(7, "v[212:215]", q, A1, A2) X(8, "v[216:219]", q, A1, A2) X(9, "v[220:223]", q, A1, A2) X(10, "v[224:227]", q, A1, A2) X(11, "v[228:231]", q, A1, A2) X(12, "v[232:235]", q, A1, A2) X(13, "v[236:239]", q, A1, A2) X(14, "v[240:243]", q, A1, A2) X(15, "v[244:247]", q, A1, A2) X(16, "v[248:251]", q, A1, A2) X(17, "v[252:255]", q, A1, A2)
-#define W3_LD1(K, R, q, P, UNUSED) if ((q) == K) asm volatile("global_load_dwordx4 " R ", %0, %1" :: "v"(wr_voff), "s"(P) : "memory");
-#define W3_MF1(K, R, q, ACC, BV) if ((q) == K) asm volatile("v_mfma_f32_32x32x16_bf16 %0, " R ", %1, %0" : "+v"(ACC) : "v"(BV));
-    /* the NQ weight quads of position 2w + i of chunk `ch` */
-#define W3_LOAD_A(ch, i)                                                                                        \
-    {                                                                                                           \
-        const unsigned* ua = wr_base + (long)(ch) * (16 * NQ * 256) + (i) * (NQ * 256);                         \
-        _Pragma("unroll") for (int qq = 0; qq < NQ; ++qq) { W3_QUADS(W3_LD1, (i) * NQ + qq, ua + qq * 256, 0) } \
-    }
-    /* weight piece `pc` of every cout sub-tile of position 2w + i of chunk `ch` (quads (i * COT + ct) * 3 + pc) */            \
-#define W3_LOAD_A_PIECE(ch, i, pc)                                                                              \
-    {                                                                                                           \
-        const unsigned* ua = wr_base + (long)(ch) * (16 * NQ * 256) + (i) * (NQ * 256);                         \
-        _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { W3_QUADS(W3_LD1, (i) * NQ + ct * 3 + (pc), ua + (ct * 3 + (pc)) * 256, 0) } \
-    }
-    /* prologue: quads Q0 .. Q1-1 of chunk `ch`, issued behind the instructions that produced DEP (which read the registers) */
-#define W3_LD1D(K, R, q, P, DEP) if ((q) == K) asm volatile("global_load_dwordx4 " R ", %0, %1" :: "v"(wr_voff), "s"(P), "v"(DEP) : "memory");
-#define W3_LOAD_A_RANGE(ch, Q0, Q1, DEP)                                                                        \
-    {                                                                                                           \
-        const unsigned* ua = wr_base + (long)(ch) * (16 * NQ * 256);                                            \
-        _Pragma("unroll") for (int qq = (Q0); qq < (Q1); ++qq) { W3_QUADS(W3_LD1D, qq, ua + qq * 256, DEP) }    \
-    }
-#define W3_WAIT(N) asm volatile("s_waitcnt vmcnt(%1)\n\ts_mov_b32 %0, 0" : "=s"(vtok) : "n"(N) : "memory");
-    /* unconditional, clamped raw loads of the patch of chunk `ch`: RA / RB = the two four-pixel slots, RH = the halo slot; DEP = a value
-       computed from the previous contents of those registers (ordering) */
+    // the chunk's stage -- the named registers v172-v255 and the W3_ macros that load, park, transform and multiply -- is
+    // conv_wino3_stage.h; W3_WCHUNK: the wave's weights of chunk `ch`
+#define W3_WCHUNK(ch) (wr_base + (long)(ch) * (16 * NQ * 256))
 #define W3_READ_OFF(OFS) { _Pragma("unroll") for (int sl = 0; sl < NPL; ++sl) OFS[sl] = sOff[sl * NT + tid]; }
-#define W3_LOAD_P(ch, DEP, OFS) W3_LOAD_PR(ch, DEP, OFS, "v[172:175]", "v[176:179]", "v180")
-#define W3_LOAD_PR(ch, DEP, OFS, RA, RB, RH)                                                                    \
-    {                                                                                                           \
-        const int cb = min((ch) * CK, Cin - 1);                                                                 \
-        const unsigned lim4 = (unsigned)((Cin - cb) * HW - 4) * 4u, lim1 = (unsigned)((Cin - cb) * HW - 1) * 4u; \
-        const bool second = cb >= a.C0;                                                                         \
-        const float* srcb = second ? a.x1 + ((long)b * a.C1 + (cb - a.C0)) * HW : a.x0 + ((long)b * a.C0 + cb) * HW; \
-        const unsigned istride = (unsigned)((second ? a.C1 : a.C0) * HW) * 4u;      /* G8: distance to the region's second sample */ \
-        /* channels past the last one are zeroed at the write: any (aligned) address inside the source will do */ \
-        if constexpr (G8) {                                                                                     \
-            const unsigned o0 = min(OFS[0], lim4) + ((p_pk[0] >> 20) & 1u) * istride;                           \
-            asm volatile("global_load_dwordx4 " RA ", %0, %1" :: "v"(o0), "s"(srcb), "v"(DEP) : "memory");     \
-        } else {                                                                                                \
-            const unsigned o0 = min(OFS[0], lim4), o1 = min(OFS[NPL > 1 ? 1 : 0], lim4), o2 = min(OFS[NPL > 2 ? 2 : 0], lim1); \
-            asm volatile("global_load_dwordx4 " RA ", %0, %3\n\tglobal_load_dwordx4 " RB ", %1, %3\n\tglobal_load_dword " RH ", %2, %3" \
-                         :: "v"(o0), "v"(o1), "v"(o2), "s"(srcb), "v"(DEP) : "memory");                           \
-        }                                                                                                       \
-    }
-    /* activate once per pixel (coefficients from the LDS table: one pair per slot, a slot is one channel) and park the patch in LDS;  \
-       zero padding applies AFTER the activation */                                                                \
 #define W3_READ_C(ch, cfv)                                                                                      \
     {                                                                                                           \
         _Pragma("unroll") for (int sl = 0; sl < NPL; ++sl) {                                                    \
@@ -283,105 +201,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
                 const int cch = min(((ch) - c_begin) * CK + (int)((p_pk[sl] >> 12) & (CK - 1)), PC - 1) + (G8 ? (int)((p_pk[sl] >> 20) & 1u) * PC : 0); \
                 cfv[sl] = *reinterpret_cast<const f32x2*>(sCo + cch * 2);                                       \
             }                                                                                                   \
-        }                                                                                                       \
-    }
-#define W3_NOHOOK(e, v)
-#define W3_WRITE_P(ch, PV, cfv) W3_WRITE_PR(ch, PV, cfv, "v172", "v173", "v174", "v175", "v176", "v177", "v178", "v179", "v180", W3_NOHOOK)
-    /* HOOK(e, v): statements placed behind value e (the prologue issues its weight loads there, one at a time) */ \
-#define W3_WRITE_PR(ch, PV, cfv, A0, A1, A2, A3, B0, B1, B2, B3, H0, HOOK)                                      \
-    {                                                                                                           \
-        float* sPw = sP + (((ch) & 1) ? PBUF : 0);                                                              \
-        const int nvalid = Cin - (ch) * CK;                                                                     \
-        /* v = A * raw + B straight out of the patch registers (PRO 0: A = 1, B = 0, exact): the only reads of those registers */ \
-        if constexpr (G8) {                                                                                     \
-            asm("v_fma_f32 %0, " A0 ", %4, %5\n\tv_fma_f32 %1, " A1 ", %4, %5\n\tv_fma_f32 %2, " A2 ", %4, %5\n\tv_fma_f32 %3, " A3 ", %4, %5" \
-                : "=&v"(PV[0]), "=&v"(PV[1]), "=&v"(PV[2]), "=&v"(PV[3]) : "v"(cfv[0].x), "v"(cfv[0].y), "s"(vtok)); \
-        } else {                                                                                                \
-            asm("v_fma_f32 %0, " A0 ", %9, %10\n\tv_fma_f32 %1, " A1 ", %9, %10\n\tv_fma_f32 %2, " A2 ", %9, %10\n\tv_fma_f32 %3, " A3 ", %9, %10\n\t" \
-                "v_fma_f32 %4, " B0 ", %11, %12\n\tv_fma_f32 %5, " B1 ", %11, %12\n\tv_fma_f32 %6, " B2 ", %11, %12\n\tv_fma_f32 %7, " B3 ", %11, %12\n\t" \
-                "v_fma_f32 %8, " H0 ", %13, %14"                                                                  \
-                : "=&v"(PV[0]), "=&v"(PV[1]), "=&v"(PV[2]), "=&v"(PV[3]), "=&v"(PV[4]), "=&v"(PV[5]), "=&v"(PV[6]), "=&v"(PV[7]), "=&v"(PV[NPV > 8 ? 8 : 0]) \
-                : "v"(cfv[0].x), "v"(cfv[0].y), "v"(cfv[NPL > 1 ? 1 : 0].x), "v"(cfv[NPL > 1 ? 1 : 0].y), "v"(cfv[NPL > 2 ? 2 : 0].x), \
-                  "v"(cfv[NPL > 2 ? 2 : 0].y), "s"(vtok));                                                        \
-        }                                                                                                       \
-        _Pragma("unroll") for (int e = 0; e < NPV; ++e) {                                                       \
-            const int sl = e >> 2;                            /* values 0-3: slot 0, 4-7: slot 1, 8: slot 2 */   \
-            float v = PV[e];                                                                                    \
-            if (PRO >= 2) v = silu_w3(v);                                                                       \
-            sPw[(p_pk[sl] & 0xfff) + 2 * (e & 3)] = ((int)((p_pk[sl] >> 12) & 0xff) < min(nvalid, CK)) ? v : 0.0f; \
-            HOOK(e, v)                                                                                          \
-        }                                                                                                       \
-    }
-    /* rows 2rg and 2rg+1 of B^T d for the two channels of the pair (packed fp32: .x = channel s_ca, .y = s_ca + 2), (.) B,      \
-       three-way bf16 split, 24 stores:                                                                                      \
-       row 0: d0 - d2   row 1: d1 + d2   row 2: d2 - d1   row 3: d1 - d3;   (.) B: m0 - m2, m1 + m2, m2 - m1, m1 - m3 */      \
-#define W3_READ_R(ch, RW)                                                                                       \
-    {                                                                                                           \
-        const f32x2* sPr = reinterpret_cast<const f32x2*>(sP + (((ch) & 1) ? PBUF : 0) + p_rd);                 \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) { RW[0][j] = sPr[j]; RW[1][j] = sPr[PP + j]; RW[2][j] = sPr[2 * PP + j]; } \
-    }
-#define W3_WRITE_V(ch, RG, RW)                                                                                  \
-    {                                                                                                           \
-        unsigned* vdst = sV + (((ch) & 1) ? VW : 0) + v_wr;                                                     \
-        f32x2 mx[4], my[4];                                                                                     \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                         \
-            const f32x2 r0 = RW[0][j], r1 = RW[1][j], r2 = RW[2][j];                                            \
-            if ((RG) == 0) { mx[j] = r0 - r2; my[j] = r1 + r2; }                                                \
-            else { mx[j] = r1 - r0; my[j] = r0 - r2; }                                                          \
-        }                                                                                                       \
-        _Pragma("unroll") for (int row = 0; row < 2; ++row) {                                                   \
-            const f32x2 m0 = row ? my[0] : mx[0], m1 = row ? my[1] : mx[1], m2 = row ? my[2] : mx[2], m3 = row ? my[3] : mx[3]; \
-            const f32x2 v0 = m0 - m2, v1 = m1 + m2, v2 = m2 - m1, v3 = m1 - m3;                                 \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                     \
-                unsigned w1, w2, w3;                                                                            \
-                w3_split3(q == 0 ? v0 : q == 1 ? v1 : q == 2 ? v2 : v3, w1, w2, w3);                            \
-                vdst[(row * 4 + q) * 256] = w1;                                                                 \
-                vdst[(row * 4 + q) * 256 + PW] = w2;                                                            \
-                vdst[(row * 4 + q) * 256 + 2 * PW] = w3;                                                        \
-            }                                                                                                   \
-        }                                                                                                       \
-    }
-    /* B operand of position 2w+i -> BQ[piece][pair]  <-  word (((p*16 + pos)*2 + half)*4 + jp)*T + l31 */
-#define W3_LOAD_B(i, BQ)                                                                                        \
-    {                                                                                                           \
-        const unsigned* q = sVc + (((2 * wave + (i)) * 2 + half) * 4) * T + l31;                                \
-        _Pragma("unroll") for (int jp = 0; jp < 4; ++jp) {                                                      \
-            BQ[0][jp] = q[jp * T]; BQ[1][jp] = q[PW + jp * T]; BQ[2][jp] = q[2 * PW + jp * T];                  \
-        }                                                                                                       \
-    }
-    /* the COT MFMAs of one piece product (weight piece PA x activation piece PB) of position 2w + i */
-#define W3_PRODUCT(i, PA, PB)                                                                                   \
-    { _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { W3_QUADS(W3_MF1, 3 * ((i) * COT + ct) + (PA), acc[i][ct], bq[i][PB]) } }
-    /* all MFMAs of chunk `ch` (V(ch) in LDS, weights(ch) in the named registers).  Per position 2w + i: wait for its NQ quads, 6*COT  \
-       MFMAs ordered product-major (u3 v1, u2 v2, u1 v3, u2 v1, u1 v2, u1 v1: smallest class first; consecutive MFMAs write different \
-       accumulators), and -- NEXT -- the same NQ quads are reloaded for chunk ch+1 piece by piece (the matrix pipe has read its A operands by the     \
-       time the wave gets past the MFMA: it issues in order).  In-order VMEM bookkeeping: when the quads of a position are needed, the \
-       loads issued after them are the other position's NQ quads and one patch group: vmcnt(NQ + NPL), in both phase orders. */      \
-#define W3_MFMA_PHASE(ch, NEXT)                                                                                 \
-    {                                                                                                           \
-        const unsigned* sVc = sV + (((ch) & 1) ? VW : 0);                                                       \
-        u32x4 bq[2][3];                                                                                         \
-        W3_TS(7)                                                                                                \
-        if (!(EXP & 8)) { W3_LOAD_B(0, bq[0]) W3_LOAD_B(1, bq[1]) }                                             \
-        else { _Pragma("unroll") for (int p = 0; p < 3; ++p) { bq[0][p] = u32x4{1, 2, 3, 4}; bq[1][p] = u32x4{5, 6, 7, 8}; } } \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
-            if (NEXT && !(EXP & 4)) W3_WAIT(VM_A)                                                               \
-            if (!(EXP & 16)) {                                                                                  \
-                /* a weight piece is re-requested for chunk ch+1 as soon as its LAST product has been issued: u3 behind the first    \
-                   product, u2 behind the fourth, u1 behind the sixth -- three requests at a time, spread over the position's 576   \
-                   cycles of matrix work (nine in one burst stall the wave in the issue: the CU's vector-memory path is 70 % busy) */ \
-                W3_PRODUCT(i, 2, 0)                                                                             \
-                if (NEXT && !(EXP & 4)) W3_LOAD_A_PIECE((ch) + 1, i, 2)                                         \
-                W3_PRODUCT(i, 1, 1) W3_PRODUCT(i, 0, 2) W3_PRODUCT(i, 1, 0)                                     \
-                if (NEXT && !(EXP & 4)) W3_LOAD_A_PIECE((ch) + 1, i, 1)                                         \
-                W3_PRODUCT(i, 0, 1) W3_PRODUCT(i, 0, 0)                                                         \
-                if (NEXT && !(EXP & 4)) W3_LOAD_A_PIECE((ch) + 1, i, 0)                                         \
-            } else {                                                                                            \
-                _Pragma("unroll") for (int ct = 0; ct < COT; ++ct)                                              \
-                    acc[i][ct][0] += __builtin_bit_cast(float, bq[i][0][0] ^ bq[i][1][1] ^ bq[i][2][2] ^ bq[i][1][3]); \
-                if (NEXT && !(EXP & 4)) W3_LOAD_A((ch) + 1, i)                                                  \
-            }                                                                                                   \
-            W3_TS(4 + i)                                                                                        \
         }                                                                                                       \
     }
     /* patch of chunk ch+2 -> LDS, raw patch of chunk ch+3 requested, V(ch+1) -> LDS.  Two LDS round trips (coefficients + load offsets,   \
@@ -399,15 +218,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
             W3_TS(0)                                                                                            \
             float pv[NPV];                                                                                      \
             _Pragma("unroll") for (int e = 0; e < NPV; ++e) pv[e] = 0.0f;                                       \
-            if (!(EXP & 2)) W3_WRITE_P((ch) + 2, pv, cfv)                                                       \
+            if (!(EXP & 2)) W3_WRITE_P(((ch) + 2) & 1, Cin - ((ch) + 2) * CK, 0u, pv, cfv)                      \
             W3_TS(1)                                                                                            \
-            if (!(EXP & 4)) W3_LOAD_P((ch) + 3, pv[0], ofs)                                                     \
+            if (!(EXP & 4)) W3_LOAD_P(b, (ch) + 3, pv[0], ofs)                                                  \
             W3_TS(2)                                                                                            \
         }                                                                                                       \
         if (!(EXP & 1)) {                                                                                       \
             f32x2 rw[3][4];                                                                                     \
-            W3_READ_R((ch) + 1, rw)                                                                             \
-            W3_WRITE_V((ch) + 1, RG, rw)                                                                        \
+            W3_READ_R(((ch) + 1) & 1, rw)                                                                       \
+            W3_WRITE_V(((ch) + 1) & 1, RG, rw)                                                                  \
         }                                                                                                       \
         W3_TS(3)                                                                                                \
     }
@@ -464,8 +283,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
         // VMEM issue order = need order.  Round 3's first form fetched the coefficients with ordinary loads and parked them before
         // anything else was requested: a full memory latency (2-3 k cycles under load) in front of every workgroup's first patch.
         // the first two patches land in the registers of weight quads 0 .. PQ-1 (v184-v203)
-        W3_LOAD_PR(c_begin, nodep, ofs, "v[184:187]", "v[188:191]", "v192")
-        W3_LOAD_PR(c_begin + 1, nodep, ofs, "v[194:197]", "v[198:201]", "v202")
+        W3_LOAD_PR(b, c_begin, nodep, ofs, "v[184:187]", "v[188:191]", "v192")
+        W3_LOAD_PR(b, c_begin + 1, nodep, ofs, "v[194:197]", "v[198:201]", "v202")
         if (G8)                            // the halo of both patch buffers is zero padding for the whole kernel
             for (int i = tid; i < 2 * PBUF; i += NT) sP[i] = 0.0f;
         if (rec) sp[0] = __builtin_amdgcn_s_memtime() - tk0;      // loads issued
@@ -487,7 +306,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
                 }
             cdep = cpre[0].x + cpre[1].x + cpre[2].x + cpre[3].x;
         }
-        W3_LOAD_P(c_begin + 2, cdep, ofs)  // (behind the reads of v172-v179)
+        W3_LOAD_P(b, c_begin + 2, cdep, ofs)  // (behind the reads of v172-v179)
         if (PRO || G8) __syncthreads();    // coefficient table (and the zeroed halo) visible
         if (rec) sp[4] = __builtin_amdgcn_s_memtime() - tk0;      // coefficient table visible
         {
@@ -495,26 +314,26 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
             // EACH ACTIVATED VALUE: issued in one burst they fill the CU's vector-memory queue and every wave sat 2-3 k cycles in the
             // issue (8 waves x 21 KB at 64 bytes per clock; profiles/r03_wino3_prologue.txt) before it could touch its patches.
             constexpr int QR = (NA - PQ + 2 * NPV - 1) / (2 * NPV);       // quads per value
-#define W3_HOOK0(e, v) W3_LOAD_A_RANGE(c_begin, PQ + (e) * QR, (PQ + ((e) + 1) * QR < NA ? PQ + ((e) + 1) * QR : NA), v)
-#define W3_HOOK1(e, v) W3_LOAD_A_RANGE(c_begin, (PQ + (NPV + (e)) * QR < NA ? PQ + (NPV + (e)) * QR : NA), (PQ + (NPV + (e) + 1) * QR < NA ? PQ + (NPV + (e) + 1) * QR : NA), v)
+#define W3_HOOK0(e, v) W3_LOAD_A_RANGE(W3_WCHUNK(c_begin), PQ + (e) * QR, (PQ + ((e) + 1) * QR < NA ? PQ + ((e) + 1) * QR : NA), v)
+#define W3_HOOK1(e, v) W3_LOAD_A_RANGE(W3_WCHUNK(c_begin), (PQ + (NPV + (e)) * QR < NA ? PQ + (NPV + (e)) * QR : NA), (PQ + (NPV + (e) + 1) * QR < NA ? PQ + (NPV + (e) + 1) * QR : NA), v)
             float pv0[NPV], pv1[NPV];
             f32x2 cf0[NPL], cf1[NPL];
             W3_READ_C(c_begin, cf0)
             W3_READ_C(c_begin + 1, cf1)
-            W3_WRITE_PR(c_begin, pv0, cf0, "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191", "v192", W3_HOOK0)
-            W3_WRITE_PR(c_begin + 1, pv1, cf1, "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", W3_HOOK1)
+            W3_WRITE_PR(c_begin & 1, Cin - c_begin * CK, 0u, pv0, cf0, "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191", "v192", W3_HOOK0)
+            W3_WRITE_PR((c_begin + 1) & 1, Cin - (c_begin + 1) * CK, 0u, pv1, cf1, "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", W3_HOOK1)
 #undef W3_HOOK0
 #undef W3_HOOK1
             const float dep = pv0[0] + pv1[0];
-            W3_LOAD_A_RANGE(c_begin, 0, PQ, dep)
+            W3_LOAD_A_RANGE(W3_WCHUNK(c_begin), 0, PQ, dep)
         }
     }
     __syncthreads();                       // the first two patches visible
     if (rec) sp[2] = __builtin_amdgcn_s_memtime() - tk0;          // first two patches activated and parked
     {
         f32x2 rw[3][4];
-        W3_READ_R(c_begin, rw)
-        W3_WRITE_V(c_begin, rg, rw)
+        W3_READ_R(c_begin & 1, rw)
+        W3_WRITE_V(c_begin & 1, rg, rw)
     }
     __syncthreads();                       // V of the first chunk visible
     W3_STAMP(0)
@@ -530,14 +349,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     if (ph == 0) {
         for (int c = c_begin; c + 1 < c_end; ++c) {
             W3_VALU_PHASE(c, rg)
-            W3_MFMA_PHASE(c, true)
+            W3_MFMA_PHASE(c & 1, true, W3_WCHUNK(c + 1))
             // chunk c read by every wave; V(c+1), patch(c+2) visible.  LDS traffic only: no VMEM wait at the barrier.
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             W3_TS(6)
         }
     } else {
         for (int c = c_begin; c + 1 < c_end; ++c) {
-            W3_MFMA_PHASE(c, true)
+            W3_MFMA_PHASE(c & 1, true, W3_WCHUNK(c + 1))
             W3_VALU_PHASE(c, rg)
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             W3_TS(6)
@@ -546,7 +365,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     W3_WAIT(0)
     {
         const int c = c_end - 1;
-        W3_MFMA_PHASE(c, false)
+        W3_MFMA_PHASE(c & 1, false, wr_base)
     }
     // The MFMAs are inline asm: the compiler does not know that the accumulators were written by the matrix pipe and inserts none of
     // the wait states a read of an MFMA result needs (8-pass MFMA -> VALU / LDS read: 11).  Nothing in the K loop reads them.
@@ -602,64 +421,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
         for (int t2 = 0; t2 < 2; ++t2) {
             const int e_col = e_col0 + 16 * t2;
             const int co = co0 + ct * 32 + e_col;
-            const f32x2 r0 = e_r0[ct][t2], r1 = e_r1[ct][t2];
-            float mm[16];
-#pragma unroll
-            for (int xi = 0; xi < 16; ++xi) mm[xi] = sM[(xi * 32 + e_col) * T + e_tile];
-            float t0[4], t1[4];                                 // A^T M
-#pragma unroll
-            for (int l = 0; l < 4; ++l) {
-                t0[l] = mm[0 * 4 + l] + mm[1 * 4 + l] + mm[2 * 4 + l];
-                t1[l] = mm[1 * 4 + l] - mm[2 * 4 + l] - mm[3 * 4 + l];
-            }
-            const float y00 = t0[0] + t0[1] + t0[2], y01 = t0[1] - t0[2] - t0[3];
-            const float y10 = t1[0] + t1[1] + t1[2], y11 = t1[1] - t1[2] - t1[3];
-            const float bvv = e_bias[ct][t2];
-            const float osc = fin ? a.out_scale : 1.0f;
-            const float v00 = (y00 + bvv + r0.x) * osc, v01 = (y01 + bvv + r0.y) * osc;
-            const float v10 = (y10 + bvv + r1.x) * osc, v11 = (y11 + bvv + r1.y) * osc;
-            if (co < a.Cout && e_valid) {
-                const long o = ((long)e_b * a.Cout + co) * HW + pix;
-                *reinterpret_cast<float2*>(ydst + o) = make_float2(v00, v01);
-                *reinterpret_cast<float2*>(ydst + o + W) = make_float2(v10, v11);
-            }
-            if (a.stats && fin) {
-                // GroupNorm partials of the FINAL values (ConvArgs::stats): the tiles of this cout are the 32 lanes of a half-wave (G8:
-                // 16 lanes = one DPP row per image).  Pilot-shifted moments (conv_wino2h.cpp has the derivation): with p = the group's
-                // first value, s = sum (v - p) and q = sum (v - p)^2 merge by plain addition, two DPP adds per level.
-                float pil;
-                {
-                    const int pv = __builtin_bit_cast(int, v00);
-                    const int s0 = __builtin_amdgcn_readlane(pv, 0), s2 = __builtin_amdgcn_readlane(pv, 32);
-                    if (G8) {
-                        const int s1 = __builtin_amdgcn_readlane(pv, 16), s3 = __builtin_amdgcn_readlane(pv, 48);
-                        pil = __builtin_bit_cast(float, (lane & 32) ? ((lane & 16) ? s3 : s2) : ((lane & 16) ? s1 : s0));
-                    } else {
-                        pil = __builtin_bit_cast(float, (lane & 32) ? s2 : s0);
-                    }
-                }
-                const float d0 = v00 - pil, d1 = v01 - pil, d2 = v10 - pil, d3 = v11 - pil;
-                float sm = (d0 + d1) + (d2 + d3);
-                float qm = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-#define W3_MERGE(CTRL, ROWMASK)                                                                                     \
-                {                                                                                                   \
-                    sm += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sm), CTRL, ROWMASK, 0xf, false)); \
-                    qm += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, qm), CTRL, ROWMASK, 0xf, false)); \
-                }
-                W3_MERGE(0xB1, 0xf)                   // quad_perm [1,0,3,2]
-                W3_MERGE(0x4E, 0xf)                   // quad_perm [2,3,0,1]
-                W3_MERGE(0x124, 0xf)                  // row_ror:4
-                W3_MERGE(0x128, 0xf)                  // row_ror:8: every lane of a row of 16 holds the row's totals
-                if (!G8) W3_MERGE(0x142, 0xa)         // row_bcast:15: lanes 16-31 / 48-63 add the totals of the row below
-#undef W3_MERGE
-                const bool writer = G8 ? (e_tile & 15) == 0 : e_tile == 31;
-                if (writer && co < a.Cout && e_valid) {
-                    constexpr float NPIX = G8 ? 64.0f : 128.0f;
-                    float* q = a.stats + (((long)e_b * a.Cout + co) * (rx_n * ry_n) + rr) * 2;
-                    q[0] = sm + NPIX * pil;           // the partial's sum over its pixels
-                    q[1] = fmaxf(qm - sm * sm * (1.0f / NPIX), 0.0f);      // M2 about the partial's own mean
-                }
-            }
+            WINO_EPILOGUE_TASK(G8, false, sM, sM, 1.0f, e_bias[ct][t2], e_r0[ct][t2], e_r1[ct][t2], e_b, e_valid, rx_n * ry_n, rr)
         }
         if (ct + 1 < COT) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
@@ -685,26 +447,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
     }
 #undef W3_STAMP
 #undef W3_TS
-#undef W3_LOAD_A
-#undef W3_LOAD_A_PIECE
-#undef W3_QUADS
-#undef W3_LD1
-#undef W3_MF1
-#undef W3_PRODUCT
-#undef W3_LOAD_P
-#undef W3_LOAD_PR
-#undef W3_WRITE_PR
-#undef W3_LD1D
-#undef W3_LOAD_A_RANGE
-#undef W3_WAIT
-#undef W3_WRITE_P
-#undef W3_WRITE_V
-#undef W3_READ_R
-#undef W3_READ_C
+#undef W3_WCHUNK
 #undef W3_READ_OFF
-#undef W3_LOAD_B
-#undef W3_MFMA_PHASE
+#undef W3_READ_C
 #undef W3_VALU_PHASE
+#undef W3_SLOT_OFF
+#define W3_STAGE_UNDEF
+#include "conv_wino3_stage.h"
 }
 
 // pc: the channels of one part (wino_part_channels): the coefficient table's entries per sample
@@ -715,18 +464,6 @@ static constexpr size_t wino3_lds_bytes(int pc, bool g8) {
 static_assert(W3_PP != 24 || wino3_lds_bytes(WINO_TABLE_CH_PLANE, false) == 151616, "a plane's table of WINO_TABLE_CH_PLANE channels");
 static_assert(wino3_lds_bytes(WINO_TABLE_CH_PLANE, false) <= 160 * 1024 && wino3_lds_bytes(WINO_TABLE_CH, true) <= 160 * 1024,
               "the widest coefficient table the rule admits (conv_kernels.h: kWinoRules), regions of a plane and 8 x 8, fits the LDS: no LDS term in the rule");
-
-template <int COT, int PRO, bool G8, int EXP>
-static int wino3_launch_k(const ConvArgs& k, dim3 grid, size_t lds, hipStream_t s) {
-    static PerDeviceOnce raised;
-    if (raised.first_use()) {
-        MCVD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino3_kernel<COT, PRO, G8, EXP>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised.done();
-    }
-    hipLaunchKernelGGL((conv_wino3_kernel<COT, PRO, G8, EXP>), grid, dim3(W3_NT), lds, s, k);
-    return 0;
-}
 
 template <int COT, int PRO, bool G8>
 static int wino3_launch2(const ConvArgs& a, hipStream_t s) {
@@ -748,34 +485,22 @@ static int wino3_launch2(const ConvArgs& a, hipStream_t s) {
     const int e = exp_s ? atoi(exp_s) : 0;
     if (COT == 3 && PRO == 2 && !G8 && e != 0) {
         switch (e) {
-            case 1: rc = wino3_launch_k<3, 2, false, 1>(k, grid, lds, s); break;        // no transform
-            case 2: rc = wino3_launch_k<3, 2, false, 2>(k, grid, lds, s); break;        // no patch activation / park
-            case 3: rc = wino3_launch_k<3, 2, false, 3>(k, grid, lds, s); break;        // neither
-            case 4: rc = wino3_launch_k<3, 2, false, 4>(k, grid, lds, s); break;        // no VMEM in the loop
-            case 16: rc = wino3_launch_k<3, 2, false, 16>(k, grid, lds, s); break;      // everything but the MFMAs
-            case 15: rc = wino3_launch_k<3, 2, false, 15>(k, grid, lds, s); break;      // MFMA only
-            case 27: rc = wino3_launch_k<3, 2, false, 27>(k, grid, lds, s); break;      // VMEM only
-            case 11: rc = wino3_launch_k<3, 2, false, 11>(k, grid, lds, s); break;      // VMEM + MFMA only
+            case 1: rc = wino_launch_kernel<conv_wino3_kernel<3, 2, false, 1>>(k, grid, W3_NT, lds, s); break;        // no transform
+            case 2: rc = wino_launch_kernel<conv_wino3_kernel<3, 2, false, 2>>(k, grid, W3_NT, lds, s); break;        // no patch activation / park
+            case 3: rc = wino_launch_kernel<conv_wino3_kernel<3, 2, false, 3>>(k, grid, W3_NT, lds, s); break;        // neither
+            case 4: rc = wino_launch_kernel<conv_wino3_kernel<3, 2, false, 4>>(k, grid, W3_NT, lds, s); break;        // no VMEM in the loop
+            case 16: rc = wino_launch_kernel<conv_wino3_kernel<3, 2, false, 16>>(k, grid, W3_NT, lds, s); break;      // everything but the MFMAs
+            case 15: rc = wino_launch_kernel<conv_wino3_kernel<3, 2, false, 15>>(k, grid, W3_NT, lds, s); break;      // MFMA only
+            case 27: rc = wino_launch_kernel<conv_wino3_kernel<3, 2, false, 27>>(k, grid, W3_NT, lds, s); break;      // VMEM only
+            case 11: rc = wino_launch_kernel<conv_wino3_kernel<3, 2, false, 11>>(k, grid, W3_NT, lds, s); break;      // VMEM + MFMA only
             default: mcvd::set_error("MCVD_WINO3_EXP=%d is not a built ablation", e); return -1;
         }
     } else
 #endif
     {
-        rc = wino3_launch_k<COT, PRO, G8, 0>(k, grid, lds, s);
+        rc = wino_launch_kernel<conv_wino3_kernel<COT, PRO, G8, 0>>(k, grid, W3_NT, lds, s);
     }
     return rc ? rc : wino_launch_done(a, G8, ksp, s);
-}
-
-template <int COT, bool G8>
-static int wino3_launch1(const ConvArgs& a, hipStream_t s) {
-    if (!a.coef && !a.act) return wino3_launch2<COT, 0, G8>(a, s);
-    if (!a.act) return wino3_launch2<COT, 1, G8>(a, s);
-    return wino3_launch2<COT, 2, G8>(a, s);
-}
-
-template <int COT>
-static int wino3_launch(const ConvArgs& a, hipStream_t s) {
-    return (a.H == 8 && a.W == 8) ? wino3_launch1<COT, true>(a, s) : wino3_launch1<COT, false>(a, s);
 }
 
 // a.wpb: the layout of launch_pack_wino3_weight, packed for conv_wino_cout_tile(Cout).
@@ -784,11 +509,7 @@ int launch_conv_wino3(const ConvArgs& a, hipStream_t s) {
     if (int rc = conv_wino_require(CF_WINO3, a, "winograd bf16x3 conv")) return rc;
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "winograd bf16x3 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
-    switch (cot) {
-        case 1: return wino3_launch<1>(a, s);
-        case 2: return wino3_launch<2>(a, s);
-        default: return wino3_launch<3>(a, s);
-    }
+    return wino_dispatch(a, cot, [&](auto COT, auto PRO, auto G8) { return wino3_launch2<COT(), PRO(), G8()>(a, s); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -18,70 +18,41 @@
 //   * a new sample (new GroupNorm coefficient table) ends the run: the pipeline drains and the prologue runs again.  At the batch
 //     sizes of BASELINE.json the item ranges are aligned with the samples and every workgroup has exactly one run.
 // Shape ids 16 / 17 (17: 2-way K split, the halves are items).  8x8 images stay with conv_wino3_kernel<.., G8> (one item per CU:
-// nothing to stream).  VMEM of the K loop is hand-counted exactly as in conv_wino3.cpp; tools/check_wino_isa.py checks this file too.
+// nothing to stream).  The stage of one chunk is the one-shot kernel's, literally: conv_wino3_stage.h holds the constants, the
+// named-register map and the macros that load, park, transform and multiply a chunk, with their hand-counted VMEM
+// (tools/check_wino_isa.py checks this file too).  This file keeps the slot table, the item stream and its chunk scalars, the
+// coefficient table over all of Cin (WP_READ_C) and the epilogue's two-buffer parking; the epilogue's task itself is wino_common.h.
 #include <stdlib.h>
 
 #include "../common.h"
+#include "conv_wino3_stage.h"
 
 namespace mcvd {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float silu_w3p(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-
-constexpr int WP_CK = 16;        // input channels per chunk = K of one bf16 MFMA
-constexpr int WP_T = 32;         // tiles per item (4 x 8 tiles = 8 x 16 output pixels)
-constexpr int WP_NT = 512;
-#ifndef MCVD_W3_PP
-#define MCVD_W3_PP 24
-#endif
-// LDS patch row pitch in channel-pair columns (18 used; 20 for the two 8x8 images side by side).  The patch park stores a lane's four pixels as
-// single dwords at ((pair * 10 + row) * PP + col) * 2 + ce; the 32 lanes of a store group are 8 rows x 4 four-pixel items, bank = (row * 2 PP +
-// 8 item) mod 32: with 2 PP = 48 = 16 (mod 32) they fall on FOUR banks -- the "x4 patch park" conflict behind 27-29 percent of the LDS-active
-// cycles (profiles/r04_pmc_sq_wave_states.txt).  Round 5 built the conflict-free pitch (25: 2 PP = 18 mod 32, 16 banks, 2-way = free for
-// ds_write_b32) and measured it against 24 on one box (tools/build_variant.sh, -DMCVD_W3_PP=25; profiles/r05_patch_pitch_ab.txt): 5577 vs 5592
-// cycles per chunk, 248.1 / 248.5 vs 248.8 / 249.4 frames/s -- nothing.  The stores are not on the chunk's critical path; 24 stays.
-constexpr int WP_PP = MCVD_W3_PP;
-constexpr int WP_PW = 16 * 2 * 4 * WP_T;          // 32-bit words of one piece plane of a V chunk: [position][half][pair][tile]
-constexpr int WP_VW = 3 * WP_PW;                  // 32-bit words of one V chunk: [piece][position][half][pair][tile]
 constexpr int WP_NPL = 3;                         // patch-load instructions per thread and chunk (two four-pixel slots + one halo slot)
 constexpr int WP_MINCH = 4;                       // chunks per item the stream needs (its staging looks three chunks ahead)
 
-__device__ __forceinline__ unsigned wp_cvt_pk(float lo, float hi) {
-    const f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-// exact three-way split of an adjacent register pair into packed bf16 pairs (conv_wino3.cpp: w3_split3)
-__device__ __forceinline__ void wp_split3(f32x2 v, unsigned& w1, unsigned& w2, unsigned& w3) {
-    w1 = wp_cvt_pk(v.x, v.y);
-    const f32x2 h = {__builtin_bit_cast(float, w1 << 16), __builtin_bit_cast(float, w1 & 0xffff0000u)};
-    v = v - h;
-    w2 = wp_cvt_pk(v.x, v.y);
-    const f32x2 g = {__builtin_bit_cast(float, w2 << 16), __builtin_bit_cast(float, w2 & 0xffff0000u)};
-    v = v - g;
-    w3 = wp_cvt_pk(v.x, v.y);
-}
+#define W3_SLOT_OFF(word) ((word) & ~3u)          // a word of the slot table: byte offset | bit 0 "zero padding here"
+#define W3_TS(i)                                  // no per-phase clock stamps in this kernel
 
 // PRO: 0 raw input, 1 affine, 2 affine + SiLU
 template <int COT, int PRO>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv_wino3p_kernel(ConvArgs a) {
     // amdgpu_num_vgpr(86): the compiler may allocate v0-v171 (LLVM doubles the number on gfx90a+; conv_wino3.cpp); v172-v255 hold the
     // in-flight loads and the MFMA A operands and are named in the asm text only.
-    constexpr int NT = WP_NT, CK = WP_CK, T = WP_T, BCO = 32 * COT, PP = WP_PP, VW = WP_VW, PW = WP_PW;
+    constexpr int NT = W3_NT, CK = W3_CK, T = W3_T, BCO = 32 * COT, PP = W3_PP, VW = W3_VW, PW = W3_PW;
     constexpr int PSZ = CK * 10 * PP;           // activated input patch of one chunk: [pair 8][10 rows][PP][2 channels]
     constexpr int PBUF = 4096;                  // + dump space for unused patch slots, rounded up to 16 KiB: the epilogue parks four position planes there
-    static_assert(PBUF >= PSZ + 8 && PBUF >= 4 * 32 * WP_T, "patch buffer: patch + dump space, and 4 positions x 32 couts x 32 tiles of the epilogue");
+    static_assert(PBUF >= PSZ + 8 && PBUF >= 4 * 32 * W3_T, "patch buffer: patch + dump space, and 4 positions x 32 couts x 32 tiles of the epilogue");
     constexpr int NPL = WP_NPL, NPV = 9;
+    constexpr bool G8 = false;                  // 8 x 8 images and the timing ablations are the one-shot kernel's: those branches of the
+    constexpr int EXP = 0;                      // shared stage vanish here
     constexpr int NQ = 3 * COT;                 // weight quads per position: COT cout sub-tiles x 3 pieces
     constexpr int NA = 2 * NQ;                  // weight loads per wave and chunk
     constexpr int VM_A = NQ + NPL;
     constexpr int PQ = 5;                       // weight quads whose registers hold the first two patches in the prologue
     constexpr long WSTR = 16L * NQ * 256;       // dwords of one chunk of a cout tile's packed weights
-    static_assert(NA <= 18 && NA > PQ, "named-register map below: v172-v180 patch, v184-v255 eighteen weight quads");
+    static_assert(NA <= 18 && NA > PQ, "named-register map of conv_wino3_stage.h: v172-v180 patch, v184-v255 eighteen weight quads");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     unsigned* sV = reinterpret_cast<unsigned*>(smem);           // [2][VW]
     float* sP = smem + 2 * VW;                  // [2][PBUF]
@@ -170,36 +141,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
 
     const unsigned wr_voff = (unsigned)lane * 16u;
 
-    /* IN-FLIGHT DATA LIVES IN REGISTERS THE COMPILER DOES NOT ALLOCATE (conv_wino3.cpp has the full account): weight quad q in
-       v[184 + 4q : 187 + 4q], patch slots in v[172:175], v[176:179], v180; bare s_waitcnt; the MFMAs name their A operand in the text. */
-#define WP_QUADS(X, q, A1, A2) X(0, "v[184:187]", q, A1, A2) X(1, "v[188:191]", q, A1, A2) X(2, "v[192:195]", q, A1, A2) X(3, "v[196:199]", q, A1, A2) X(4, "v[200:203]", q, A1, A2) X(5, "v[204:207]", q, A1, A2) X(6, "v[208:211]", q, A1, A2) X(7, "v[212:215]", q, A1, A2) X(8, "v[216:219]", q, A1, A2) X(9, "v[220:223]", q, A1, A2) X(10, "v[224:227]", q, A1, A2) X(11, "v[228:231]", q, A1, A2) X(12, "v[232:235]", q, A1, A2) X(13, "v[236:239]", q, A1, A2) X(14, "v[240:243]", q, A1, A2) X(15, "v[244:247]", q, A1, A2) X(16, "v[248:251]", q, A1, A2) X(17, "v[252:255]", q, A1, A2)
-#define WP_LD1(K, R, q, P, UNUSED) if ((q) == K) asm volatile("global_load_dwordx4 " R ", %0, %1" :: "v"(wr_voff), "s"(P) : "memory");
-#define WP_MF1(K, R, q, ACC, BV) if ((q) == K) asm volatile("v_mfma_f32_32x32x16_bf16 %0, " R ", %1, %0" : "+v"(ACC) : "v"(BV));
-    /* weight piece `pc` of every cout sub-tile of position 2w + i of the chunk whose (wave's) weights start at WPTR */
-#define WP_LOAD_A_PIECE(WPTR, i, pc)                                                                            \
-    {                                                                                                           \
-        const unsigned* ua = (WPTR) + (i) * (NQ * 256);                                                         \
-        _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { WP_QUADS(WP_LD1, (i) * NQ + ct * 3 + (pc), ua + (ct * 3 + (pc)) * 256, 0) } \
-    }
-#define WP_LD1D(K, R, q, P, DEP) if ((q) == K) asm volatile("global_load_dwordx4 " R ", %0, %1" :: "v"(wr_voff), "s"(P), "v"(DEP) : "memory");
-#define WP_LOAD_A_RANGE(WPTR, Q0, Q1, DEP)                                                                      \
-    {                                                                                                           \
-        const unsigned* ua = (WPTR);                                                                            \
-        _Pragma("unroll") for (int qq = (Q0); qq < (Q1); ++qq) { WP_QUADS(WP_LD1D, qq, ua + qq * 256, DEP) }    \
-    }
-#define WP_WAIT(N) asm volatile("s_waitcnt vmcnt(%1)\n\ts_mov_b32 %0, 0" : "=s"(vtok) : "n"(N) : "memory");
-    /* unconditional, clamped raw loads of the patch of absolute chunk `ch` of sample bb: OFS = the slots' table words */
-#define WP_LOAD_P(bb, ch, DEP, OFS) WP_LOAD_PR(bb, ch, DEP, OFS, "v[172:175]", "v[176:179]", "v180")
-#define WP_LOAD_PR(bb, ch, DEP, OFS, RA, RB, RH)                                                                \
-    {                                                                                                           \
-        const int cb = min((ch) * CK, Cin - 1);                                                                 \
-        const unsigned lim4 = (unsigned)((Cin - cb) * HW - 4) * 4u, lim1 = (unsigned)((Cin - cb) * HW - 1) * 4u; \
-        const bool second = cb >= a.C0;                                                                         \
-        const float* srcb = second ? a.x1 + ((long)(bb) * a.C1 + (cb - a.C0)) * HW : a.x0 + ((long)(bb) * a.C0 + cb) * HW; \
-        const unsigned o0 = min(OFS[0] & ~3u, lim4), o1 = min(OFS[1] & ~3u, lim4), o2 = min(OFS[2] & ~3u, lim1); \
-        asm volatile("global_load_dwordx4 " RA ", %0, %3\n\tglobal_load_dwordx4 " RB ", %1, %3\n\tglobal_load_dword " RH ", %2, %3" \
-                     :: "v"(o0), "v"(o1), "v"(o2), "s"(srcb), "v"(DEP) : "memory");                               \
-    }
+    // the chunk's stage -- the named registers v172-v255 and the W3_ macros that load, park, transform and multiply -- is conv_wino3_stage.h
 #define WP_READ_C(ch, cfv)                                                                                      \
     {                                                                                                           \
         _Pragma("unroll") for (int sl = 0; sl < NPL; ++sl) {                                                    \
@@ -208,80 +150,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
                 const int cch = min((ch) * CK + (int)((p_pk[sl] >> 12) & (CK - 1)), Cin - 1);                   \
                 cfv[sl] = *reinterpret_cast<const f32x2*>(sCo + cch * 2);                                       \
             }                                                                                                   \
-        }                                                                                                       \
-    }
-#define WP_NOHOOK(e, v)
-#define WP_WRITE_P(par, ch, FL, PV, cfv) WP_WRITE_PR(par, ch, FL, PV, cfv, "v172", "v173", "v174", "v175", "v176", "v177", "v178", "v179", "v180", WP_NOHOOK)
-    /* activate once per pixel and park the patch of absolute chunk `ch` in patch buffer `par`; FL bit sl = slot sl is zero padding;
-       zero padding applies AFTER the activation.  HOOK(e, v): statements placed behind value e */
-#define WP_WRITE_PR(par, ch, FL, PV, cfv, A0, A1, A2, A3, B0, B1, B2, B3, H0, HOOK)                             \
-    {                                                                                                           \
-        float* sPw = sP + ((par) ? PBUF : 0);                                                                   \
-        const int nvalid = min(Cin - (ch) * CK, CK);                                                            \
-        asm("v_fma_f32 %0, " A0 ", %9, %10\n\tv_fma_f32 %1, " A1 ", %9, %10\n\tv_fma_f32 %2, " A2 ", %9, %10\n\tv_fma_f32 %3, " A3 ", %9, %10\n\t" \
-            "v_fma_f32 %4, " B0 ", %11, %12\n\tv_fma_f32 %5, " B1 ", %11, %12\n\tv_fma_f32 %6, " B2 ", %11, %12\n\tv_fma_f32 %7, " B3 ", %11, %12\n\t" \
-            "v_fma_f32 %8, " H0 ", %13, %14"                                                                      \
-            : "=&v"(PV[0]), "=&v"(PV[1]), "=&v"(PV[2]), "=&v"(PV[3]), "=&v"(PV[4]), "=&v"(PV[5]), "=&v"(PV[6]), "=&v"(PV[7]), "=&v"(PV[8]) \
-            : "v"(cfv[0].x), "v"(cfv[0].y), "v"(cfv[1].x), "v"(cfv[1].y), "v"(cfv[2].x), "v"(cfv[2].y), "s"(vtok)); \
-        _Pragma("unroll") for (int e = 0; e < NPV; ++e) {                                                       \
-            const int sl = e >> 2;                            /* values 0-3: slot 0, 4-7: slot 1, 8: slot 2 */   \
-            float v = PV[e];                                                                                    \
-            if (PRO >= 2) v = silu_w3p(v);                                                                      \
-            const bool keep = (((FL) >> sl) & 1u) == 0u && (int)((p_pk[sl] >> 12) & 0xff) < nvalid;             \
-            sPw[(p_pk[sl] & 0xfff) + 2 * (e & 3)] = keep ? v : 0.0f;                                            \
-            HOOK(e, v)                                                                                          \
-        }                                                                                                       \
-    }
-#define WP_READ_R(par, RW)                                                                                      \
-    {                                                                                                           \
-        const f32x2* sPr = reinterpret_cast<const f32x2*>(sP + ((par) ? PBUF : 0) + p_rd);                      \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) { RW[0][j] = sPr[j]; RW[1][j] = sPr[PP + j]; RW[2][j] = sPr[2 * PP + j]; } \
-    }
-#define WP_WRITE_V(par, RG, RW)                                                                                 \
-    {                                                                                                           \
-        unsigned* vdst = sV + ((par) ? VW : 0) + v_wr;                                                          \
-        f32x2 mx[4], my[4];                                                                                     \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                         \
-            const f32x2 r0 = RW[0][j], r1 = RW[1][j], r2 = RW[2][j];                                            \
-            if ((RG) == 0) { mx[j] = r0 - r2; my[j] = r1 + r2; }                                                \
-            else { mx[j] = r1 - r0; my[j] = r0 - r2; }                                                          \
-        }                                                                                                       \
-        _Pragma("unroll") for (int row = 0; row < 2; ++row) {                                                   \
-            const f32x2 m0 = row ? my[0] : mx[0], m1 = row ? my[1] : mx[1], m2 = row ? my[2] : mx[2], m3 = row ? my[3] : mx[3]; \
-            const f32x2 v0 = m0 - m2, v1 = m1 + m2, v2 = m2 - m1, v3 = m1 - m3;                                 \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                     \
-                unsigned w1, w2, w3;                                                                            \
-                wp_split3(q == 0 ? v0 : q == 1 ? v1 : q == 2 ? v2 : v3, w1, w2, w3);                            \
-                vdst[(row * 4 + q) * 256] = w1;                                                                 \
-                vdst[(row * 4 + q) * 256 + PW] = w2;                                                            \
-                vdst[(row * 4 + q) * 256 + 2 * PW] = w3;                                                        \
-            }                                                                                                   \
-        }                                                                                                       \
-    }
-#define WP_LOAD_B(i, BQ)                                                                                        \
-    {                                                                                                           \
-        const unsigned* q = sVc + (((2 * wave + (i)) * 2 + half) * 4) * T + l31;                                \
-        _Pragma("unroll") for (int jp = 0; jp < 4; ++jp) {                                                      \
-            BQ[0][jp] = q[jp * T]; BQ[1][jp] = q[PW + jp * T]; BQ[2][jp] = q[2 * PW + jp * T];                  \
-        }                                                                                                       \
-    }
-#define WP_PRODUCT(i, PA, PB)                                                                                   \
-    { _Pragma("unroll") for (int ct = 0; ct < COT; ++ct) { WP_QUADS(WP_MF1, 3 * ((i) * COT + ct) + (PA), acc[i][ct], bq[i][PB]) } }
-    /* all MFMAs of the chunk whose V sits in buffer `par` (weights in the named registers); behind each piece's last product the
-       same registers are re-requested from WNX, the (wave's) weights of the NEXT chunk of the stream (conv_wino3.cpp: W3_MFMA_PHASE) */
-#define WP_MFMA_PHASE(par, WNX)                                                                                 \
-    {                                                                                                           \
-        const unsigned* sVc = sV + ((par) ? VW : 0);                                                            \
-        u32x4 bq[2][3];                                                                                         \
-        WP_LOAD_B(0, bq[0]) WP_LOAD_B(1, bq[1])                                                                 \
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                         \
-            WP_WAIT(VM_A)                                                                                       \
-            WP_PRODUCT(i, 2, 0)                                                                                 \
-            WP_LOAD_A_PIECE(WNX, i, 2)                                                                          \
-            WP_PRODUCT(i, 1, 1) WP_PRODUCT(i, 0, 2) WP_PRODUCT(i, 1, 0)                                         \
-            WP_LOAD_A_PIECE(WNX, i, 1)                                                                          \
-            WP_PRODUCT(i, 0, 1) WP_PRODUCT(i, 0, 0)                                                             \
-            WP_LOAD_A_PIECE(WNX, i, 0)                                                                          \
         }                                                                                                       \
     }
     /* staging of the stream at chunk g (V(g) is being multiplied): park chunk g+2 (absolute chunk CH2, patch buffer par: g+2 and g
@@ -294,17 +162,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
             unsigned ofs[NPL];                                                                                  \
             WP_READ_C(CH2, cfv)                                                                                 \
             _Pragma("unroll") for (int sl = 0; sl < NPL; ++sl) ofs[sl] = sOff[((TAB3) * NPL + sl) * NT + tid];  \
-            WP_WAIT(NA)                                                                                         \
+            W3_WAIT(NA)                                                                                         \
             float pv[NPV];                                                                                      \
             _Pragma("unroll") for (int e = 0; e < NPV; ++e) pv[e] = 0.0f;                                       \
-            WP_WRITE_P(par, CH2, pfl, pv, cfv)                                                                  \
+            W3_WRITE_P(par, min(Cin - (CH2) * CK, CK), pfl, pv, cfv)                                            \
             pfl = (ofs[0] & 1u) | ((ofs[1] & 1u) << 1) | ((ofs[2] & 1u) << 2);                                  \
-            WP_LOAD_P(b, CH3, pv[0], ofs)                                                                       \
+            W3_LOAD_P(b, CH3, pv[0], ofs)                                                                       \
         }                                                                                                       \
         {                                                                                                       \
             f32x2 rw[3][4];                                                                                     \
-            WP_READ_R((par) ^ 1, rw)                                                                            \
-            WP_WRITE_V((par) ^ 1, RG, rw)                                                                       \
+            W3_READ_R((par) ^ 1, rw)                                                                            \
+            W3_WRITE_V((par) ^ 1, RG, rw)                                                                       \
         }                                                                                                       \
     }
 
@@ -354,9 +222,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
             unsigned ofs[NPL];
             WP_SLOT_TABLE(it & 1, oy0, ox0, ofs)
             const unsigned fl0 = (ofs[0] & 1u) | ((ofs[1] & 1u) << 1) | ((ofs[2] & 1u) << 2);
-            WP_LOAD_PR(b, cbeg, nodep, ofs, "v[184:187]", "v[188:191]", "v192")
-            WP_LOAD_PR(b, cbeg + 1, nodep, ofs, "v[194:197]", "v[198:201]", "v202")
-            WP_WAIT(0)                         // the coefficients and the two patches have landed
+            W3_LOAD_PR(b, cbeg, nodep, ofs, "v[184:187]", "v[188:191]", "v192")
+            W3_LOAD_PR(b, cbeg + 1, nodep, ofs, "v[194:197]", "v[198:201]", "v202")
+            W3_WAIT(0)                         // the coefficients and the two patches have landed
             float cdep = 0.0f;
             if (PRO) {
                 f32x2 cpre[2];
@@ -367,33 +235,33 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
                     if (tid + k * NT < Cin) *reinterpret_cast<f32x2*>(sCo + (tid + k * NT) * 2) = cpre[k];
                 cdep = cpre[0].x + cpre[1].x;
             }
-            WP_LOAD_P(b, cbeg + 2, cdep, ofs)  // (behind the reads of v172-v175)
+            W3_LOAD_P(b, cbeg + 2, cdep, ofs)  // (behind the reads of v172-v175)
             pfl = fl0;
             if (PRO) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // coefficient table visible
             {
                 // the weight quads PQ.. of the first chunk are requested one behind each activated value (conv_wino3.cpp)
                 constexpr int QR = (NA - PQ + 2 * NPV - 1) / (2 * NPV);
-#define WP_HOOK0(e, v) WP_LOAD_A_RANGE(w0, PQ + (e) * QR, (PQ + ((e) + 1) * QR < NA ? PQ + ((e) + 1) * QR : NA), v)
-#define WP_HOOK1(e, v) WP_LOAD_A_RANGE(w0, (PQ + (NPV + (e)) * QR < NA ? PQ + (NPV + (e)) * QR : NA), (PQ + (NPV + (e) + 1) * QR < NA ? PQ + (NPV + (e) + 1) * QR : NA), v)
+#define WP_HOOK0(e, v) W3_LOAD_A_RANGE(w0, PQ + (e) * QR, (PQ + ((e) + 1) * QR < NA ? PQ + ((e) + 1) * QR : NA), v)
+#define WP_HOOK1(e, v) W3_LOAD_A_RANGE(w0, (PQ + (NPV + (e)) * QR < NA ? PQ + (NPV + (e)) * QR : NA), (PQ + (NPV + (e) + 1) * QR < NA ? PQ + (NPV + (e) + 1) * QR : NA), v)
                 float pv0[NPV], pv1[NPV];
                 f32x2 cf0[NPL], cf1[NPL];
                 WP_READ_C(cbeg, cf0)
                 WP_READ_C(cbeg + 1, cf1)
-                WP_WRITE_PR(0, cbeg, fl0, pv0, cf0, "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191", "v192", WP_HOOK0)
-                WP_WRITE_PR(1, cbeg + 1, fl0, pv1, cf1, "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", WP_HOOK1)
+                W3_WRITE_PR(0, min(Cin - cbeg * CK, CK), fl0, pv0, cf0, "v184", "v185", "v186", "v187", "v188", "v189", "v190", "v191", "v192", WP_HOOK0)
+                W3_WRITE_PR(1, min(Cin - (cbeg + 1) * CK, CK), fl0, pv1, cf1, "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", WP_HOOK1)
 #undef WP_HOOK0
 #undef WP_HOOK1
                 const float dep = pv0[0] + pv1[0];
-                WP_LOAD_A_RANGE(w0, 0, PQ, dep)
+                W3_LOAD_A_RANGE(w0, 0, PQ, dep)
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");               // the first two patches visible
             {
                 f32x2 rw[3][4];
-                WP_READ_R(0, rw)
-                WP_WRITE_V(0, rg, rw)
+                W3_READ_R(0, rw)
+                W3_WRITE_V(0, rg, rw)
             }
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");               // V of the first chunk visible
-            WP_WAIT(0)                         // the loop's in-order counts start from an empty queue
+            W3_WAIT(0)                         // the loop's in-order counts start from an empty queue
         }
         WP_STAMP(0)
         int par = 0;                           // parity of the stream's current chunk: V(g) in sV[par], patch(g + 2) goes to sP[par]
@@ -425,7 +293,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
                 for (int c = 0; c < nch; ++c) {
                     WP_CHUNK_SCALARS
                     WP_VALU_PHASE(par, ch2, ch3, tab3, rg)
-                    WP_MFMA_PHASE(par, wnx)
+                    W3_MFMA_PHASE(par, true, wnx)
                     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                     par ^= 1;
                 }
@@ -435,7 +303,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
             } else {
                 for (int c = 0; c < nch; ++c) {
                     WP_CHUNK_SCALARS
-                    WP_MFMA_PHASE(par, wnx)
+                    W3_MFMA_PHASE(par, true, wnx)
                     WP_VALU_PHASE(par, ch2, ch3, tab3, rg)
                     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
                     par ^= 1;
@@ -504,55 +372,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
                 for (int t2 = 0; t2 < 2; ++t2) {
                     const int e_col = e_col0 + 16 * t2;
                     const int co = co0 + ct * 32 + e_col;
-                    const f32x2 r0 = e_r0[ct][t2], r1 = e_r1[ct][t2];
-                    float mm[16];
-#pragma unroll
-                    for (int xi = 0; xi < 16; ++xi) mm[xi] = xi < 12 ? sM0[(xi * 32 + e_col) * T + e_tile] : sM1[((xi - 12) * 32 + e_col) * T + e_tile];
-                    float t0[4], t1[4];                                 // A^T M
-#pragma unroll
-                    for (int l = 0; l < 4; ++l) {
-                        t0[l] = mm[0 * 4 + l] + mm[1 * 4 + l] + mm[2 * 4 + l];
-                        t1[l] = mm[1 * 4 + l] - mm[2 * 4 + l] - mm[3 * 4 + l];
-                    }
-                    const float y00 = t0[0] + t0[1] + t0[2], y01 = t0[1] - t0[2] - t0[3];
-                    const float y10 = t1[0] + t1[1] + t1[2], y11 = t1[1] - t1[2] - t1[3];
-                    const float bvv = e_bias[ct][t2];
-                    const float osc = fin ? a.out_scale : 1.0f;
-                    const float v00 = (y00 + bvv + r0.x) * osc, v01 = (y01 + bvv + r0.y) * osc;
-                    const float v10 = (y10 + bvv + r1.x) * osc, v11 = (y11 + bvv + r1.y) * osc;
-                    if (co < a.Cout) {
-                        const long o = ((long)b * a.Cout + co) * HW + pix;
-                        *reinterpret_cast<float2*>(ydst + o) = make_float2(v00, v01);
-                        *reinterpret_cast<float2*>(ydst + o + W) = make_float2(v10, v11);
-                    }
-                    if (a.stats && fin) {
-                        // GroupNorm partials of the FINAL values, pilot-shifted moments over the 32 tiles of a half-wave (conv_wino3.cpp)
-                        float pil;
-                        {
-                            const int pv = __builtin_bit_cast(int, v00);
-                            const int s0 = __builtin_amdgcn_readlane(pv, 0), s2 = __builtin_amdgcn_readlane(pv, 32);
-                            pil = __builtin_bit_cast(float, (lane & 32) ? s2 : s0);
-                        }
-                        const float d0 = v00 - pil, d1 = v01 - pil, d2 = v10 - pil, d3 = v11 - pil;
-                        float sm = (d0 + d1) + (d2 + d3);
-                        float qm = (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-#define WP_MERGE(CTRL, ROWMASK)                                                                                     \
-                        {                                                                                           \
-                            sm += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, sm), CTRL, ROWMASK, 0xf, false)); \
-                            qm += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, qm), CTRL, ROWMASK, 0xf, false)); \
-                        }
-                        WP_MERGE(0xB1, 0xf)                   // quad_perm [1,0,3,2]
-                        WP_MERGE(0x4E, 0xf)                   // quad_perm [2,3,0,1]
-                        WP_MERGE(0x124, 0xf)                  // row_ror:4
-                        WP_MERGE(0x128, 0xf)                  // row_ror:8: every lane of a row of 16 holds the row's totals
-                        WP_MERGE(0x142, 0xa)                  // row_bcast:15: lanes 16-31 / 48-63 add the totals of the row below
-#undef WP_MERGE
-                        if (e_tile == 31 && co < a.Cout) {
-                            float* q = a.stats + (((long)b * a.Cout + co) * rpi + rr) * 2;
-                            q[0] = sm + 128.0f * pil;           // the partial's sum over its pixels
-                            q[1] = fmaxf(qm - sm * sm * (1.0f / 128.0f), 0.0f);      // M2 about the partial's own mean
-                        }
-                    }
+                    WINO_EPILOGUE_TASK(false, true, sM0, sM1, 1.0f, e_bias[ct][t2], e_r0[ct][t2], e_r1[ct][t2], b, true, rpi, rr)
                 }
                 // the round's LDS reads done before the next round's writes -- and, behind the last round, before the stream's next
                 // park / transform write into these buffers
@@ -586,29 +406,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_vgpr(86))) void conv
 #undef WP_STAMP
 #undef WP_EPI_FETCH
 #undef WP_SLOT_TABLE
-#undef WP_QUADS
-#undef WP_LD1
-#undef WP_MF1
-#undef WP_LOAD_A_PIECE
-#undef WP_LD1D
-#undef WP_LOAD_A_RANGE
-#undef WP_WAIT
-#undef WP_LOAD_P
-#undef WP_LOAD_PR
 #undef WP_READ_C
-#undef WP_NOHOOK
-#undef WP_WRITE_P
-#undef WP_WRITE_PR
-#undef WP_READ_R
-#undef WP_WRITE_V
-#undef WP_LOAD_B
-#undef WP_PRODUCT
-#undef WP_MFMA_PHASE
 #undef WP_VALU_PHASE
+#undef W3_SLOT_OFF
+#undef W3_TS
+#define W3_STAGE_UNDEF
+#include "conv_wino3_stage.h"
 }
 
 static constexpr size_t wino3p_lds_bytes(int Cin) {
-    return (size_t)(2 * WP_VW + 2 * 4096 + 2 * Cin + 2 * WP_NPL * WP_NT) * sizeof(float);
+    return (size_t)(2 * W3_VW + 2 * 4096 + 2 * Cin + 2 * WP_NPL * W3_NT) * sizeof(float);
 }
 static_assert(wino3p_lds_bytes(WINO_TABLE_CH) == 151552 && wino3p_lds_bytes(WINO_TABLE_CH) <= 160 * 1024,
               "the widest table the rule admits (conv_kernels.h: kWinoRules, all Cin <= WINO_TABLE_CH channels) fits the LDS: no LDS term in the rule");
@@ -628,12 +435,6 @@ static int wino3p_num_cus() {
 template <int COT, int PRO>
 static int wino3p_launch2(const ConvArgs& a, hipStream_t s) {
     constexpr int BCO = 32 * COT;
-    static PerDeviceOnce raised;
-    if (raised.first_use()) {
-        MCVD_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wino3p_kernel<COT, PRO>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        raised.done();
-    }
     const int ksp = a.ksplit >= 2 ? a.ksplit : 1;
     const long n_items = (long)a.B * (a.H / 8) * (a.W / 16) * (a.CoutP / BCO) * ksp;
     const int cus = a.pgrid > 0 ? a.pgrid : wino3p_num_cus();
@@ -650,30 +451,19 @@ static int wino3p_launch2(const ConvArgs& a, hipStream_t s) {
 #else
     k.wdma &= 0xff;
 #endif
-    hipLaunchKernelGGL((conv_wino3p_kernel<COT, PRO>), grid, dim3(WP_NT), wino3p_lds_bytes(a.Cin), s, k);
+    if (int rc = wino_launch_kernel<conv_wino3p_kernel<COT, PRO>>(k, grid, W3_NT, wino3p_lds_bytes(a.Cin), s)) return rc;
     return wino_launch_done(a, false, ksp, s);
-}
-
-template <int COT>
-static int wino3p_launch1(const ConvArgs& a, hipStream_t s) {
-    if (!a.coef && !a.act) return wino3p_launch2<COT, 0>(a, s);
-    if (!a.act) return wino3p_launch2<COT, 1>(a, s);
-    return wino3p_launch2<COT, 2>(a, s);
 }
 
 // Shape ids 16 / 17 / 20: regions of 8 x 16 output pixels only, at least WP_MINCH chunks per item, all Cin channels in one table (the rule's row
 // says why it stops at WINO_TABLE_CH); wider layers take the one-shot kernel (ids 11 / 18 / 19).
 int launch_conv_wino3p(const ConvArgs& a, hipStream_t s) {
-    static_assert(wino_rule(CF_WINO3P)->chunk == WP_CK && wino_rule(CF_WINO3P)->min_chunks[0] == WP_MINCH && wino_rule(CF_WINO3P)->min_chunks[3] == WP_MINCH,
+    static_assert(wino_rule(CF_WINO3P)->chunk == W3_CK && wino_rule(CF_WINO3P)->min_chunks[0] == WP_MINCH && wino_rule(CF_WINO3P)->min_chunks[3] == WP_MINCH,
                   "the rule's chunk and the fewest chunks of an item are the kernel's");
     if (int rc = conv_wino_require(CF_WINO3P, a, "persistent winograd bf16x3 conv")) return rc;
     const int cot = conv_wino_cout_tile(a.Cout);
     MCVD_REQUIRE(a.CoutP % (32 * cot) == 0, "persistent winograd bf16x3 conv: CoutP=%d vs tile %d", a.CoutP, 32 * cot);
-    switch (cot) {
-        case 1: return wino3p_launch1<1>(a, s);
-        case 2: return wino3p_launch1<2>(a, s);
-        default: return wino3p_launch1<3>(a, s);
-    }
+    return wino_dispatch(a, cot, [&](auto COT, auto PRO, auto) { return wino3p_launch2<COT(), PRO()>(a, s); });
 }
 
 }  // namespace mcvd

@@ -16,6 +16,12 @@ loads and 2*COT MFMAs per K loop): their K loops (two per kernel, one per phase 
 loads, no scratch traffic, and keep the load destinations untouched up to a vmcnt wait that covers them.  Their MFMAs are inline
 asm that read their A operand straight out of the load destinations, so in addition nothing but MFMAs may touch an accumulator
 register inside a K loop (the compiler does not know they are MFMA results and would not insert the wait states).
+
+Where the text lives: the K-loop stage of conv_wino3_kernel and conv_wino3p_kernel (the asm loads, waits and MFMAs checked here, and
+the named-register map v172-v255) is one header, kernels/conv_wino3_stage.h, expanded in both files; conv_wino2h.cpp keeps its own
+stage macros (v202-v255); the epilogue's task and the launch chain of all four files are kernels/wino_common.h.  The kernels are
+matched by their mangled symbol names, which none of this changes.  tools/compare_wino_isa.py uses this module's loop delimiting to
+compare the K loops of two trees instruction by instruction.
 """
 import os
 import re
