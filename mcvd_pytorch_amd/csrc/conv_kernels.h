@@ -2,7 +2,7 @@
 // what a launch tries after it.  The ids are public (the context options conv_shape / conv_shape1, the committed tuning tables under
 // profiles/, mcvd_last_conv_kernel / mcvd_model_op_kernel): a new variant gets a new number and one line here; numbers are never reused.
 // Plain C++17, no HIP: the static_asserts at the end check the table in every build.  Which launches the Winograd families take is the second
-// table of this file (kWinoRules / wino_admits, below the id table).
+// table of this file (kWinoRules / wino_admits, below the id table); which ids the autotuner offers a layer is conv_tuner.h.
 #pragma once
 #include <cstddef>
 #include <initializer_list>
@@ -121,7 +121,6 @@ static_assert(WINO_MAX_CIN_K4 > 2 * WINO_TABLE_CH && WINO_MAX_CIN <= 2 * WINO_TA
 constexpr int wino_max_cin(int parts) { return parts >= 4 ? WINO_MAX_CIN_K4 : WINO_MAX_CIN; }
 constexpr int wino_table_ch(bool g8) { return g8 ? WINO_TABLE_CH : WINO_TABLE_CH_PLANE; }
 constexpr int wino_part_channels(int CinP, int parts) { return CinP / (parts >= 2 ? parts : 1); }      // PC: the table's entries per sample
-constexpr bool wino_needs_4_parts(int Cin) { return Cin > WINO_MAX_CIN; }      // no launch of fewer than four parts takes this layer (the tuner offers 4 at every batch)
 // the K parts a kernel makes of ConvArgs::ksplit.  conv_wino.cpp counts 2 as a split and every other value, 4 included, as none; the others
 // take the value as it comes, and the rule refuses the counts their row does not have
 constexpr int wino_kernel_parts(ConvFamily f, int ksplit) { return f == CF_WINO ? (ksplit == 2 ? 2 : 1) : ksplit; }
@@ -307,7 +306,6 @@ static_assert(!wino_admits(CF_WINO3, with_room(wino_case_launch({CF_WINO3, 1056,
               !wino_admits(CF_WINO3, with_room(wino_case_launch({CF_WINO3, 1056, 1056, 2, 8, 0, false, true}), 0)) &&
               wino_admits(CF_WINO3, with_room(wino_case_launch({CF_WINO3, 1056, 1056, 2, 8, 0, false, true}), 2 * 2 * 32 * 64)),
               "a K split needs room for its partial results");
-static_assert(wino_needs_4_parts(2304) && !wino_needs_4_parts(2048), "layers the tuner offers four parts at every batch");
 
 // the rule's geometric clause over planes that are not square: B = 2, Cout = 32, one source, CinP = Cin, weights present, room for exactly the
 // parts.  `parts` is what the kernel makes of the split (wino_kernel_parts), not ConvArgs::ksplit.  tests/test_wino_rule_cpu.py evaluates the

@@ -663,39 +663,37 @@ int mcvd_model::ensure_guided(int B, int weak_mask) {
     return 0;
 }
 
-float* mcvd_model::resolve(const TRef& r,const float* x, const float* cond, float* out, int B) const {
+float* mcvd_model::resolve(const TRef& r, const Io& io) const {
     switch (r.kind) {
-        case REF_ARENA: return arena + r.off * (int64_t)B;
-        case REF_X: return const_cast<float*>(x);
-        case REF_COND: return const_cast<float*>(cond);
-        case REF_OUT: return out;
+        case REF_ARENA: return arena + r.off * (int64_t)io.B;
+        case REF_X: return const_cast<float*>(io.x);
+        case REF_COND: return const_cast<float*>(io.cond);
+        case REF_OUT: return io.out;
         default: return nullptr;
     }
 }
 
+// what a GroupNorm op asks of the kernel that writes its (A, B) table: GnArgs of its own launch, GnOut of a conv that finalizes it
+template <class G>
+void mcvd_model::gn_params(G& g, const Op& n, const Io& io) const {
+    g.coef = resolve(n.coef, io);
+    g.groups = n.groups; g.eps = n.eps; g.mode = n.gn_mode;
+    if (n.gn_mode == 1) { g.p0 = resolve(ops[1].dst, io); g.emb_stride = one_temb_row() ? 0 : NE; g.emb_off = n.emb_off; }
+    else if (n.gn_mode == 2) { g.p0 = blob + n.p0; g.p1 = blob + n.p1; }
+}
+
 // GroupNorm -> (A, B).  Statistics already computed by the producers' epilogues (every source must have them) are finalized by a
 // small kernel (or were, by the producing conv's own K-split reduce pass: gn_done).  Without producer statistics: one pass over the tensor.
-int mcvd_model::launch_gn(const Op& op, const float* x, const void* lab, const float* cond, float* out, int B) {
+int mcvd_model::launch_gn(const Op& op, const Io& io) {
     hipStream_t s = op_stream ? op_stream : ctx->stream;
     const size_t gi = (size_t)(&op - ops.data());
     GnArgs a{};
-    a.x0 = resolve(op.src0, x, cond, out, B);
-    a.x1 = resolve(op.src1, x, cond, out, B);
+    a.x0 = resolve(op.src0, io);
+    a.x1 = resolve(op.src1, io);
     a.C0 = op.src0.C;
     a.C1 = op.src1.kind == REF_NONE ? 0 : op.src1.C;
-    a.groups = op.groups;
-    a.eps = op.eps;
-    a.mode = op.gn_mode;
-    if (op.gn_mode == 1) {
-        a.p0 = resolve(ops[1].dst, x, cond, out, B);
-        a.emb_stride = (uniform_labels && !d.cond_emb) ? 0 : NE;
-        a.emb_off = op.emb_off;
-    } else if (op.gn_mode == 2) {
-        a.p0 = blob + op.p0;
-        a.p1 = blob + op.p1;
-    }
-    a.coef = resolve(op.coef, x, cond, out, B);
-    a.B = B;
+    gn_params(a, op, io);
+    a.B = io.B;
     a.HW = op.H * op.W;
     const int np0 = op.prod0 >= 0 ? stats_np[op.prod0] : 0;
     const int np1 = a.C1 == 0 ? 1 : (op.prod1 >= 0 ? stats_np[op.prod1] : 0);
@@ -708,8 +706,7 @@ int mcvd_model::launch_gn(const Op& op, const float* x, const void* lab, const f
         // launch -- the table keeps the values of the eager first forward.  The upper bound of what ANY scheme that removes these launches
         // (producer-side last arriver, consumer-side reduction) can gain (profiles/r05_tail_launch_bound.txt).
         if (ctx->dbg_skip_finalize && op_stream) return 0;
-        return launch_gn_finalize(a, resolve(ops[op.prod0].stats, x, cond, out, B), np0,
-                                  a.C1 ? resolve(ops[op.prod1].stats, x, cond, out, B) : nullptr, np1, s);
+        return launch_gn_finalize(a, resolve(ops[op.prod0].stats, io), np0, a.C1 ? resolve(ops[op.prod1].stats, io) : nullptr, np1, s);
     }
     return launch_gn_coef(a, s);
 }
@@ -772,8 +769,164 @@ int mcvd_model::launch_gemm_form(const Op& op, const ConvArgs& a, float* buf, hi
     return 0;
 }
 
+// the conv reads the tensor spade_apply materialised, silu(((A x + B)(1 + gamma) + beta) s1 + b2), plainly
+static void read_materialised(ConvArgs& a, const float* tmp) {
+    a.x0 = tmp; a.x1 = nullptr; a.C0 = a.Cin; a.C1 = 0; a.coef = nullptr; a.act = 0; a.gb = nullptr; a.coef2 = nullptr;
+}
+
+ConvArgs mcvd_model::conv_args(const Op& op, const Io& io, bool spade_fused) const {
+    ConvArgs a{};
+    a.x0 = resolve(op.src0, io);
+    a.x1 = resolve(op.src1, io);
+    a.C0 = op.src0.C;
+    a.C1 = op.src1.kind == REF_NONE ? 0 : op.src1.C;
+    a.coef = resolve(op.coef, io);
+    a.act = op.act;
+    a.wp = packed + op.wp;
+    a.wpw = op.wpw >= 0 ? packed + op.wpw : nullptr;
+    a.wph = (op.wph >= 0 && packed_h_valid) ? packed_h + op.wph : nullptr;      // present only while the option f16x2 or f16x1 is on
+    a.wpb = op.wpb >= 0 ? packed + op.wpb : nullptr;
+    a.bias = packed + op.bias;
+    a.res = resolve(op.res, io);
+    a.out_scale = op.out_scale;
+    a.y = resolve(op.dst, io);
+    a.B = io.B; a.Cin = a.C0 + a.C1; a.CinP = op.CinP; a.Cout = op.Cout; a.CoutP = op.CoutP; a.H = op.H; a.W = op.W; a.ks = op.ks;
+    a.cot = op.cot;
+    a.shape_hint = (op.ks == 1 && ctx->conv_shape1 >= 0) ? ctx->conv_shape1 : ctx->conv_shape;
+    a.wdma = ctx->conv_wdma;
+    a.pgrid = ctx->persist_grid;
+    a.part = (op.ks == 3 && op.H * op.W <= 256) ? ksplit_buf : nullptr;
+    a.part_floats = a.part ? ksplit_floats : 0;
+    if (op.gb.kind != REF_NONE && spade_fused) {
+        a.gb = resolve(op.gb, io);
+        a.coef2 = resolve(op.coef2, io);
+    } else if (op.gb.kind != REF_NONE) {
+        read_materialised(a, resolve(op.tmp, io));
+    }
+    return a;
+}
+
+// which kernel the launch asks for: a forced id (tests), else the tuned or imported table's, remapped to the options in force
+void mcvd_model::select_hint(const Op& op, ConvArgs& a) const {
+    const size_t oi = (size_t)(&op - ops.data());
+    if (conv_kernel(a.shape_hint).family == CF_SPLIT1) {      // forced split-operand 1x1 GEMM (tests): a cout tile that kernel serves
+        const int np = pieces(a.shape_hint);
+        for (int c = 4; c >= 1 && !conv1x1_h2_supported(a, a.cot, np); --c)
+            if (conv1x1_h2_supported(a, c, np)) a.cot = c;
+    }
+    if (!(a.shape_hint < 0 && tuned_B == a.B && oi < tuned_shape.size() && tuned_shape[oi] >= 0)) return;
+    a.shape_hint = tuned_shape[oi];
+    a.cot = tuned_cot[oi];
+    // an imported table from a run under other options: the options win.  f16x2 hints go to their bf16x3 counterparts when
+    // f16x2 is off -- and for convs with a raw input in any case (f16x2 range guard, conv_tuner.h); bf16x3 hints go to the fp32-MFMA
+    // kernels when bf16x3 is off; one-piece hints go to their bf16x3 counterparts when f16x1 is off or the input is raw, in
+    // front of the bf16x3 remap (conv_kernels.h: no_f16x2 / no_f16x1 / no_bf16x3)
+    const bool raw_in = conv_input_raw(op);
+    if (!ctx->f16x1 || raw_in) a.shape_hint = without_f16x1(a.shape_hint);
+    if ((!ctx->f16x2 || raw_in) && without_f16x2(a.shape_hint) != a.shape_hint) {
+        a.shape_hint = without_f16x2(a.shape_hint);
+        if (conv_kernel(a.shape_hint).own_cot && !conv_kernel_usable(a.shape_hint, a)) a.cot = op.cot;
+    }
+    if (!ctx->bf16x3 && without_bf16x3(a.shape_hint) != a.shape_hint) {
+        a.shape_hint = without_bf16x3(a.shape_hint);
+        a.cot = op.cot;
+    }
+}
+
+// SPADE norm in front of the conv (a.gb set): fused into the Winograd loader where that kernel takes the launch, otherwise
+// spade_apply materialises the normalised tensor and the conv reads it plainly
+int mcvd_model::apply_spade(const Op& op, const Io& io, ConvArgs& a) {
+    if (a.shape_hint == CK_RETIRED_SPADE_WINO || a.shape_hint == CK_RETIRED_SPADE_WINO_K2) a.shape_hint = CK_AUTO;      // (a round-5 table)
+    const bool want_fused = ctx->spade_fuse && !ctx->naive_conv && ctx->winograd;
+    ConvArgs t = a;
+    t.shape_hint = a.shape_hint == CK_WINO_K2 ? CK_WINO_K2 : CK_WINO;
+    t.ksplit = k_parts(t.shape_hint);
+    bool fused = want_fused && conv_kernel_usable(CK_WINO, t);
+    if (!fused && t.ksplit == 2) { t.ksplit = 0; t.shape_hint = CK_WINO; fused = want_fused && conv_kernel_usable(CK_WINO, t); }
+    if (fused) {
+        a.shape_hint = t.shape_hint;
+        ++fused_launches[2];
+        return 0;
+    }
+    float* tmp = resolve(op.tmp, io);
+    if (int rc = launch_spade_apply(a.x0, a.C0, a.x1, a.C1, a.coef, a.gb, a.coef2, tmp, a.B, op.H * op.W, op_stream ? op_stream : ctx->stream)) return rc;
+    read_materialised(a, tmp);
+    return 0;
+}
+
+// the norm over this conv's output: if the launch ends in a K-split reduce pass over 8 x 8 / 16 x 16 planes, that pass writes
+// the norm's (A, B) table too (gn.cpp: ksplit_reduce_gn_kernel) and the norm's own launch is skipped
+void mcvd_model::set_gn_producer(const Op& op, const Io& io, ConvArgs& a) {
+    gn_done[op.gn_next] = 0;
+    if (ctx->gn_producer && ctx->gn_stats && a.stats && op.ks == 3 && !ctx->dbg_skip_finalize) gn_params(a.gno, ops[op.gn_next], io);
+}
+
+// the q|k|v projection of an attention block: where the launch goes to the three-piece 1x1 GEMM and the attention op will run
+// the three-piece kernel on a device of its own, K and V leave this kernel pre-split (conv1x1_h2.cpp KV -> attn_h2p_kernel)
+void mcvd_model::set_kv_presplit(const Op& op, const Io& io, ConvArgs& a) {
+    kv_live[op.attn_op] = 0;
+    const Op& at = ops[op.attn_op];
+    const bool want = ctx->attn_presplit && !ctx->naive_conv && ctx->bf16x3 && !ctx->f16x2 && (ctx->naive_attn == 0 || ctx->naive_attn == 4) &&
+                      !(ctx->share_fence && mcvd_ctx_shares_device(ctx)) && attn_h2p_supported(at.Cout, at.heads, at.H * at.W) && a.shape_hint == CK_GEMM1_BF16X3;
+    if (!want) return;
+    ConvArgs t = a;
+    t.kv_img = resolve(op.kv, io);
+    t.kv_C = at.Cout;
+    t.kv_D = at.Cout / at.heads;
+    if (conv1x1_h2_kv_supported(t, t.cot)) {
+        a = t;
+        kv_live[op.attn_op] = 1;
+    }
+}
+
+int mcvd_model::launch_conv_op(const Op& op, const Io& io) {
+    hipStream_t s = op_stream ? op_stream : ctx->stream;
+    const size_t oi = (size_t)(&op - ops.data());
+    ConvArgs a = conv_args(op, io, true);
+    MCVD_REQUIRE(a.x0 && (a.C1 == 0 || a.x1), "forward: module %d needs a conditioning tensor (cond is NULL)", op.module);
+    // (a.gb is already set here; select_hint asks only the 1x1 kernels whether they take `a`, and only the Winograd rule reads gb, of a 3x3)
+    select_hint(op, a);
+    if (op.gb.kind != REF_NONE)
+        if (int rc = apply_spade(op, io, a)) return rc;
+    // epilogue statistics from the 3x3 (Winograd) producers; the 1x1 GEMM's epilogue can emit them too, but its 16*COT
+    // 32-lane reductions per wave cost the NIN_3 launches more than the norms they spare save (measured): "gn_stats" = 2 only
+    // (the split-operand 1x1 GEMM emits them cheaply from its transposed epilogue)
+    a.stats = (ctx->gn_stats && op.stats.kind != REF_NONE && !ctx->naive_conv && (op.ks == 3 || ctx->gn_stats >= 2 || conv_kernel(a.shape_hint).family == CF_SPLIT1))
+                  ? resolve(op.stats, io) : nullptr;
+    if (ran_kernel.size() != ops.size()) ran_kernel.assign(ops.size(), -1);
+    if (kv_live.size() != ops.size()) kv_live.assign(ops.size(), 0);
+    if (gn_done.size() != ops.size()) gn_done.assign(ops.size(), 0);
+    if (op.gn_next >= 0) set_gn_producer(op, io, a);
+    if (op.attn_op >= 0) set_kv_presplit(op, io, a);
+    if (ctx->naive_conv) {
+        stats_np[oi] = 0;
+        ran_kernel[oi] = -2;
+        return launch_conv_naive(a, s);
+    }
+    if (conv_kernel(a.shape_hint).family == CF_GEMM3) {
+        if (gemm_form_usable(op, a)) {
+            const int rc = launch_gemm_form(op, a, resolve(op.alt_buf, io), s);
+            stats_np[oi] = a.stats ? last_conv_stats_np() : 0;
+            ran_kernel[oi] = op.alt_kind;
+            return rc;
+        }
+        a.shape_hint = CK_AUTO;          // (forced for the whole network, or a table of another build: the dispatcher's own choice)
+        a.cot = op.cot;
+    }
+    const int rc = launch_conv_mfma(a, s);
+    stats_np[oi] = a.stats ? last_conv_stats_np() : 0;
+    ran_kernel[oi] = last_conv_kernel();
+    if (rc == 0 && a.gno.coef && last_conv_gn_fused()) {
+        gn_done[op.gn_next] = 1;
+        ++fused_launches[3];
+    }
+    return rc;
+}
+
 int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const float* cond, float* out, int B) {
     hipStream_t s = op_stream ? op_stream : ctx->stream;
+    const Io io{x, cond, out, B};
+    auto at = [&](const TRef& r) { return resolve(r, io); };      // NULL for a TRef the op does not have
     switch (op.kind) {
         case OP_TEMB: {
             if (temb_row_live) return 0;      // this forward's row of the call's table is already in ops[1].dst (use_temb_row)
@@ -782,175 +935,23 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
             const float* w1 = blob + params[find_param("unet.all_modules.1.weight")].off;
             const float* b1 = blob + params[find_param("unet.all_modules.1.bias")].off;
             const float* emb = d.cond_emb ? blob + params[find_param("unet.all_modules.2.weight")].off : nullptr;
-            // uniform labels (and no per-row mask embedding): one row serves the batch
-            return launch_temb_mlp(lab, labels_f32, packed + freqs_off, w0, b0, w1, b1, resolve(op.dst, x, cond, out, B),
-                                   (uniform_labels && !d.cond_emb) ? 1 : B, d.ngf, T, emb, cond_mask, s);
+            return launch_temb_mlp(lab, labels_f32, packed + freqs_off, w0, b0, w1, b1, at(op.dst), one_temb_row() ? 1 : B, d.ngf, T, emb, cond_mask, s);
         }
         case OP_DENSE:
             if (temb_row_live) return 0;
-            return launch_dense_all(resolve(op.src0, x, cond, out, B), packed + dense_wt, packed + dense_bias,
-                                    resolve(op.dst, x, cond, out, B), (uniform_labels && !d.cond_emb) ? 1 : B, T, NE, s);
+            return launch_dense_all(at(op.src0), packed + dense_wt, packed + dense_bias, at(op.dst), one_temb_row() ? 1 : B, T, NE, s);
         case OP_GN:
-            return launch_gn(op, x, lab, cond, out, B);
-        case OP_CONV: {
-            ConvArgs a{};
-            a.x0 = resolve(op.src0, x, cond, out, B);
-            a.x1 = resolve(op.src1, x, cond, out, B);
-            a.C0 = op.src0.C;
-            a.C1 = op.src1.kind == REF_NONE ? 0 : op.src1.C;
-            MCVD_REQUIRE(a.x0 && (a.C1 == 0 || a.x1), "forward: module %d needs a conditioning tensor (cond is NULL)", op.module);
-            a.coef = op.coef.kind == REF_NONE ? nullptr : resolve(op.coef, x, cond, out, B);
-            a.act = op.act;
-            a.wp = packed + op.wp;
-            a.wpw = op.wpw >= 0 ? packed + op.wpw : nullptr;
-            a.wph = (op.wph >= 0 && packed_h_valid) ? packed_h + op.wph : nullptr;      // present only while the option f16x2 or f16x1 is on
-            a.wpb = op.wpb >= 0 ? packed + op.wpb : nullptr;
-            a.bias = packed + op.bias;
-            a.res = op.res.kind == REF_NONE ? nullptr : resolve(op.res, x, cond, out, B);
-            a.out_scale = op.out_scale;
-            a.y = resolve(op.dst, x, cond, out, B);
-            a.B = B;
-            a.Cin = a.C0 + a.C1;
-            a.CinP = op.CinP;
-            a.Cout = op.Cout;
-            a.CoutP = op.CoutP;
-            a.H = op.H;
-            a.W = op.W;
-            a.ks = op.ks;
-            a.cot = op.cot;
-            a.shape_hint = (op.ks == 1 && ctx->conv_shape1 >= 0) ? ctx->conv_shape1 : ctx->conv_shape;
-            a.wdma = ctx->conv_wdma;
-            a.pgrid = ctx->persist_grid;
-            a.part = (op.ks == 3 && op.H * op.W <= 256) ? ksplit_buf : nullptr;
-            a.part_floats = a.part ? ksplit_floats : 0;
-            const size_t oi = (size_t)(&op - ops.data());
-            if (conv_kernel(a.shape_hint).family == CF_SPLIT1) {      // forced split-operand 1x1 GEMM (tests): a cout tile that kernel serves
-                const int np = pieces(a.shape_hint);
-                for (int c = 4; c >= 1 && !conv1x1_h2_supported(a, a.cot, np); --c)
-                    if (conv1x1_h2_supported(a, c, np)) a.cot = c;
-            }
-            if (a.shape_hint < 0 && tuned_B == B && oi < tuned_shape.size() && tuned_shape[oi] >= 0) {
-                a.shape_hint = tuned_shape[oi];
-                a.cot = tuned_cot[oi];
-                // an imported table from a run under other options: the options win.  f16x2 hints go to their bf16x3 counterparts when
-                // f16x2 is off -- and for convs with a raw input in any case (f16x2 range guard, below); bf16x3 hints go to the fp32-MFMA
-                // kernels when bf16x3 is off; one-piece hints go to their bf16x3 counterparts when f16x1 is off or the input is raw, in
-                // front of the bf16x3 remap (conv_kernels.h: no_f16x2 / no_f16x1 / no_bf16x3)
-                const bool raw_in = conv_input_raw(op);
-                if ((!ctx->f16x1 || raw_in) && without_f16x1(a.shape_hint) != a.shape_hint) a.shape_hint = without_f16x1(a.shape_hint);
-                if ((!ctx->f16x2 || raw_in) && without_f16x2(a.shape_hint) != a.shape_hint) {
-                    a.shape_hint = without_f16x2(a.shape_hint);
-                    if (conv_kernel(a.shape_hint).own_cot && !conv_kernel_usable(a.shape_hint, a)) a.cot = op.cot;
-                }
-                if (!ctx->bf16x3 && without_bf16x3(a.shape_hint) != a.shape_hint) {
-                    a.shape_hint = without_bf16x3(a.shape_hint);
-                    a.cot = op.cot;
-                }
-            }
-            // epilogue statistics from the 3x3 (Winograd) producers; the 1x1 GEMM's epilogue can emit them too, but its 16*COT
-            // 32-lane reductions per wave cost the NIN_3 launches more than the norms they spare save (measured): "gn_stats" = 2 only
-            if (op.gb.kind != REF_NONE) {
-                // SPADE norm in front of this conv: fused into the Winograd loader where that kernel takes the launch, otherwise
-                // spade_apply materialises silu(((A x + B)(1 + gamma) + beta) s1 + b2) and the conv reads it plainly
-                a.gb = resolve(op.gb, x, cond, out, B);
-                a.coef2 = op.coef2.kind == REF_NONE ? nullptr : resolve(op.coef2, x, cond, out, B);
-                if (a.shape_hint == CK_RETIRED_SPADE_WINO || a.shape_hint == CK_RETIRED_SPADE_WINO_K2) a.shape_hint = CK_AUTO;      // (a round-5 table)
-                const bool want_fused = ctx->spade_fuse && !ctx->naive_conv && ctx->winograd;
-                ConvArgs t = a;
-                t.shape_hint = a.shape_hint == CK_WINO_K2 ? CK_WINO_K2 : CK_WINO;
-                t.ksplit = k_parts(t.shape_hint);
-                bool fused = want_fused && conv_kernel_usable(CK_WINO, t);
-                if (!fused && t.ksplit == 2) { t.ksplit = 0; t.shape_hint = CK_WINO; fused = want_fused && conv_kernel_usable(CK_WINO, t); }
-                if (fused) {
-                    a.shape_hint = t.shape_hint;
-                    ++fused_launches[2];
-                } else {
-                    float* tmp = resolve(op.tmp, x, cond, out, B);
-                    if (int rc = launch_spade_apply(a.x0, a.C0, a.x1, a.C1, a.coef, a.gb, a.coef2, tmp, B, op.H * op.W, s)) return rc;
-                    a.x0 = tmp; a.x1 = nullptr; a.C0 = a.Cin; a.C1 = 0; a.coef = nullptr; a.act = 0; a.gb = nullptr; a.coef2 = nullptr;
-                }
-            }
-            // (the split-operand 1x1 GEMM emits them cheaply from its transposed epilogue)
-            a.stats = (ctx->gn_stats && op.stats.kind != REF_NONE && !ctx->naive_conv && (op.ks == 3 || ctx->gn_stats >= 2 || conv_kernel(a.shape_hint).family == CF_SPLIT1))
-                          ? resolve(op.stats, x, cond, out, B) : nullptr;
-            if (ran_kernel.size() != ops.size()) ran_kernel.assign(ops.size(), -1);
-            if (kv_live.size() != ops.size()) kv_live.assign(ops.size(), 0);
-            if (gn_done.size() != ops.size()) gn_done.assign(ops.size(), 0);
-            if (op.gn_next >= 0) {
-                // the norm over this conv's output: if the launch ends in a K-split reduce pass over 8 x 8 / 16 x 16 planes, that pass writes
-                // the norm's (A, B) table too (gn.cpp: ksplit_reduce_gn_kernel) and the norm's own launch is skipped
-                gn_done[op.gn_next] = 0;
-                const Op& g = ops[op.gn_next];
-                if (ctx->gn_producer && ctx->gn_stats && a.stats && op.ks == 3 && !ctx->dbg_skip_finalize) {
-                    a.gno.coef = resolve(g.coef, x, cond, out, B);
-                    a.gno.groups = g.groups;
-                    a.gno.eps = g.eps;
-                    a.gno.mode = g.gn_mode;
-                    if (g.gn_mode == 1) {
-                        a.gno.p0 = resolve(ops[1].dst, x, cond, out, B);
-                        a.gno.emb_stride = (uniform_labels && !d.cond_emb) ? 0 : NE;
-                        a.gno.emb_off = g.emb_off;
-                    } else if (g.gn_mode == 2) {
-                        a.gno.p0 = blob + g.p0;
-                        a.gno.p1 = blob + g.p1;
-                    }
-                }
-            }
-            if (op.attn_op >= 0) {
-                // the q|k|v projection of an attention block: where the launch goes to the three-piece 1x1 GEMM and the attention op will run
-                // the three-piece kernel on a device of its own, K and V leave this kernel pre-split (conv1x1_h2.cpp KV -> attn_h2p_kernel)
-                kv_live[op.attn_op] = 0;
-                const Op& at = ops[op.attn_op];
-                const bool want = ctx->attn_presplit && !ctx->naive_conv && ctx->bf16x3 && !ctx->f16x2 && (ctx->naive_attn == 0 || ctx->naive_attn == 4) &&
-                                  !(ctx->share_fence && mcvd_ctx_shares_device(ctx)) && attn_h2p_supported(at.Cout, at.heads, at.H * at.W) && a.shape_hint == CK_GEMM1_BF16X3;
-                if (want) {
-                    ConvArgs t = a;
-                    t.kv_img = resolve(op.kv, x, cond, out, B);
-                    t.kv_C = at.Cout;
-                    t.kv_D = at.Cout / at.heads;
-                    if (conv1x1_h2_kv_supported(t, t.cot)) {
-                        a = t;
-                        kv_live[op.attn_op] = 1;
-                    }
-                }
-            }
-            if (ctx->naive_conv) {
-                stats_np[oi] = 0;
-                ran_kernel[oi] = -2;
-                return launch_conv_naive(a, s);
-            }
-            if (conv_kernel(a.shape_hint).family == CF_GEMM3) {
-                if (gemm_form_usable(op, a)) {
-                    const int rc = launch_gemm_form(op, a, resolve(op.alt_buf, x, cond, out, B), s);
-                    stats_np[oi] = a.stats ? last_conv_stats_np() : 0;
-                    ran_kernel[oi] = op.alt_kind;
-                    return rc;
-                }
-                a.shape_hint = CK_AUTO;          // (forced for the whole network, or a table of another build: the dispatcher's own choice)
-                a.cot = op.cot;
-            }
-            const int rc = launch_conv_mfma(a, s);
-            stats_np[oi] = a.stats ? last_conv_stats_np() : 0;
-            ran_kernel[oi] = last_conv_kernel();
-            if (rc == 0 && a.gno.coef && last_conv_gn_fused()) {
-                gn_done[op.gn_next] = 1;
-                ++fused_launches[3];
-            }
-            return rc;
-        }
+            return launch_gn(op, io);
+        case OP_CONV:
+            return launch_conv_op(op, io);
         case OP_FIR: {
-            const float* gb = op.gb.kind == REF_NONE ? nullptr : resolve(op.gb, x, cond, out, B);
-            return launch_fir2(resolve(op.src0, x, cond, out, B),
-                               op.coef.kind == REF_NONE ? nullptr : resolve(op.coef, x, cond, out, B), op.act, op.up,
-                               resolve(op.dst, x, cond, out, B), B, op.src0.C, op.H, op.W, gb,
-                               gb ? gb + (size_t)op.src0.C * op.H * op.W : nullptr,
-                               op.coef2.kind == REF_NONE ? nullptr : resolve(op.coef2, x, cond, out, B),
-                               op.dst2.kind == REF_NONE ? nullptr : resolve(op.dst2, x, cond, out, B), s, ctx->fir_form);
+            const float* gb = at(op.gb);
+            return launch_fir2(at(op.src0), at(op.coef), op.act, op.up, at(op.dst), B, op.src0.C, op.H, op.W, gb,
+                               gb ? gb + (size_t)op.src0.C * op.H * op.W : nullptr, at(op.coef2), at(op.dst2), s, ctx->fir_form);
         }
         case OP_NEAREST:
             MCVD_REQUIRE(cond, "forward: SPADE model needs the conditioning tensor");
-            return launch_nearest_resize(resolve(op.src0, x, cond, out, B), resolve(op.dst, x, cond, out, B), B * op.src0.C,
-                                         d.image_size, d.image_size, op.H, op.W, s);
+            return launch_nearest_resize(at(op.src0), at(op.dst), B * op.src0.C, d.image_size, d.image_size, op.H, op.W, s);
         case OP_CONDNOISE: {
             // cond <- sqrt(a[t]) cond + sqrt(1 - a[t]) z, a fresh z per forward (ncsnpp_more.py:755-768)
             MCVD_REQUIRE(cond, "forward: noise_in_cond model needs the conditioning tensor");
@@ -977,29 +978,23 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
                 ++cond_noise_draw;
                 z = cond_z;
             }
-            return launch_cond_noise(cond, z, alphas_dev, static_cast<const int64_t*>(lab), d.num_classes,
-                                     resolve(op.dst, x, cond, out, B), B, per, s);
+            return launch_cond_noise(cond, z, alphas_dev, static_cast<const int64_t*>(lab), d.num_classes, at(op.dst), B, per, s);
         }
         case OP_COEF2: {
             // the FIRST table op of the plan fills every table of the forward in one launch (they all read the fused Dense_0 row, which
             // is complete before any of them); the others are no-ops.  All tables are arena tensors.
             const int self = (int)(&op - ops.data());
+            const int emb_stride = one_temb_row() ? 0 : NE;
             if (coef2_desc_dev && coef2_count > 1) {
                 if (self != coef2_first) return 0;
-                return launch_coef2_all(resolve(ops[1].dst, x, cond, out, B), (uniform_labels && !d.cond_emb) ? 0 : NE, coef2_desc_dev,
-                                        coef2_count, coef2_cmax, arena, B, s);
+                return launch_coef2_all(at(ops[1].dst), emb_stride, coef2_desc_dev, coef2_count, coef2_cmax, arena, B, s);
             }
-            return launch_coef2(resolve(ops[1].dst, x, cond, out, B), (uniform_labels && !d.cond_emb) ? 0 : NE, op.emb_off,
-                                resolve(op.dst, x, cond, out, B), B, op.Cout, s);
+            return launch_coef2(at(ops[1].dst), emb_stride, op.emb_off, at(op.dst), B, op.Cout, s);
         }
         case OP_APPLY:
-            return launch_spade_apply(resolve(op.src0, x, cond, out, B), op.src0.C, resolve(op.src1, x, cond, out, B),
-                                      op.src1.kind == REF_NONE ? 0 : op.src1.C, resolve(op.coef, x, cond, out, B),
-                                      resolve(op.gb, x, cond, out, B),
-                                      op.coef2.kind == REF_NONE ? nullptr : resolve(op.coef2, x, cond, out, B),
-                                      resolve(op.dst, x, cond, out, B), B, op.H * op.W, s);
-        case OP_ATTN:
-        {
+            return launch_spade_apply(at(op.src0), op.src0.C, at(op.src1), op.src1.kind == REF_NONE ? 0 : op.src1.C, at(op.coef), at(op.gb),
+                                      at(op.coef2), at(op.dst), B, op.H * op.W, s);
+        case OP_ATTN: {
             // (option share_fence, off since round 6 found and removed the cause: a context that shares its device -- another process, or another
             // stream of this one -- keeps the split-operand attention kernels off it: api.cpp, mcvd_ctx_shares_device)
             const bool shared = ctx->share_fence && mcvd_ctx_shares_device(ctx);
@@ -1009,11 +1004,10 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
             if (ai < kv_live.size() && kv_live[ai]) {                     // K and V were written pre-split by the projection of this forward
                 kv_live[ai] = 0;
                 ++fused_launches[0];
-                rc = launch_attention_h2p(resolve(op.src0, x, cond, out, B), resolve(op.kv, x, cond, out, B), resolve(op.dst, x, cond, out, B), B,
-                                          op.Cout, op.heads, op.H * op.W, s);
+                rc = launch_attention_h2p(at(op.src0), at(op.kv), at(op.dst), B, op.Cout, op.heads, op.H * op.W, s);
             } else {
                 // (which kernel: attn_kernels.h, attn_kernel_for)
-                rc = launch_attention(ctx->naive_attn, shared ? 0 : ctx->f16x2, shared ? 0 : ctx->bf16x3, resolve(op.src0, x, cond, out, B), resolve(op.dst, x, cond, out, B), B,
+                rc = launch_attention(ctx->naive_attn, shared ? 0 : ctx->f16x2, shared ? 0 : ctx->bf16x3, at(op.src0), at(op.dst), B,
                                       op.Cout, op.heads, op.H * op.W, s);
             }
             ran_attn[ai] = last_attention_kernel();
@@ -1025,8 +1019,17 @@ int mcvd_model::launch_op(const Op& op, const float* x, const void* lab, const f
     }
 }
 
-// Measurement-driven tile selection: for every distinct conv layer shape, time the candidate (pixel tile, cout tile)
-// pairs with HIP events on the real workspace buffers and keep the fastest.  ~0.2 s once per batch size.
+TunerOptions mcvd_model::tuner_options() const {
+    return {ctx->winograd != 0, ctx->conv_dma1 != 0, ctx->bf16x3 != 0, ctx->f16x2 != 0, ctx->f16x1 != 0, ctx->spade_fuse != 0, ctx->conv_wdma != 0};
+}
+
+TunerLayer mcvd_model::tuner_layer(const Op& op, int B) const {
+    const int cin = op.src0.C + (op.src1.kind == REF_NONE ? 0 : op.src1.C);
+    return {op.ks, op.H, op.W, B, cin, op.Cout, op.CoutP, op.cot, conv_wino_cout_tile(op.Cout), conv_input_raw(op), op.gb.kind != REF_NONE, op.alt_kind};
+}
+
+// Measurement-driven kernel selection: for every distinct conv layer shape, time the candidates the rule of conv_tuner.h offers it
+// with HIP events on the real workspace buffers and keep the fastest.  ~0.2 s once per batch size.
 int mcvd_model::autotune(int B) {
     hipStream_t s = ctx->stream;
     tuned_shape.assign(ops.size(), -1);
@@ -1039,160 +1042,53 @@ int mcvd_model::autotune(int B) {
     struct Key { int ks, H, cin, cout, coef, res; bool operator<(const Key& o) const {
         return std::tie(ks, H, cin, cout, coef, res) < std::tie(o.ks, o.H, o.cin, o.cout, o.coef, o.res); } };
     std::map<Key, std::pair<int, int>> best;
-    float* scratch_io = arena;      // stands in for the caller's x / cond / out during tuning
+    const Io io{arena, arena, arena, B};      // the arena stands in for the caller's x / cond / out during tuning
+    const TunerOptions opts = tuner_options();
     for (size_t i = 0; i < ops.size(); ++i) {
         const Op& op = ops[i];
         if (op.kind != OP_CONV) continue;
-        const int cin = op.src0.C + (op.src1.kind == REF_NONE ? 0 : op.src1.C);
-        Key k{op.ks, op.H, cin, op.Cout, (op.coef.kind != REF_NONE ? 1 : 0) + (op.gb.kind != REF_NONE ? 2 : 0) + (op.coef2.kind != REF_NONE ? 4 : 0),
+        const TunerLayer layer = tuner_layer(op, B);
+        Key k{op.ks, op.H, layer.Cin, op.Cout, (op.coef.kind != REF_NONE ? 1 : 0) + (op.gb.kind != REF_NONE ? 2 : 0) + (op.coef2.kind != REF_NONE ? 4 : 0),
               op.res.kind != REF_NONE};
         auto it = best.find(k);
         if (it == best.end()) {
-            ConvArgs a{};
-            a.x0 = resolve(op.src0, scratch_io, scratch_io, scratch_io, B);
-            a.x1 = resolve(op.src1, scratch_io, scratch_io, scratch_io, B);
-            a.C0 = op.src0.C;
-            a.C1 = op.src1.kind == REF_NONE ? 0 : op.src1.C;
-            a.coef = op.coef.kind == REF_NONE ? nullptr : resolve(op.coef, scratch_io, scratch_io, scratch_io, B);
-            a.act = op.act;
-            a.wp = packed + op.wp;
-            a.wpw = op.wpw >= 0 ? packed + op.wpw : nullptr;
-            a.wph = (op.wph >= 0 && packed_h_valid) ? packed_h + op.wph : nullptr;      // present only while the option f16x2 or f16x1 is on
-            a.wpb = op.wpb >= 0 ? packed + op.wpb : nullptr;
-            a.bias = packed + op.bias;
-            a.res = op.res.kind == REF_NONE ? nullptr : resolve(op.res, scratch_io, scratch_io, scratch_io, B);
-            a.out_scale = op.out_scale;
-            a.y = resolve(op.dst, scratch_io, scratch_io, scratch_io, B);
-            a.B = B; a.Cin = cin; a.CinP = op.CinP; a.Cout = op.Cout; a.CoutP = op.CoutP; a.H = op.H; a.W = op.W; a.ks = op.ks;
-            a.wdma = ctx->conv_wdma;
-            a.pgrid = ctx->persist_grid;
-            a.part = (op.ks == 3 && op.H * op.W <= 256) ? ksplit_buf : nullptr;
-            a.part_floats = a.part ? ksplit_floats : 0;
-            const bool spade_fused = op.gb.kind != REF_NONE && ctx->spade_fuse && ctx->winograd;
-            if (spade_fused) {
-                a.gb = resolve(op.gb, scratch_io, scratch_io, scratch_io, B);
-                a.coef2 = op.coef2.kind == REF_NONE ? nullptr : resolve(op.coef2, scratch_io, scratch_io, scratch_io, B);
-            } else if (op.gb.kind != REF_NONE) {           // unfused: the conv sees the materialised tensor
-                a.x0 = resolve(op.tmp, scratch_io, scratch_io, scratch_io, B);
-                a.x1 = nullptr; a.C0 = cin; a.C1 = 0; a.coef = nullptr; a.act = 0;
-            }
+            ConvArgs a = conv_args(op, io, opts.spade_fuse && opts.winograd);
+            a.shape_hint = CK_AUTO;          // (not a forced conv_shape: every candidate sets its own id and cout tile before it is asked or timed)
+            ConvArgs t = a;                  // the conv as a 1x1 GEMM + its copy / shift pass (gemm_form_args), with the statistics the forward asks of it
+            t.shape_hint = op.alt_kind;
+            t.stats = (ctx->gn_stats && op.stats.kind != REF_NONE) ? resolve(op.stats, io) : nullptr;
+            float* buf = resolve(op.alt_buf, io);
             float best_ms = 1e30f;
             std::pair<int, int> choice{-1, op.cot};
-            auto time_candidate = [&](int shape, int cot) -> int {
-                a.cot = cot;
-                a.shape_hint = shape;
-                if (launch_conv_mfma(a, s)) return 0;                     // warm-up (and validity check)
+            // one candidate: a launch as warm-up and validity check (refused: no candidate), three launches between two events, kept if strictly faster
+            auto time_candidate = [&](int id, int cot, auto&& launch) -> int {
+                if (launch()) return 0;
                 MCVD_HIP_CHECK(hipEventRecord(e0, s));
                 for (int r = 0; r < 3; ++r)
-                    if (int rc = launch_conv_mfma(a, s)) return rc;
+                    if (int rc = launch()) return rc;
                 MCVD_HIP_CHECK(hipEventRecord(e1, s));
                 MCVD_HIP_CHECK(hipEventSynchronize(e1));
                 float ms = 0.f;
                 MCVD_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-                if (ms < best_ms) { best_ms = ms; choice = {shape, cot}; }
+                if (ms < best_ms) { best_ms = ms; choice = {id, cot}; }
                 return 0;
             };
-            auto offer = [&](int id, int cot) -> int {                      // a kernel of the table, timed where it takes this layer with this cout tile
+            auto usable = [&](int id, int cot) {
+                if (conv_kernel(id).family == CF_GEMM3) { t.cot = cot; return gemm_form_usable(op, t); }
                 a.cot = cot;
-                return conv_kernel_usable(id, a) ? time_candidate(id, cot) : 0;
+                return conv_kernel_usable(id, a);
             };
-            const int cots[2] = {op.cot, 1};
-            for (int ci = 0; ci < (op.cot == 1 ? 1 : 2); ++ci) {
-                for (int shape = CK_TILE256; shape <= CK_WINO; ++shape) {
-                    if (spade_fused && conv_kernel_usable(CK_WINO, a) && shape != CK_WINO) continue;   // SPADE prologue: the Winograd kernel only
-                    if (shape == CK_TILE_SPLITK && (op.ks != 3 || !ctx->conv_wdma)) continue;          // split-K with double-buffered weights
-                    if (shape == CK_WINO && (ci > 0 || !ctx->winograd || !conv_kernel_usable(CK_WINO, a))) continue;   // own cout tile
-                    const int bpx = shape == CK_TILE256 ? 256 : shape == CK_TILE128 ? 128 : 64;
-                    const bool fits = bpx % op.W == 0 && (bpx / op.W <= op.H ? op.H % (bpx / op.W) == 0 : (bpx / op.W) % op.H == 0);
-                    if (shape != CK_WINO && !fits) continue;
-                    if (int rc = time_candidate(shape, cots[ci])) return rc;
+            auto time_kernel = [&](int id, int cot) -> int {
+                if (conv_kernel(id).family == CF_GEMM3) {
+                    t.cot = cot;
+                    if (gemm_form_args(op, t, buf).cot != cot) return 0;      // (the GEMM would run another cout tile: that one is timed as itself)
+                    return time_candidate(id, cot, [&] { return launch_gemm_form(op, t, buf, s); });
                 }
-            }
-            a.cot = op.cot;
-            if (op.alt_kind && !spade_fused && op.gb.kind == REF_NONE) {         // the conv as a 1x1 GEMM on the three-piece kernel + its copy / shift pass
-                ConvArgs t = a;
-                t.shape_hint = op.alt_kind;
-                t.stats = (ctx->gn_stats && op.stats.kind != REF_NONE) ? resolve(op.stats, scratch_io, scratch_io, scratch_io, B) : nullptr;
-                float* buf = resolve(op.alt_buf, scratch_io, scratch_io, scratch_io, B);
-                for (int c = 4; c >= 1; --c) {
-                    t.cot = c;
-                    if (!gemm_form_usable(op, t)) break;
-                    if (gemm_form_args(op, t, buf).cot != c) continue;
-                    if (launch_gemm_form(op, t, buf, s)) continue;            // warm-up (and validity check)
-                    MCVD_HIP_CHECK(hipEventRecord(e0, s));
-                    for (int r = 0; r < 3; ++r)
-                        if (int rc = launch_gemm_form(op, t, buf, s)) return rc;
-                    MCVD_HIP_CHECK(hipEventRecord(e1, s));
-                    MCVD_HIP_CHECK(hipEventSynchronize(e1));
-                    float ms = 0.f;
-                    MCVD_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-                    if (ms < best_ms) { best_ms = ms; choice = {op.alt_kind, c}; }
-                }
-            }
-            if (op.ks == 3 && ctx->winograd)               // the K split fills the CUs on 8x8 layers
-                if (int rc = offer(CK_WINO_K2, op.cot)) return rc;
-            // (region, cout tile) pairs of a Winograd launch: few of them leave CUs idle, and the deeper K splits are offered
-            const bool g8 = op.H == 8 && op.W == 8;
-            const long pairs = op.ks == 3 ? (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout))) : 0;
-            // (a layer of more than WINO_MAX_CIN channels has no 2-way split to fall back on -- 4 parts are the shallowest Winograd launch that takes
-            // it -- so it is offered the 4-way ids at every batch; the 8-way one on the terms of every other layer)
-            const bool few_pairs = op.ks == 3 && (2 * pairs < 1024 || wino_needs_4_parts(cin));
-            if (op.ks == 3 && ctx->winograd && ctx->bf16x3 && !spade_fused) {     // Winograd on the bf16 pipe, three exact pieces per operand
-                for (int id : {CK_WINO3, CK_WINO3_K2, CK_WINO3P, CK_WINO3P_K2})    // (persistent: the staging pipeline runs on across the items of a CU)
-                    if (int rc = offer(id, op.cot)) return rc;
-                // 4 / 8 K parts are offered where the 2-way split leaves the chip with less than a few workgroups per CU (the measurement
-                // decides; above that the reduce pass only costs)
-                if (few_pairs) {
-                    for (int id : {CK_WINO3_K4, CK_WINO3P_K4})
-                        if (int rc = offer(id, op.cot)) return rc;
-                    if (4 * pairs < 1024)
-                        if (int rc = offer(CK_WINO3_K8, op.cot)) return rc;
-                }
-            }
-            // f16x2 range guard: the two-piece fp16 kernels see NORMALISED inputs only -- GroupNorm-ed (a.coef set: O(1) by construction) or
-            // SPADE-normalised, which here is the tensor spade_apply materialises (a.coef == nullptr at the launch, and as bounded as the
-            // other up to the cond-derived gamma / beta: an overflow there ends as NaN in eps, which the non-finite scan reports as
-            // MCVD_ERANGE).  A conv over a RAW tensor (stem, shortcuts, NIN_3, the SPADE prep convs) has no bound on its input and stays on
-            // the fp32-range kernels.  With spade_fuse = 1 the modulation stays in the fp32 Winograd loader: no fp16 kernel has that loader.
-            const bool f16_ok = ctx->f16x2 && !conv_input_raw(op);
-            if (op.ks == 3 && ctx->winograd && f16_ok && !spade_fused) {          // Winograd on the fp16 pipe, two-piece operands
-                for (int id : {CK_WINO2H, CK_WINO2H_K2})
-                    if (int rc = offer(id, op.cot)) return rc;
-                if (few_pairs)                                                    // (the 4-way split: where the three-piece kernel is offered it)
-                    if (int rc = offer(CK_WINO2H_K4, op.cot)) return rc;
-            }
-            // ... one-piece operands (the draft arithmetic "f16x1"): the same convs, under the same guard.  The 1x1 GEMMs below and the
-            // attention have no one-piece form: they stay where f16x2 / bf16x3 put them
-            const bool f16x1_ok = ctx->f16x1 && !conv_input_raw(op);
-            if (op.ks == 3 && ctx->winograd && f16x1_ok && !spade_fused) {
-                for (int id : {CK_WINO1H, CK_WINO1H_K2})
-                    if (int rc = offer(id, op.cot)) return rc;
-                if (few_pairs)
-                    if (int rc = offer(CK_WINO1H_K4, op.cot)) return rc;
-            }
-            if (op.ks == 1 && ctx->conv_dma1) {        // the 1x1 GEMMs, cout tiles of their own
-                // small cout tiles first: the sweep of every 1x1 layer shape (profiles/r02_conv1x1_candidates.txt) has tiles 1-3 winning
-                // everywhere; 6 / 9 never did
-                static const int g1_cots[] = {2, 1, 3, 4, 6, 9};
-                for (int id : {CK_DMA1, CK_DMA1_CK32}) {
-                    int tried = 0;
-                    for (int c : g1_cots) {
-                        a.cot = c;
-                        if ((op.CoutP / 32) % c != 0 || tried >= 3 || !conv_kernel_usable(id, a)) continue;
-                        ++tried;
-                        if (int rc = time_candidate(id, c)) return rc;
-                    }
-                }
-                if (f16_ok)                                 // the split-operand GEMMs, cout tiles 1..4: two fp16 pieces ...
-                    for (int c = 4; c >= 1; --c)
-                        if (int rc = offer(CK_GEMM1_F16X2, c)) return rc;
-                if (ctx->bf16x3)                            // ... three exact bf16 pieces
-                    for (int c = 4; c >= 1; --c)
-                        if (int rc = offer(CK_GEMM1_BF16X3, c)) return rc;
-                if (int rc = offer(CK_DMA1_PX64, 1)) return rc;              // 256-pixel tiles, cout tiles 1 / 2
-                if ((op.CoutP / 32) % 2 == 0)
-                    if (int rc = offer(CK_DMA1_PX64, 2)) return rc;
-            }
+                a.cot = cot;
+                a.shape_hint = id;
+                return time_candidate(id, cot, [&] { return launch_conv_mfma(a, s); });
+            };
+            if (int rc = tuner_candidates(layer, opts, usable, time_kernel)) return rc;
             it = best.emplace(k, choice).first;
         }
         tuned_shape[i] = it->second.first;
@@ -1209,8 +1105,7 @@ int mcvd_model::autotune(int B) {
 // "f16x2" = 0 must really mean that no two-piece fp16 kernel runs, "f16x1" = 0 that no one-piece kernel does.  Called before a table is looked up and before one is imported
 // (mcvd_model_set_tuning stamps its table with the options in force at the import).
 void mcvd_model::sync_tuning_options() {
-    const int sig = (ctx->winograd ? 1 : 0) | (ctx->conv_dma1 ? 2 : 0) | (ctx->bf16x3 ? 4 : 0) | (ctx->f16x2 ? 8 : 0) |
-                    (ctx->spade_fuse ? 16 : 0) | (ctx->conv_wdma ? 32 : 0) | (ctx->f16x1 ? 64 : 0);
+    const int sig = tuner_options().signature();
     if (sig != tuned_sig) {
         if (tuned_sig >= 0) { tuned_cache.clear(); tuned_B = 0; }
         tuned_sig = sig;
@@ -1242,21 +1137,19 @@ int mcvd_model::ensure_f16x2_weights() {
 
 // Partial-output buffer of the K-split Winograd layers (H*W <= 256): `parts` x B x Cout x HW floats for the DEEPEST split anything can
 // select at this batch (it was 8 parts for every model and batch, ~200 MB for config 2 at B = 64 where no layer ever takes more
-// than 2): 2 parts everywhere; 4 / 8 where the autotuner's own rule offers the 4- / 8-part kernels (few (region, cout tile) pairs:
-// autotune()), where a test forces one of them (conv_shape), or where an installed table for this batch names one.
+// than 2): 2 parts everywhere; 4 / 8 where the rule autotune() is about to enumerate offers a 4- / 8-part kernel (conv_tuner.h:
+// tuner_deepest_split), where a test forces one of them (conv_shape), or where an installed table for this batch names one.
 int mcvd_model::ensure_ksplit(int B) {
     size_t need = 0;
     const std::vector<int>* table = nullptr;
     auto it = tuned_cache.find(B);
     if (it != tuned_cache.end() && it->second.first.size() == ops.size()) table = &it->second.first;
+    const bool will_tune = ctx->autotune && !table && tuned_B != B;
     for (size_t i = 0; i < ops.size(); ++i) {
         const Op& op = ops[i];
         if (!(op.kind == OP_CONV && op.ks == 3 && op.wpw >= 0 && op.H * op.W <= 256)) continue;
         int parts = 2;
-        const bool g8 = op.H == 8 && op.W == 8;
-        const long pairs = (g8 ? (B + 1) / 2 : (long)B * (op.H / 8) * (op.W / 16)) * (op.CoutP / (32 * conv_wino_cout_tile(op.Cout)));
-        const bool wide = wino_needs_4_parts(op.src0.C + (op.src1.kind == REF_NONE ? 0 : op.src1.C));        // autotune() offers 4 parts at every batch
-        if (ctx->autotune && !table && tuned_B != B && (2 * pairs < 1024 || wide)) parts = 4 * pairs < 1024 ? 8 : 4;    // the candidates autotune() is about to time
+        if (will_tune) parts = std::max(parts, tuner_deepest_split(tuner_layer(op, B), tuner_options()));
         auto deepen = [&](int shape) { parts = std::max(parts, k_parts(shape)); };
         deepen(ctx->conv_shape);
         if (table) deepen((*table)[i]);

@@ -7,6 +7,7 @@
 
 #include "../../include/mcvd_hip.h"
 #include "common.h"
+#include "conv_tuner.h"
 
 struct mcvd_ctx {
     int device = 0;
@@ -239,7 +240,6 @@ struct mcvd_model {
     long fused_launches[4] = {0, 0, 0, 0};   // mcvd_model_fused_launches: pre-split attention blocks, fused SPADE norms, convs with the SPADE loader,
                                              // norms finalized by their producer's K-split reduce pass
     std::vector<signed char> gn_done;       // per OP_GN of the forward in flight: 1 = its table was written by the producing conv's last pass
-    int launch_gn(const mcvd::Op& op, const float* x, const void* labels, const float* cond, float* out, int B);
     std::vector<int> ran_kernel;      // per conv op: the kernel family its last launch REALLY ran (last_conv_kernel(); -2 the naive kernel,
                                       //    -1 never launched): what mcvd_model_op_kernel reports
     std::vector<int> ran_attn;        // per OP_ATTN: the kernel (attn_kernels.h: AttnKernel) its last launch ran, -1 never launched: mcvd_model_op_attention_kernel
@@ -250,6 +250,9 @@ struct mcvd_model {
     std::map<int, std::pair<std::vector<int>, std::vector<int>>> tuned_cache;
     int autotune(int B);
     void sync_tuning_options();
+    // what the candidate rule (conv_tuner.h) reads of the context and of a conv op: autotune() enumerates with them, ensure_ksplit sizes by them
+    mcvd::TunerOptions tuner_options() const;
+    mcvd::TunerLayer tuner_layer(const mcvd::Op& op, int B) const;
 
     // per-op HIP event timing (bench.py roofline): events are recorded on the ctx stream around each op of ONE forward
     std::vector<hipEvent_t> ev;
@@ -306,10 +309,24 @@ struct mcvd_model {
     int labels_f32 = 0;            // the labels of the forward in flight are float [B] instead of int64 [B] (mcvd_unet_forward_ft)
     int forward(const float* x, const void* labels, const float* cond, float* out, int B);
     int forward_unchecked(const float* x, const void* labels, const float* cond, float* out, int B);
+    // the buffers of the forward in flight: what a TRef of the plan resolves against (autotune(): the arena stands in for x, cond and out)
+    struct Io { const float* x; const float* cond; float* out; int B; };
+    float* resolve(const mcvd::TRef& r, const Io& io) const;                 // NULL for REF_NONE
+    bool one_temb_row() const { return uniform_labels && !d.cond_emb; }     // uniform labels and no per-row mask embedding: one row serves the batch, read with stride 0
     int launch_op(const mcvd::Op& op, const float* x, const void* labels, const float* cond, float* out, int B);
+    int launch_gn(const mcvd::Op& op, const Io& io);
+    template <class G> void gn_params(G& g, const mcvd::Op& n, const Io& io) const;      // G: GnArgs or GnOut (model.cpp)
+    // a conv op's launch arguments over `io`, everything but what only a real forward sets (the table's hint, stats, gno, kv_*).  A SPADE norm in
+    // front: spade_fused leaves it to the kernel's loader (gb, coef2), otherwise the conv reads the tensor spade_apply materialises in op.tmp.
+    // launch_conv_op and autotune() both build here: the tuner times the launch the forward makes
+    mcvd::ConvArgs conv_args(const mcvd::Op& op, const Io& io, bool spade_fused) const;
+    int launch_conv_op(const mcvd::Op& op, const Io& io);
+    void select_hint(const mcvd::Op& op, mcvd::ConvArgs& a) const;                             // launch_conv_op's stages, in order
+    int apply_spade(const mcvd::Op& op, const Io& io, mcvd::ConvArgs& a);
+    void set_gn_producer(const mcvd::Op& op, const Io& io, mcvd::ConvArgs& a);
+    void set_kv_presplit(const mcvd::Op& op, const Io& io, mcvd::ConvArgs& a);
     // 3x3 conv as a 1x1 GEMM on the three-piece kernel (shape ids 22 / 23; kernels/conv_gemm_forms.cpp)
     bool gemm_form_usable(const mcvd::Op& op, const mcvd::ConvArgs& a) const;
     mcvd::ConvArgs gemm_form_args(const mcvd::Op& op, const mcvd::ConvArgs& a, float* buf) const;
     int launch_gemm_form(const mcvd::Op& op, const mcvd::ConvArgs& a, float* buf, hipStream_t s);
-    float* resolve(const mcvd::TRef& r, const float* x, const float* cond, float* out, int B) const;
 };
